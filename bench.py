@@ -13,9 +13,11 @@ parameter gradients are averaged with ONE all-reduce per step (global batch 36*N
 --shard samples = every rank holds the same 36 rows and 200 of the 200*N samples per row, the row (max, sum-exp)
 pairs are all-gathered and one all-reduce sums the gradients.
 
-Prints ONE JSON line (< 6 KB: compact_line) on rank 0 with `roofline` for the dominant kernel (the decoder launch) and
-`cpu_baseline` (the oracle's op-by-op CPU restatement of the same step, timed here).  `--all-legs` also runs the other
-BASELINE configurations and the Training.run() / unchanged-spec legs and writes everything to bench_extra.json."""
+Prints ONE JSON line (< 6 KB: compact_line) on rank 0.  A plain run sets up, warms up, times the K steps and prints the
+line (`roofline` and `cpu_baseline` null).  `--full` also measures `roofline` for the dominant kernel (the decoder launch)
+and `cpu_baseline` (the oracle's op-by-op CPU restatement of the same step, timed here) and writes everything to
+bench_extra.json; `--all-legs` (implies --full) also runs the other BASELINE configurations and the Training.run() /
+unchanged-spec legs.  `--dump-outputs DIR` writes the last timed step's loss and the trained parameters to DIR."""
 import argparse
 import json
 import math
@@ -32,7 +34,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 B_ROWS, N_IWAE, N_TIMES, N_STATES, N_PARAMS = 36, 200, 86, 8, 35
-SETUP_SECONDS = float(os.environ.get("VIHDS_BENCH_SETUP_SECONDS", "0.3"))  # untimed graph launches ahead of the W warm-up steps
+SETUP_STEPS = int(os.environ.get("VIHDS_BENCH_SETUP_STEPS", "4096"))  # untimed graph-replayed steps ahead of the W warm-up steps
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs
 MULTI_RANK_WATCHDOG_S = 300  # a multi-rank graph path that has not finished by then gives way to the eager line taken before it
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 
@@ -109,6 +112,21 @@ def emit_line(full):
     except OSError:
         named = None
     emit(compact_line(full, named))
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs DIR: what a caller of the timed step holds after its last step -- the loss (-ELBO) and every trained
+    parameter after that step's Adam update -- as DIR/<name>.npy in float32, so that two builds can be compared output for
+    output on the same seeded inputs."""
+    arrays = {"loss": loss}
+    arrays.update(model.named_parameters())
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def load_pmc(path):
@@ -446,14 +464,15 @@ def run_workload(a, name, min_seconds=None, bounded_cpu=False):
     if not np.isfinite(final):
         raise SystemExit("non-finite objective %r after the timed passes: not a valid bench run" % final)
 
-    # ---- roofline: the step's own ODE launches, re-issued back to back ---------------------------------------------
+    # ---- roofline (--full): the step's own ODE launches, re-issued back to back -------------------------------------
     rec = ops.LaunchRecorder()
-    ops.TIMER = rec
-    if mode == "train":
-        training.step(batch)
-    else:
-        training._evaluation_device_side(batch, S)  # (the pass's own launches, eager: a graph replay records none)
-    ops.TIMER = None
+    if a.full:
+        ops.TIMER = rec
+        if mode == "train":
+            training.step(batch)
+        else:
+            training._evaluation_device_side(batch, S)  # (the pass's own launches, eager: a graph replay records none)
+        ops.TIMER = None
     ode = model.decoder.ode_model
     T = int(batch.times.shape[0])
     P = len(model.encoder.names)
@@ -549,7 +568,7 @@ def run_workload(a, name, min_seconds=None, bounded_cpu=False):
                                    "data parallel over rows x%d (one gradient all-reduce per step)" % world)},
         "final_objective": final, "roofline": roofline,
     }
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         # the oracle on this box's host cores: a training step (white-box models and, since round 4, dr_blackbox) or an
         # evaluation pass; the evaluation shape's sample is 36 of its 234 rows (the pass is row-wise independent; 234 rows
         # x 1000 samples of eager [B,S] tensors would be minutes), scaled to passes of the full shape
@@ -916,6 +935,100 @@ def issue_bound(kernel_name, mean_us):
     return None
 
 
+def headline_roofline(a, model, settings, batch, training, n_iwae_model):
+    """`--full`: the decoder launch and the ODE kernels of the headline step, re-issued back to back between HIP events,
+    against SURVEY 8d's fixed byte numerator (`roofline` in the line)."""
+    from vihds import ops
+
+    # (training.step needs a live autograd graph; the direct launches below reuse the resident batch and the model)
+    kt = ode_kernel_times(model, settings, batch, n_iwae_model, a.roofline_steps)
+    # the step's own decoder launch (sampling + conditioning + sweeps), re-issued back to back with its own arguments
+    rec = ops.LaunchRecorder()
+    ops.TIMER = rec
+    training.step(batch)
+    ops.TIMER = None
+    step_launch = rec.calls.get("decoder_step")
+    if step_launch is not None:
+        st = torch.cuda.current_stream()
+        for _ in range(3):
+            step_launch()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(a.roofline_steps):
+            step_launch()
+        e1.record(st)
+        torch.cuda.synchronize()
+        kt["ode_step"] = {"mean_us": e0.elapsed_time(e1) * 1e3 / a.roofline_steps, "launches": a.roofline_steps}
+    fwd_b, bwd_b = algorithmic_bytes(B_ROWS, N_IWAE)
+    solver_id = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4}[a.solver]
+    lanes = B_ROWS * N_IWAE <= 16384  # the library's automatic choice (vihds_dr_lanes.hpp)
+    kname = {k: ("void vihds::dr_lane_%s_kernel<1, %d, true>(vihds::OdeArgs)" % (k[4:], solver_id)) if lanes else
+                ("void vihds::%s_kernel<vihds::DrConstant<1>, %d>(vihds::OdeArgs)" % (k, solver_id))
+             for k in ("ode_fwd", "ode_bwd")}
+    # the decoder launch: the time-parallel kernel (csrc/vihds_dr_scan.hpp), ITEMS = steps per lane
+    scan_items = (N_TIMES - 1 + 31) // 32
+    kname["ode_fused"] = "void vihds::dr_scan_train_kernel<1, %d, %d>(vihds::OdeArgs)" % (solver_id, scan_items)
+    kname["ode_step"] = ("void vihds::dr_scan_train_theta_kernel<1, %d, %d>(vihds::OdeArgs, int, "
+                         "vihds::ThetaStageArgs)" % (solver_id, scan_items))
+    theta_b = 4 * (2 * N_PARAMS * B_ROWS * N_IWAE + 2 * B_ROWS * N_IWAE)  # the sampling stage's u, theta, log q, log p
+    # SURVEY 8d's fixed numerator for every form of the decoder launch: 30 729 600 + 20 822 400 = 51 552 000 B; the
+    # sampling stage's bytes (theta_b) are reported next to it, never added to it
+    nbytes = {"ode_fwd": fwd_b, "ode_bwd": bwd_b, "ode_fused": fwd_b + bwd_b, "ode_step": fwd_b + bwd_b}
+
+    def gbs(nb, us):
+        return nb / (us * 1e-6) / 1e9
+
+    # HBM traffic per launch from the PMC passes committed under profiles/ (newest set that has this kernel)
+    import glob
+    pmc_kernels, pmc_name, pmc_stale = {}, None, None
+    for pmc_file in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic.json")), reverse=True):
+        ks, fresh = load_pmc(pmc_file)
+        if kname["ode_step" if "ode_step" in kt else "ode_fused"] in ks:
+            if fresh:
+                pmc_kernels, pmc_name = ks, os.path.basename(pmc_file)
+            else:  # counters of other kernel code are not this kernel's traffic
+                pmc_stale = os.path.basename(pmc_file)
+            break
+
+    def entry(k):
+        pmc = pmc_kernels.get(kname[k])
+        return {"kernel": kname[k], "mean_us": kt[k]["mean_us"], "achieved": gbs(nbytes[k], kt[k]["mean_us"]),
+                "algorithmic_bytes_per_launch": nbytes[k], "traffic": pmc["hbm_bytes_corrected"] if pmc else None}
+
+    fused_step = not a.two_kernel_ode and lanes
+    if fused_step and "ode_step" in kt:
+        dom, others = "ode_step", ["ode_fused", "ode_fwd", "ode_bwd"]
+    elif fused_step:
+        dom, others = "ode_fused", ["ode_fwd", "ode_bwd"]
+    else:
+        dom = "ode_bwd" if kt["ode_bwd"]["mean_us"] >= kt["ode_fwd"]["mean_us"] else "ode_fwd"
+        others = ["ode_fwd" if dom == "ode_bwd" else "ode_bwd", "ode_fused"]
+    others = [k for k in others if k in kt]
+    d = entry(dom)
+    roofline = {
+        "bound": "hbm", "kernel": d["kernel"], "achieved": d["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": d["achieved"] / HBM_PEAK_GBS, "traffic": d["traffic"],
+        "traffic_source": ("profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, same workload, same "
+                           "kernel sources: csrc_sha16 checked)" % pmc_name) if d["traffic"] is not None else
+                          ("none: newest profiles/%s was measured on other kernel sources (csrc_sha16 differs); re-run "
+                           "tests/probe/profile_set.sh" % pmc_stale) if pmc_stale else None,
+        "algorithmic_bytes_per_launch": d["algorithmic_bytes_per_launch"], "mean_us": d["mean_us"],
+        "launches_timed": kt[dom]["launches"],
+        "timing": "back-to-back launches of the kernel between one HIP event pair on the launch stream",
+        "numerator_note": ("fixed SURVEY 8d numerator: the bytes the forward + adjoint pair moves when the trajectory "
+                           "goes through HBM (30 729 600 + 20 822 400 B).  The fused kernel keeps the trajectory in LDS and "
+                           "itself moves only the draws, theta, the log-probabilities and d theta (see traffic); the "
+                           "sampling stage that runs in the same launch is NOT in the numerator (theta_stage_bytes)")
+        if fused_step else None,
+        "theta_stage_bytes": theta_b if (fused_step and "ode_step" in kt) else None,
+        "issue_bound": issue_bound(d["kernel"], d["mean_us"]),
+        "other_kernels": [entry(k) for k in others],
+        "step_algorithmic_bytes": fwd_b + bwd_b,
+    }
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -952,8 +1065,8 @@ def main():
                     help="consecutive training steps captured into one hipGraph (single process, resident batch); 1 = one "
                          "graph launch per step as in round 2")
     ap.add_argument("--no-strong-leg", dest="strong_leg", action="store_false",
-                    help="N > 1: skip the extra strong-scaling measurement (config 3's one batch, n_iwae=1000, sample-sharded) "
-                         "that is otherwise added to the line as `strong_scaling_config3`")
+                    help="N > 1 with --full: skip the extra strong-scaling measurement (config 3's one batch, n_iwae=1000, "
+                         "sample-sharded) that is otherwise added to the line as `strong_scaling_config3`")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--all-legs", action="store_true",
                     help="N = 1: after the headline, also time the other single-GPU BASELINE configurations (config3_train, "
@@ -972,7 +1085,17 @@ def main():
                          "real plate data 0.01 trains for 3 000 steps without incident (tests/probe/real_data_long_run.py)")
     ap.add_argument("--no-loop-legs", dest="loop_legs", action="store_false",
                     help="--all-legs: skip the `run_loop` / `real_plate` legs (Training.run() end to end)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline legs, the CPU baseline, the long window behind a "
+                         "short one and (N > 1) the strong-scaling legs, and write bench_extra.json.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline workload: after the timed steps write the last step's loss and the trained parameters as "
+                         "DIR/<name>.npy (float32)")
     a = ap.parse_args()
+    a.full = a.full or a.all_legs
+    if a.dump_outputs and a.workload != "config2":
+        ap.error("--dump-outputs writes the headline workload's outputs (--workload config2)")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as typed: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1) and
         # hand the same arguments on; rank 0 of that job prints the line
@@ -999,7 +1122,7 @@ def main():
         return
     a.solver = a.solver or "rk4"
 
-    from vihds import ops, parallel, synthetic
+    from vihds import parallel, synthetic
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
@@ -1102,6 +1225,7 @@ def main():
             out = step(batch)
         return out
 
+    setup_seconds = 0.0
     if use_graph:
         capture_error = None
         try:
@@ -1111,18 +1235,18 @@ def main():
                 for k in sorted({a.warmup % G, a.steps % G}):  # (and for the graphs that hold the remainders)
                     if k > 1:
                         # (setup, like the capture itself -- not among the W warm-up or the K timed steps: the graph that holds the
-                        # remainder is launched until the device has been busy for SETUP_SECONDS.  A launch after an idle stretch
+                        # remainder is launched for SETUP_STEPS steps, ~0.3 s of device time.  A launch after an idle stretch
                         # runs below the steady rate: the driver's 20-step window measured 13.5-14.1k steps/s behind two such
-                        # launches, 14.4-14.6k behind 32 (gpurun_out/r06d), 14.9k in a long run.  Reported as config.setup_seconds)
-                        # (several ranks: a FIXED number of launches -- every launch holds collectives, and ranks that looked at
-                        # their own clocks would disagree about how many there are)
+                        # launches, 14.4-14.6k behind 32 (profiles/r06_setup_launches.log), 14.9k in a long run.  Reported as
+                        # config.setup_seconds)
+                        # (a FIXED number of launches, never a time: the timed steps then start from the same model state on every
+                        # run, which --dump-outputs relies on; several ranks: 32 launches -- every launch holds collectives)
                         t_setup = time.perf_counter()
-                        for _round in range(4 if multi else 1 << 30):
+                        for _round in range(4 if multi else -(-SETUP_STEPS // (8 * k))):
                             for _ in range(8):
                                 training.graph_step(batch, repeat=k)
                             torch.cuda.synchronize()
-                            if not multi and time.perf_counter() - t_setup >= SETUP_SECONDS:
-                                break
+                        setup_seconds += time.perf_counter() - t_setup
         except Exception as exc:  # noqa: BLE001 -- (reported in the line; the run goes on with eager launches)
             if not multi:
                 raise
@@ -1150,9 +1274,11 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
-    # a short timed window (the driver's --steps 20 is ~2 ms) is also reported over >= 0.5 s of the same replay
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, model)
+    # --full: a short timed window (the driver's --steps 20 is ~2 ms) is also reported over >= 0.5 s of the same replay
     long_run = None
-    if use_graph and elapsed < 0.25:
+    if a.full and use_graph and elapsed < 0.25:
         n_long = int(math.ceil(0.5 / max(elapsed / a.steps, 1e-6) / G)) * G
         barrier()
         t1 = time.perf_counter()
@@ -1175,15 +1301,15 @@ def main():
         gathered = [None] * world
         torch.distributed.all_gather_object(gathered, "rank %d: %s (%s)" % (rank, dev, torch.cuda.get_device_name(local_rank)))
         rank_devices = gathered
-        if a.strong_leg:
+        if a.full and a.strong_leg:
             strong = strong_scaling_leg(a, dev, world, rank)
             strong5 = strong_scaling_leg(a, dev, world, rank, "relay_constant_precisions", 200, "midpoint", "config5")
     eager_ms = None
     if watchdog is not None:
         watchdog.cancel()
         eager_ms = fallback["ms_per_step"]
-    # ---- roofline leg: the same step, eager, with HIP events around every ODE kernel launch -----------------
-    if a.roofline_steps <= 0:
+    # ---- roofline leg (--full): the same step, eager, with HIP events around every ODE kernel launch -----------
+    if a.full and a.roofline_steps <= 0:
         if rank == 0:
             short = {"metric": "ELBO training steps/sec (dr_constant_icml, n_iwae=200)",
                               "value": world * a.steps / elapsed, "unit": "steps/s", "n_gpus": world, "steps": a.steps,
@@ -1205,92 +1331,7 @@ def main():
                                "solver": a.solver, "launch": short.pop("launch"), "world_size": world}
             emit_line(short)
         return
-    # (training.step needs a live autograd graph; the direct launches below reuse the resident batch and the model)
-    kt = ode_kernel_times(model, settings, batch, n_iwae_model, a.roofline_steps)
-    # the step's own decoder launch (sampling + conditioning + sweeps), re-issued back to back with its own arguments
-    rec = ops.LaunchRecorder()
-    ops.TIMER = rec
-    training.step(batch)
-    ops.TIMER = None
-    step_launch = rec.calls.get("decoder_step")
-    if step_launch is not None:
-        st = torch.cuda.current_stream()
-        for _ in range(3):
-            step_launch()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        for _ in range(a.roofline_steps):
-            step_launch()
-        e1.record(st)
-        torch.cuda.synchronize()
-        kt["ode_step"] = {"mean_us": e0.elapsed_time(e1) * 1e3 / a.roofline_steps, "launches": a.roofline_steps}
-    fwd_b, bwd_b = algorithmic_bytes(B_ROWS, N_IWAE)
-    solver_id = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4}[a.solver]
-    lanes = B_ROWS * N_IWAE <= 16384  # the library's automatic choice (vihds_dr_lanes.hpp)
-    kname = {k: ("void vihds::dr_lane_%s_kernel<1, %d, true>(vihds::OdeArgs)" % (k[4:], solver_id)) if lanes else
-                ("void vihds::%s_kernel<vihds::DrConstant<1>, %d>(vihds::OdeArgs)" % (k, solver_id))
-             for k in ("ode_fwd", "ode_bwd")}
-    # the decoder launch: the time-parallel kernel (csrc/vihds_dr_scan.hpp), ITEMS = steps per lane
-    scan_items = (N_TIMES - 1 + 31) // 32
-    kname["ode_fused"] = "void vihds::dr_scan_train_kernel<1, %d, %d>(vihds::OdeArgs)" % (solver_id, scan_items)
-    kname["ode_step"] = ("void vihds::dr_scan_train_theta_kernel<1, %d, %d>(vihds::OdeArgs, int, "
-                         "vihds::ThetaStageArgs)" % (solver_id, scan_items))
-    theta_b = 4 * (2 * N_PARAMS * B_ROWS * N_IWAE + 2 * B_ROWS * N_IWAE)  # the sampling stage's u, theta, log q, log p
-    # SURVEY 8d's fixed numerator for every form of the decoder launch: 30 729 600 + 20 822 400 = 51 552 000 B; the
-    # sampling stage's bytes (theta_b) are reported next to it, never added to it
-    nbytes = {"ode_fwd": fwd_b, "ode_bwd": bwd_b, "ode_fused": fwd_b + bwd_b, "ode_step": fwd_b + bwd_b}
-
-    def gbs(nb, us):
-        return nb / (us * 1e-6) / 1e9
-
-    # HBM traffic per launch from the PMC passes committed under profiles/ (newest set that has this kernel)
-    import glob
-    pmc_kernels, pmc_name, pmc_stale = {}, None, None
-    for pmc_file in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic.json")), reverse=True):
-        ks, fresh = load_pmc(pmc_file)
-        if kname["ode_step" if "ode_step" in kt else "ode_fused"] in ks:
-            if fresh:
-                pmc_kernels, pmc_name = ks, os.path.basename(pmc_file)
-            else:  # counters of other kernel code are not this kernel's traffic
-                pmc_stale = os.path.basename(pmc_file)
-            break
-
-    def entry(k):
-        pmc = pmc_kernels.get(kname[k])
-        return {"kernel": kname[k], "mean_us": kt[k]["mean_us"], "achieved": gbs(nbytes[k], kt[k]["mean_us"]),
-                "algorithmic_bytes_per_launch": nbytes[k], "traffic": pmc["hbm_bytes_corrected"] if pmc else None}
-
-    fused_step = not a.two_kernel_ode and lanes
-    if fused_step and "ode_step" in kt:
-        dom, others = "ode_step", ["ode_fused", "ode_fwd", "ode_bwd"]
-    elif fused_step:
-        dom, others = "ode_fused", ["ode_fwd", "ode_bwd"]
-    else:
-        dom = "ode_bwd" if kt["ode_bwd"]["mean_us"] >= kt["ode_fwd"]["mean_us"] else "ode_fwd"
-        others = ["ode_fwd" if dom == "ode_bwd" else "ode_bwd", "ode_fused"]
-    others = [k for k in others if k in kt]
-    d = entry(dom)
-    roofline = {
-        "bound": "hbm", "kernel": d["kernel"], "achieved": d["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": d["achieved"] / HBM_PEAK_GBS, "traffic": d["traffic"],
-        "traffic_source": ("profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, same workload, same "
-                           "kernel sources: csrc_sha16 checked)" % pmc_name) if d["traffic"] is not None else
-                          ("none: newest profiles/%s was measured on other kernel sources (csrc_sha16 differs); re-run "
-                           "tests/probe/profile_set.sh" % pmc_stale) if pmc_stale else None,
-        "algorithmic_bytes_per_launch": d["algorithmic_bytes_per_launch"], "mean_us": d["mean_us"],
-        "launches_timed": kt[dom]["launches"],
-        "timing": "back-to-back launches of the kernel between one HIP event pair on the launch stream",
-        "numerator_note": ("fixed SURVEY 8d numerator: the bytes the forward + adjoint pair moves when the trajectory "
-                           "goes through HBM (30 729 600 + 20 822 400 B).  The fused kernel keeps the trajectory in LDS and "
-                           "itself moves only the draws, theta, the log-probabilities and d theta (see traffic); the "
-                           "sampling stage that runs in the same launch is NOT in the numerator (theta_stage_bytes)")
-        if fused_step else None,
-        "theta_stage_bytes": theta_b if (fused_step and "ode_step" in kt) else None,
-        "issue_bound": issue_bound(d["kernel"], d["mean_us"]),
-        "other_kernels": [entry(k) for k in others],
-        "step_algorithmic_bytes": fwd_b + bwd_b,
-    }
+    roofline = headline_roofline(a, model, settings, batch, training, n_iwae_model) if a.full else None
     if rank != 0:
         return
     out = {
@@ -1310,7 +1351,7 @@ def main():
                    "solver": a.solver, "n_iwae_per_gpu": N_IWAE, "n_iwae_global": n_iwae_model,
                    "rows_global": B_ROWS * (world if replica is not None else 1),
                    "launch": launch_mode, "steps_per_graph_launch": G, "learning_rate": a.lr,
-                   "setup_seconds": (SETUP_SECONDS if not multi else "32 launches per remainder graph") if use_graph else 0.0,
+                   "setup_seconds": (setup_seconds if not multi else "32 launches per remainder graph") if use_graph else 0.0,
                    "world_size": torch.distributed.get_world_size() if multi else 1, "rank_devices": rank_devices,
                    "dist_backend": torch.distributed.get_backend() if multi else None,
                    "collectives_in_graph": bool(getattr(training, "collectives_captured", False)) if multi else None,
@@ -1324,6 +1365,8 @@ def main():
         "final_loss": final_loss, "roofline": roofline, "strong_scaling_config3": strong,
         "strong_scaling_config5": strong5, "eager_ms_per_step": eager_ms,
     }
+    if not a.full:
+        out["note"] = "roofline, cpu_baseline and the other legs: --full"
     if multi and eager_ms is not None and fallback["steps"] == a.steps and eager_ms < out["ms_per_step"]:
         # Several ranks: BOTH measurements are exactly K steps of the same workload between the same barriers -- the eager one
         # taken first, the hipGraph replay after it.  The captured multi-rank step has never run on more than one GPU; should
@@ -1333,7 +1376,7 @@ def main():
                                "steps_per_graph_launch": G}
         out["value"], out["ms_per_step"] = fallback["value"], eager_ms
         out["config"]["launch"] = "eager (faster than the hipGraph replay on this run: see graph_replay)"
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.solver, batch.observations.detach().cpu())
         out["speedup_vs_cpu_restatement"] = out["value"] / out["cpu_baseline"]["value"]
     if world == 1 and a.all_legs and a.other_configs and not (a.eager or a.host_rng or a.two_kernel_ode):
@@ -1346,7 +1389,10 @@ def main():
             loops = loop_legs_for_default_line(a)
             out["run_loop"], out["real_plate"] = loops["run_loop"], loops["real_plate"]
             out["newton_iters"] = {k: (loops[k] or {}).get("newton_iters") for k in ("run_loop", "real_plate")}
-    emit_line(out)
+    if a.full:
+        emit_line(out)
+    else:  # (a plain run writes no side file: the line is all it measured)
+        emit(compact_line(out))
     if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() == 1:
         try:  # (the one-rank legs: a group left alive aborted in RCCL's teardown now and then, behind the line)
             torch.cuda.synchronize()

@@ -95,3 +95,33 @@ def test_stale_counter_files_are_not_attached(tmp_path):
         p.write_text(json.dumps(d))
         ks, ok = bench.load_pmc(str(p))
         assert ok is fresh and "k" in ks
+
+
+def test_dump_outputs_writes_loss_and_every_parameter_as_float32(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss and the trained parameters, one float32 <name>.npy each, values as held."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.Linear(4, 1))
+    loss = torch.tensor(1.25, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "out"), loss, model)
+    names = {"loss"} | {k for k, _ in model.named_parameters()}
+    assert {f[:-4] for f in os.listdir(tmp_path / "out")} == names
+    for k, v in model.named_parameters():
+        got = np.load(tmp_path / "out" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v.detach().numpy())
+    assert float(np.load(tmp_path / "out" / "loss.npy")) == 1.25
+
+
+def test_dump_outputs_refuses_more_than_the_limit(tmp_path, monkeypatch):
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "out"), torch.tensor(0.0), torch.nn.Linear(8, 8))
+    assert not (tmp_path / "out").exists()
