@@ -182,7 +182,7 @@ class Encoder(nn.Module):
         self.p = p
 
     def _kernel_shape(self, B, data):
-        """struct vihds_encoder_shape for this encoder and batch size (cached)."""
+        """struct vihds_encoder_shape for this encoder and batch size (cached; None once the kernels declined it)."""
         from vihds import hip
 
         if B not in self._shapes:
@@ -203,19 +203,25 @@ class Encoder(nn.Module):
         delta_obs = data.get("delta_obs", None) if hasattr(data, "get") else None  # staged with the batch (graph mode)
         if delta_obs is None:
             delta_obs = obs[:, :, 1: self.n_times] - obs[:, :, : self.n_times - 1]
-        if self.use_kernel and delta_obs.is_cuda:
+        if self.use_kernel and delta_obs.is_cuda and self._kernel_shape(B, data) is not None:
             # one forward / two backward launches instead of the 8 + 15 framework launches below
             from vihds import ops
 
             lh, gh = self.local_heads, self.gcond_heads
-            q_all = ops.EncoderQTables.apply(
-                self._kernel_shape(B, data), delta_obs, data.inputs, data.dev_1hot, self.conditional.conv.weight,
-                self.conditional.conv.bias, self.conditional.lin.weight, self.conditional.lin.bias,
-                None if lh is None else lh.weight, None if lh is None else lh.bias,
-                None if gh is None else gh.weight, self.global_free, self.const_values)
-            q = ChainedDistribution(name="q")
-            q.attach_packed(self.kind, q_all, self.names, lambda chain: self._build_members(chain, q_all), self.q_rows)
-            return q
+            try:
+                q_all = ops.EncoderQTables.apply(
+                    self._kernel_shape(B, data), delta_obs, data.inputs, data.dev_1hot, self.conditional.conv.weight,
+                    self.conditional.conv.bias, self.conditional.lin.weight, self.conditional.lin.bias,
+                    None if lh is None else lh.weight, None if lh is None else lh.bias,
+                    None if gh is None else gh.weight, self.global_free, self.const_values)
+            except ops.EncoderUnsupported:
+                # a shape past the fused kernels' LDS budget (declined before anything was queued): this batch size
+                # takes the module path below from now on
+                self._shapes[B] = None
+            else:
+                q = ChainedDistribution(name="q")
+                q.attach_packed(self.kind, q_all, self.names, lambda chain: self._build_members(chain, q_all), self.q_rows)
+                return q
         encoded = self.conditional(delta_obs)
         local_t = gcond_t = None
         if self.local:

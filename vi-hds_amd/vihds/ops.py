@@ -398,6 +398,11 @@ class FusedTrainingUnsupported(RuntimeError):
     """vihds_ode_logp_grad declined this (model, shape): the caller uses OdeSolveObserve instead."""
 
 
+class EncoderUnsupported(RuntimeError):
+    """vihds_encoder_fwd declined this encoder shape (past the fused kernels' LDS budget) before queuing anything: the
+    caller uses the nn.Module encoder instead."""
+
+
 class OdeLogLikFused(torch.autograd.Function):
     """Training fast path (vihds_ode_logp_grad): per-species log-likelihood [4,B,S] and, in the same launch, the theta
     gradient for a unit upstream gradient; neither trajectory nor x_predict is produced.  backward: the ELBO hands
@@ -851,6 +856,8 @@ class EncoderQTables(torch.autograd.Function):
                                          hip.ptr(local_w), hip.ptr(local_b), hip.ptr(gcond_w), hip.ptr(global_free),
                                          hip.ptr(const_values), hip.ptr(q_all), hip.ptr(pooled), hip.ptr(hidden),
                                          hip.current_stream())
+        if rc == hip.E_UNSUPPORTED:
+            raise EncoderUnsupported(hip.lib().vihds_last_error().decode())
         hip.check(rc, "vihds_encoder_fwd")
         ctx.shape = s
         ctx.save_for_backward(delta_obs, inputs, dev_1hot, conv_w, lin_w, local_w, local_b, gcond_w, global_free,
