@@ -441,8 +441,9 @@ __device__ __forceinline__ void stv(float* p, const float* o) {
   else p[0] = o[0];
 }
 
-// LDS floats the conditioner's staged inputs need (relevance masks, the block's device one-hot rows, default flags:
-// they sit in the VG area, which holds at least items * DR_SCAN_THREADS floats and is dead until the gamma pass)
+// LDS floats the conditioner's staged inputs need (relevance masks, the block's device one-hot rows, default flags):
+// they sit at O_C, behind everything dr_scan_lds_floats counts (the per-step area or the reduction overlay, the time grid
+// and x(T-1)/K per trajectory), so the launch adds them to the block's dynamic LDS
 __host__ __device__ inline size_t dr_scan_theta_floats(int E, int D) {
   return (size_t)E * D + (size_t)DR_SCAN_TPB * D + (size_t)E;
 }
