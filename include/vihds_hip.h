@@ -113,6 +113,14 @@ int vihds_model_n_slots(int model);       /* number of theta slots the kernel re
 const char* vihds_model_slot_name(int model, int slot); /* reference parameter name of a slot */
 int vihds_model_n_weights(const vihds_ode_problem* p);  /* floats in the `weights` buffer (0 if none) */
 
+/* Models generated from a Python definition (vi-hds_amd/vihds/modelgen.py): load the side library libvihds_gen_<tag>.so
+ * built for one of them, check that it was compiled against this library's kernel headers, and return the model id it
+ * runs under (1024 and above, far from the built-in enum vihds_model), or a negative VIHDS_E_* code with the reason in
+ * vihds_last_error(): missing file, missing record symbol, layout / version mismatch.  The same path registered twice
+ * gives the same id.  Every model-generic entry point then takes the id (vihds_model_*, vihds_ode_fwd / _bwd / _bwd_elbo,
+ * vihds_ode_adaptive_grid, vihds_problem_*); the dr-only and lane-specific kernels decline it as for any other model. */
+int vihds_model_register(const char* library_path);
+
 /* Forward: integrate, observe, and reduce the observation log-likelihood over time.
  * traj / xpred / logp may each be NULL to skip that output.  `weights` is NULL for white-box models. */
 int vihds_ode_fwd(const vihds_ode_problem* p, const float* theta, const float* cond, const float* dev1hot,

@@ -1,0 +1,79 @@
+// One model generated from a Python definition (vihds/modelgen.py; see ../vihds_gen_model.hpp) as a side library, built with
+//   -DVIHDS_GEN_HEADER="<generated header>"
+// as ten objects compiled in parallel (Makefile, target `generated`): one per solver (-DVIHDS_ONLY_SOLVER=<id>: the
+// kernels of that solver behind vihds_gen_launch_<id>) and the table object (no VIHDS_ONLY_SOLVER: the GenModelRecord
+// that dispatches to them).  The generated header defines VIHDS_GEN_CORE (the struct) and VIHDS_GEN_NEURAL (0 / 1).
+#include "../vihds_ode_kernels.hpp"
+#include "../vihds_gen_model.hpp"
+
+#ifndef VIHDS_GEN_HEADER
+#error "define VIHDS_GEN_HEADER (the header vihds/modelgen.py wrote)"
+#endif
+#include VIHDS_GEN_HEADER
+
+namespace vihds {
+template <bool NEURAL>
+struct GenSel {
+  using type = VIHDS_GEN_CORE;
+};
+template <>
+struct GenSel<true> {
+  using type = WithPrec<VIHDS_GEN_CORE>;
+};
+using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
+typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, AdaptiveCtl*);
+}  // namespace vihds
+
+#define VIHDS_GEN_CAT2(a, b) a##b
+#define VIHDS_GEN_CAT(a, b) VIHDS_GEN_CAT2(a, b)
+
+#ifdef VIHDS_ONLY_SOLVER
+extern "C" int VIHDS_GEN_CAT(vihds_gen_launch_, VIHDS_ONLY_SOLVER)(bool backward, int solver, const vihds::OdeArgs& a,
+                                                                  hipStream_t st, vihds::AdaptiveCtl* ctl) {
+  using namespace vihds;
+  g_adaptive_ctl = ctl;
+  const int rc = launch_ode<GenM>(backward, solver, a, st);
+  g_adaptive_ctl = nullptr;
+  return rc;
+}
+#else
+#define VIHDS_GEN_DECL(k) \
+  extern "C" int vihds_gen_launch_##k(bool, int, const vihds::OdeArgs&, hipStream_t, vihds::AdaptiveCtl*);
+VIHDS_GEN_DECL(0) VIHDS_GEN_DECL(1) VIHDS_GEN_DECL(2) VIHDS_GEN_DECL(3) VIHDS_GEN_DECL(4) VIHDS_GEN_DECL(5)
+VIHDS_GEN_DECL(6) VIHDS_GEN_DECL(7) VIHDS_GEN_DECL(8)
+static_assert(VIHDS_SOLVER_COUNT == 9, "one object per solver: extend the table and the Makefile");
+namespace vihds {
+// this library's own thread-locals (it does not link against libvihds_hip.so).  Only g_adaptive_ctl is ever set here (by
+// the launch functions above, from their argument): the wrapper in vihds_api.hip declines the sampling stage, the one-pass
+// summaries and the device-resident adaptive solver for registered models before it calls in.
+thread_local AdaptiveCtl* g_adaptive_ctl = nullptr;
+thread_local AdaptiveDevCtl* g_adaptive_dev = nullptr;
+thread_local const ThetaStageArgs* g_theta_stage = nullptr;
+thread_local const SummArgs* g_summ = nullptr;
+template <class M>
+static int n_weights_of(int H) {
+  if constexpr (M::NEURAL_PREC) return M::n_weights(H);
+  else return 0;
+}
+static int n_weights_gen(int H) { return n_weights_of<GenM>(H); }
+static const char* const* slot_names_gen() {
+  static const char* n[GenM::NSLOT];
+  for (int s = 0; s < GenM::NSLOT; ++s) n[s] = GenM::slot_name(s);
+  return n;
+}
+static int launch_gen(bool backward, int solver, const OdeArgs& a, hipStream_t st, AdaptiveCtl* ctl) {
+  static const gen_launch_fn table[VIHDS_SOLVER_COUNT] = {vihds_gen_launch_0, vihds_gen_launch_1, vihds_gen_launch_2,
+                                                          vihds_gen_launch_3, vihds_gen_launch_4, vihds_gen_launch_5,
+                                                          vihds_gen_launch_6, vihds_gen_launch_7, vihds_gen_launch_8};
+  if (solver < 0 || solver >= VIHDS_SOLVER_COUNT) return VIHDS_E_BADARG;
+  return table[solver](backward, solver, a, st, ctl);
+}
+}  // namespace vihds
+
+extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
+  using namespace vihds;
+  static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, GenM::N, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
+                                   slot_names_gen(), n_weights_gen, launch_gen};
+  return &r;
+}
+#endif

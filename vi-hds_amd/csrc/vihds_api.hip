@@ -6,14 +6,21 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <utility>
+
+#include <limits.h>
+#include <stdlib.h>
+#include <unistd.h>
 
 #include "../../include/vihds_hip.h"
 #include "vihds_ode_kernels.hpp"
 #include "vihds_bb_variant.hpp"
+#include "vihds_gen_model.hpp"
 
 #include "vihds_relay_lanes.hpp"
 #include "vihds_relay_lanes.hpp"
@@ -147,7 +154,37 @@ static int check_hip(const char* what) {
 }
 static const char* kPrecNames[4] = {"prec_x", "prec_rfp", "prec_yfp", "prec_cfp"};
 
+// ---- registered models (vihds_gen_model.hpp): ids VIHDS_GEN_MODEL_BASE + k -------------------------------------------
+// ModelEntry holds plain function pointers, so every registration slot k has its own set of wrappers over g_gen[k].  The
+// switches below are thread-locals of THIS library, invisible to the side library: the wrapper declines the sampling stage,
+// the one-pass summaries and the device-resident adaptive solver (none of them exists for a registered model) and hands the
+// host-driven adaptive controller over as an argument.
+static const GenModelRecord* g_gen[VIHDS_GEN_MODEL_MAX];
+static ModelEntry g_gen_entries[VIHDS_GEN_MODEL_MAX];
+static std::atomic<int> g_gen_count{0};
+template <int K>
+struct GenSlot {
+  static int launch(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
+    if (g_theta_stage || g_summ || g_adaptive_dev) return VIHDS_E_UNSUPPORTED;
+    return g_gen[K]->launch(backward, solver, a, st, g_adaptive_ctl);
+  }
+  static int n_slots() { return g_gen[K]->n_slots; }
+  static int n_states() { return g_gen[K]->n_states; }
+  static int n_cond() { return g_gen[K]->n_cond; }
+  static const char* slot_name(int s) { return g_gen[K]->slot_names[s]; }
+};
+template <int... K>
+static ModelEntry gen_entry_of(int k, std::integer_sequence<int, K...>) {
+  static const ModelEntry table[] = {{GenSlot<K>::launch, GenSlot<K>::n_slots, GenSlot<K>::n_states, GenSlot<K>::n_cond,
+                                      GenSlot<K>::slot_name, false}...};
+  return table[k];
+}
+static bool is_registered(int model) {
+  return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
+}
+
 static const ModelEntry* entry(int model) {
+  if (is_registered(model)) return &g_gen_entries[model - VIHDS_GEN_MODEL_BASE];
   if (model < 0 || model >= VIHDS_MODEL_COUNT) return nullptr;
   return kModels[model].launch ? &kModels[model] : nullptr;
 }
@@ -240,6 +277,59 @@ int vihds_debug_newton_hist(unsigned int* hist) {
 }
 const char* vihds_last_error(void) { return g_err; }
 
+int vihds_model_register(const char* library_path) {
+  static std::mutex mu;
+  static std::map<std::string, int> by_path;
+  if (!library_path || !*library_path) return fail(VIHDS_E_BADARG, "vihds_model_register: null or empty path");
+  char resolved[PATH_MAX];
+  if (access(library_path, R_OK) != 0 || !realpath(library_path, resolved)) {
+    std::snprintf(g_err, sizeof(g_err), "vihds_model_register: %s: no such file", library_path);
+    return VIHDS_E_BADARG;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = by_path.find(resolved);
+  if (it != by_path.end()) return it->second;
+  void* h = dlopen(resolved, RTLD_NOW | RTLD_LOCAL);
+  if (!h) {
+    const char* why = dlerror();
+    std::snprintf(g_err, sizeof(g_err), "vihds_model_register: cannot load %s: %s", resolved, why ? why : "?");
+    return VIHDS_E_UNSUPPORTED;
+  }
+  typedef const GenModelRecord* (*record_fn)(void);
+  record_fn f = (record_fn)dlsym(h, "vihds_generated_model_v1");
+  const GenModelRecord* r = f ? f() : nullptr;
+  if (!r) {
+    dlclose(h);
+    std::snprintf(g_err, sizeof(g_err), "vihds_model_register: %s has no vihds_generated_model_v1 record", resolved);
+    return VIHDS_E_UNSUPPORTED;
+  }
+  if (r->abi_version != VIHDS_ABI_VERSION || r->odeargs_size != (int)sizeof(OdeArgs) || r->header_hash != VIHDS_HDR_HASH) {
+    std::snprintf(g_err, sizeof(g_err),
+                  "vihds_model_register: %s was built against other kernel headers (ABI %d, OdeArgs %d bytes, header hash "
+                  "%llx; this library: ABI %d, %d bytes, %llx): rebuild it",
+                  resolved, r->abi_version, r->odeargs_size, r->header_hash, VIHDS_ABI_VERSION, (int)sizeof(OdeArgs),
+                  (unsigned long long)VIHDS_HDR_HASH);
+    dlclose(h);
+    return VIHDS_E_UNSUPPORTED;
+  }
+  if (r->n_slots + (r->neural_prec ? 0 : 4) > VIHDS_MAX_SLOTS || r->n_states < 1 || !r->launch || !r->slot_names ||
+      !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT)) {
+    dlclose(h);
+    return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
+  }
+  const int k = g_gen_count.load(std::memory_order_relaxed);
+  if (k >= VIHDS_GEN_MODEL_MAX) {
+    dlclose(h);
+    return fail(VIHDS_E_UNSUPPORTED, "vihds_model_register: too many registered models in this process");
+  }
+  g_gen[k] = r;
+  g_gen_entries[k] = gen_entry_of(k, std::make_integer_sequence<int, VIHDS_GEN_MODEL_MAX>{});
+  g_gen_entries[k].neural_prec = r->neural_prec != 0;
+  g_gen_count.store(k + 1, std::memory_order_release);  // (entry() sees the slot only once it is filled)
+  by_path[resolved] = VIHDS_GEN_MODEL_BASE + k;
+  return VIHDS_GEN_MODEL_BASE + k;
+}
+
 int vihds_model_n_states(int model) {
   const ModelEntry* e = entry(model);
   return e ? e->n_states() : VIHDS_E_UNSUPPORTED;
@@ -265,6 +355,7 @@ int vihds_model_n_weights(const vihds_ode_problem* p) {
   const ModelEntry* e = entry(p->model);
   if (!e) return VIHDS_E_UNSUPPORTED;
   if (!e->neural_prec) return 0;
+  if (is_registered(p->model)) return g_gen[p->model - VIHDS_GEN_MODEL_BASE]->n_weights(p->n_hidden_prec);
   if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
     if (bb_builtin(p)) return bb_n_weights(p->n_const);
     const BbVariant* v = bb_sized(p);
@@ -521,7 +612,7 @@ static int summ_species(const vihds_ode_problem* p, const ModelEntry* e) {
 int vihds_ode_fwd_summaries_supported(const vihds_ode_problem* p) {
   if (!p) return 0;
   const ModelEntry* e = entry(p->model);
-  if (!e || p->model == VIHDS_MODEL_DR_BLACKBOX || solver_is_adaptive(p->solver)) return 0;
+  if (!e || p->model == VIHDS_MODEL_DR_BLACKBOX || solver_is_adaptive(p->solver) || is_registered(p->model)) return 0;
   if (e->neural_prec && p->n_hidden_prec > 256) return 0;
   // ... and the forward launch of this problem is the thread-per-trajectory kernel (whose integration the second pass
   // repeats bit for bit): asked for, or an evaluation-sized launch
@@ -631,7 +722,9 @@ int vihds_ode_adaptive_grid(const vihds_ode_problem* p, const float* theta, cons
 // ---- torchdiffeq's adaptive algorithm on the device (csrc/vihds_rk_adaptive_device.hpp) -------------------------------------
 static bool adaptive_device_model(const vihds_ode_problem* p, const ModelEntry* e) {
   // (round 5: the white-box models with neural precisions too, when their network has no hidden layer; not dr_blackbox)
-  const bool net_ok = e && (!e->neural_prec || (p->model != VIHDS_MODEL_DR_BLACKBOX && p->n_hidden_prec < 1));
+  // (registered models: the host-driven controller, vihds_ode_adaptive_grid)
+  const bool net_ok = e && !is_registered(p->model) &&
+                      (!e->neural_prec || (p->model != VIHDS_MODEL_DR_BLACKBOX && p->n_hidden_prec < 1));
   return net_ok && p->solver >= VIHDS_SOLVER_DOPRI5 && p->solver <= VIHDS_SOLVER_ADAPTIVE_HEUN &&
          (long long)p->B * p->S <= (long long)ADP_MAX_BLOCKS * ADP_BLOCK;
 }

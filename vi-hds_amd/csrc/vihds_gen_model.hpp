@@ -1,0 +1,39 @@
+// Models generated from a Python definition (vihds/modelgen.py): the generator writes one struct that satisfies the
+// model contract of vihds_models.hpp, and the side library
+//   libvihds_gen_<tag>.so          (make -C vi-hds_amd/csrc generated SRC=<header> TAG=<tag>)
+// compiles the thread-per-trajectory kernels of vihds_ode_kernels.hpp for it (csrc/generated/ode_generated_model.hip).
+// The library exports one record; vihds_model_register (vihds_api.hip) loads it, checks the layout guard and gives the
+// model an id at VIHDS_GEN_MODEL_BASE or above, which every model-generic entry point then serves.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "vihds_args.hpp"
+
+// registered models take ids from here on (far above the built-in enum vihds_model)
+#define VIHDS_GEN_MODEL_BASE 1024
+#define VIHDS_GEN_MODEL_MAX 64
+
+// hash of the kernel headers a library was compiled from (the Makefile passes it to every object that needs it)
+#ifndef VIHDS_HDR_HASH
+#define VIHDS_HDR_HASH 0ull
+#endif
+
+namespace vihds {
+struct AdaptiveCtl;
+struct GenModelRecord {
+  // layout guard: a library built against other kernel headers or another OdeArgs is refused at registration
+  int abi_version;                 // VIHDS_ABI_VERSION
+  int odeargs_size;                // sizeof(OdeArgs)
+  unsigned long long header_hash;  // VIHDS_HDR_HASH
+  int n_states;     // N (incl. the 4 precision states of a neural-precision model)
+  int n_slots;      // kernel theta slots (a neural-precision model's init_prec_* included, constant precisions not)
+  int n_cond;       // treatments read per data row
+  int observe_kind; // ObserveKind
+  int neural_prec;  // 1: WithPrec<> around the generated struct
+  const char* const* slot_names;
+  int (*n_weights)(int n_hidden_prec);  // floats of the neural-precision weight buffer (vihds_model_n_weights)
+  // ctl != nullptr: run the step-size controller of an adaptive solver instead of the integration (as BbVariant::launch)
+  int (*launch)(bool backward, int solver, const OdeArgs& a, hipStream_t st, AdaptiveCtl* ctl);
+};
+}  // namespace vihds
+extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

@@ -26,3 +26,10 @@ LOOKUP = {
     "relay_constant": relay_constant.Relay_Constant,
     "relay_constant_precisions": relay_constant.Relay_Constant_Precisions,
 }
+
+
+def register(cls):
+    """Make a model class selectable from a spec YAML (`model: <cls.model_key>`): the reference's own mechanism, an entry of
+    LOOKUP.  For vihds.modelgen.GeneratedOdeModel subclasses the kernels are generated and registered on first use."""
+    LOOKUP[cls.model_key] = cls
+    return cls

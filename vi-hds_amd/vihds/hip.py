@@ -163,6 +163,7 @@ _PROTOTYPES = {
     "vihds_model_n_slots": (_I, [_I]),
     "vihds_model_slot_name": (ctypes.c_char_p, [_I, _I]),
     "vihds_model_n_weights": (_I, [ctypes.POINTER(OdeProblem)]),
+    "vihds_model_register": (_I, [ctypes.c_char_p]),
     "vihds_ode_fwd": (_I, [ctypes.POINTER(OdeProblem)] + [_P] * 10),
     "vihds_ode_bwd": (_I, [ctypes.POINTER(OdeProblem)] + [_P] * 14),
     "vihds_ode_bwd_elbo": (_I, [ctypes.POINTER(OdeProblem)] + [_P] * 14),

@@ -1,0 +1,822 @@
+"""New ODE models defined in Python and run on generated HIP kernels.
+
+A model is one subclass of GeneratedOdeModel (the plugin surface of the reference's vihds/ode.py:20-96):
+
+    class MyModel(GeneratedOdeModel):
+        model_key = "my_model"
+        species = ["OD", "RFP", ...]                 # ODE states, in order
+        parameters = ["r", "K", ..., "init_x"]       # theta names the kernel reads, in slot order
+        n_conditions = 0                             # treatments read per data row
+        observe_kind = "default"                     # or "direct" (the kinds the kernels implement)
+
+        def __init__(self, config):
+            super().__init__(config)
+            self.precisions = ConstantPrecisions([...])   # or NeuralPrecisions(...), as the built-in models do
+
+        def prepare(self, th, c):          # reference <Model>_RHS.__init__: named effective parameters
+            return {"r": clamp(th.r, 0.0, 4.0), ...}
+        def initial_state(self, th, c):    # reference initialize_state: one entry per species
+            return [th.init_x, ..., 0.0]
+        def rhs(self, t, y, p, c):         # reference OdeFunc.forward: one entry per species
+            return [...]
+
+`c` holds the treatments after clamp(exp(cond) - 1, 1e-12, 1e6) (the c[] contract of csrc/vihds_models.hpp).  The three
+functions use + - * / (unary minus, Python numbers) and the operations of this module: exp, log, pow, sigmoid, tanh and
+clamp (constant bounds).  Each of them dispatches on its arguments:
+  - symbols (when the class is defined): an expression DAG, from which the model struct of vihds_models.hpp and its
+    reverse-mode adjoint are generated as HIP C++ (generate_source);
+  - torch tensors: torch ops, eagerly -- the same definition is then a float64 PyTorch right-hand side (torch_problem).
+On first use the struct is compiled for gfx950 into the side library vi-hds_amd/lib/libvihds_gen_<tag>.so, registered
+with the C ABI (vihds_model_register) and its key added to hip.MODELS: the general training / evaluation path takes it from
+there like any built-in key.  Neural precisions wrap the generated struct in WithPrec<> (nothing generated).
+
+The adjoint of each operation is torch autograd's formula, with one exception kept on purpose: the exponent adjoint of
+pow(a, n) is g * a^n * log(a) everywhere, as csrc pow_vjp computes it for the built-in models.  At a = 0 that is NaN
+(0 * -inf) where autograd masks it to 0 (pow_backward_exponent, base 0 and exponent >= 0); clamp the base away from 0
+(as the reference models do: clamp(K, 1e-12, 1) * c) when the exponent is a parameter.
+"""
+import hashlib
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from vihds import hip
+from vihds.ode import OdeModel
+
+MAX_STATES = 32  # ODE states of a generated model (all of them live in registers of one thread)
+OBSERVE_KINDS = {"default": ("OBS_DEFAULT", 6), "direct": ("OBS_DIRECT", 4)}  # kernel enum, species observe() reads
+OPERATIONS = ("exp", "log", "pow", "sigmoid", "tanh", "clamp")
+
+
+class ModelDefinitionError(TypeError):
+    """A generated model's definition cannot be traced or breaks a limit of the kernels."""
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# expression DAG
+# ---------------------------------------------------------------------------------------------------------------------
+_LEAVES = ("const", "th", "c", "y", "p", "t", "seed")
+_COMMUTATIVE = ("add", "mul")
+
+
+def _control_flow(*_args, **_kw):
+    raise ModelDefinitionError(
+        "a generated model's functions are traced once, symbolically: Python control flow on a model quantity (if, "
+        "and/or, comparisons, bool(), float(), abs(), math.*) is not possible -- write it with the operations %s "
+        "(clamp for bounds)" % ", ".join(OPERATIONS))
+
+
+class Sym(object):
+    """A node of the expression DAG (interned by its graph: equal expressions are one node)."""
+
+    __slots__ = ("g", "op", "args", "val", "id")
+
+    def __init__(self, g, op, args, val, nid):
+        self.g, self.op, self.args, self.val, self.id = g, op, args, val, nid
+
+    def __add__(self, o):
+        return self.g.make("add", (self, o))
+
+    def __radd__(self, o):
+        return self.g.make("add", (o, self))
+
+    def __sub__(self, o):
+        return self.g.make("sub", (self, o))
+
+    def __rsub__(self, o):
+        return self.g.make("sub", (o, self))
+
+    def __mul__(self, o):
+        return self.g.make("mul", (self, o))
+
+    def __rmul__(self, o):
+        return self.g.make("mul", (o, self))
+
+    def __truediv__(self, o):
+        return self.g.make("div", (self, o))
+
+    def __rtruediv__(self, o):
+        return self.g.make("div", (o, self))
+
+    def __neg__(self):
+        return self.g.make("neg", (self,))
+
+    def __pos__(self):
+        return self
+
+    def __pow__(self, o):
+        return self.g.make("pow", (self, o))
+
+    def __rpow__(self, o):
+        return self.g.make("pow", (o, self))
+
+    __bool__ = __float__ = __int__ = __index__ = __abs__ = _control_flow
+    __lt__ = __le__ = __gt__ = __ge__ = __eq__ = __ne__ = _control_flow
+    __hash__ = object.__hash__
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        raise ModelDefinitionError("%s on a model quantity: a generated model can only use + - * / and %s"
+                                   % (getattr(func, "__name__", func), ", ".join(OPERATIONS)))
+
+    def __repr__(self):
+        return "Sym(%s#%d)" % (self.op, self.id)
+
+
+def _fold(op, a, b=None, val=None):
+    """Constant folding in float64 (IEEE semantics: inf / NaN instead of exceptions)."""
+    with np.errstate(all="ignore"):
+        a = np.float64(a)
+        if op == "add": return float(a + b)
+        if op == "sub": return float(a - b)
+        if op == "mul": return float(a * b)
+        if op == "div": return float(a / np.float64(b))
+        if op == "neg": return float(-a)
+        if op == "exp": return float(np.exp(a))
+        if op == "log": return float(np.log(a))
+        if op == "pow": return float(np.power(a, np.float64(b)))
+        if op == "sigmoid": return float(1.0 / (1.0 + np.exp(-a)))
+        if op == "tanh": return float(np.tanh(a))
+        if op == "clamp": return float(min(max(a, val[0]), val[1])) if a == a else float(a)
+        if op == "cpass": return 1.0 if val[0] <= a <= val[1] else 0.0
+    raise AssertionError(op)
+
+
+class Graph(object):
+    """Hash-consed expression DAG: building a node that exists returns that node (common-subexpression elimination);
+    operations on constants are folded; x+0, x*1, x*0, x/1, -(-x), pow(x, 1) simplify."""
+
+    def __init__(self):
+        self.nodes = []
+        self._table = {}
+
+    def _intern(self, op, args, val):
+        key = (op, tuple(a.id for a in args), val)
+        n = self._table.get(key)
+        if n is None:
+            n = Sym(self, op, tuple(args), val, len(self.nodes))
+            self.nodes.append(n)
+            self._table[key] = n
+        return n
+
+    def const(self, v):
+        v = float(v)
+        return self._intern("const", (), 0.0 if v == 0.0 else v)  # (one zero: -0.0 and 0.0 fold together)
+
+    def leaf(self, kind, index):
+        return self._intern(kind, (), index)
+
+    def _arg(self, a):
+        if isinstance(a, Sym):
+            if a.g is not self:
+                raise ModelDefinitionError("a model quantity from another trace was used")
+            return a
+        if isinstance(a, (bool, np.bool_)) or not isinstance(a, (int, float, np.integer, np.floating)):
+            raise ModelDefinitionError("unsupported operand %r of type %s in a generated model (Python numbers and model "
+                                       "quantities only)" % (a, type(a).__name__))
+        return self.const(a)
+
+    def make(self, op, args, val=None):
+        args = tuple(self._arg(a) for a in args)
+        if all(a.op == "const" for a in args):
+            return self.const(_fold(op, *[a.val for a in args], val=val))
+        zero = lambda s: s.op == "const" and s.val == 0.0  # noqa: E731
+        one = lambda s: s.op == "const" and s.val == 1.0  # noqa: E731
+        if op == "add":
+            if zero(args[0]): return args[1]
+            if zero(args[1]): return args[0]
+        elif op == "sub":
+            if zero(args[1]): return args[0]
+            if zero(args[0]): return self.make("neg", (args[1],))
+        elif op == "mul":
+            if zero(args[0]) or zero(args[1]): return self.const(0.0)
+            if one(args[0]): return args[1]
+            if one(args[1]): return args[0]
+            if args[0].op == "const" and args[0].val == -1.0: return self.make("neg", (args[1],))
+            if args[1].op == "const" and args[1].val == -1.0: return self.make("neg", (args[0],))
+        elif op == "div":
+            if one(args[1]): return args[0]
+            if zero(args[0]): return self.const(0.0)
+        elif op == "neg":
+            if args[0].op == "neg": return args[0].args[0]
+        elif op == "pow":
+            if one(args[1]): return args[0]
+        if op in _COMMUTATIVE and args[0].id > args[1].id:
+            args = (args[1], args[0])
+        return self._intern(op, args, val)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the operation namespace (dispatch on argument type)
+# ---------------------------------------------------------------------------------------------------------------------
+def _sym_of(args):
+    for a in args:
+        if isinstance(a, Sym):
+            return a.g
+    return None
+
+
+def _tensor_of(args):
+    return any(isinstance(a, torch.Tensor) for a in args)
+
+
+def _number(x, what):
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise ModelDefinitionError("%s must be a Python number (got %s)" % (what, type(x).__name__))
+    return float(x)
+
+
+def exp(x):
+    g = _sym_of((x,))
+    if g: return g.make("exp", (x,))
+    return torch.exp(x) if _tensor_of((x,)) else math.exp(x)
+
+
+def log(x):
+    g = _sym_of((x,))
+    if g: return g.make("log", (x,))
+    return torch.log(x) if _tensor_of((x,)) else math.log(x)
+
+
+def pow(x, n):  # noqa: A001  (the operation's name in the model namespace)
+    g = _sym_of((x, n))
+    if g: return g.make("pow", (x, n))
+    if _tensor_of((x, n)):
+        return torch.pow(x, n)
+    return math.pow(x, n)
+
+
+def sigmoid(x):
+    g = _sym_of((x,))
+    if g: return g.make("sigmoid", (x,))
+    return torch.sigmoid(x) if _tensor_of((x,)) else 1.0 / (1.0 + math.exp(-x))
+
+
+def tanh(x):
+    g = _sym_of((x,))
+    if g: return g.make("tanh", (x,))
+    return torch.tanh(x) if _tensor_of((x,)) else math.tanh(x)
+
+
+def clamp(x, lo, hi):
+    lo, hi = _number(lo, "clamp's lower bound"), _number(hi, "clamp's upper bound")
+    if not lo <= hi:
+        raise ModelDefinitionError("clamp: lower bound %g above upper bound %g" % (lo, hi))
+    g = _sym_of((x,))
+    if g: return g.make("clamp", (x,), (lo, hi))
+    if _tensor_of((x,)):
+        return torch.clamp(x, lo, hi)
+    return min(max(x, lo), hi)
+
+
+class _Namespace(object):
+    """`op.exp(x)` ...: the operations as one object; any other name is refused with the list."""
+
+    exp, log, pow, sigmoid, tanh, clamp = (staticmethod(f) for f in (exp, log, pow, sigmoid, tanh, clamp))
+
+    def __getattr__(self, name):
+        raise ModelDefinitionError("operation '%s' is not available to generated models (available: + - * / and %s)"
+                                   % (name, ", ".join(OPERATIONS)))
+
+
+op = _Namespace()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# reverse mode
+# ---------------------------------------------------------------------------------------------------------------------
+def _topo(roots):
+    """Nodes reachable from roots, every node after its arguments (deterministic: roots and arguments in order)."""
+    seen, order = set(), []
+    for r in roots:
+        stack = [(r, False)]
+        while stack:
+            n, done = stack.pop()
+            if done:
+                order.append(n)
+                continue
+            if n.id in seen:
+                continue
+            seen.add(n.id)
+            stack.append((n, True))
+            for a in reversed(n.args):
+                if a.id not in seen:
+                    stack.append((a, False))
+    return order
+
+
+def vjp(g, outputs, seeds):
+    """Reverse-mode derivative of the DAG: {leaf node id: adjoint node} for sum_k seeds[k] * d outputs[k] / d leaf.  Each
+    operation's rule is torch autograd's formula (clamp: gradient where lo <= x <= hi; pow: csrc pow_vjp, unmasked at a
+    zero base -- module docstring)."""
+    adj = {}
+
+    def acc(node, contrib):
+        if node.op == "const":
+            return
+        adj[node.id] = g.make("add", (adj[node.id], contrib)) if node.id in adj else contrib
+
+    for o, s in zip(outputs, seeds):
+        if isinstance(o, Sym):
+            acc(o, g._arg(s))
+    order = _topo([o for o in outputs if isinstance(o, Sym)])
+    for n in reversed(order):
+        if n.id not in adj or n.op in _LEAVES:
+            continue
+        gb = adj[n.id]
+        a = n.args
+        if n.op == "add":
+            acc(a[0], gb); acc(a[1], gb)
+        elif n.op == "sub":
+            acc(a[0], gb); acc(a[1], -gb)
+        elif n.op == "mul":
+            acc(a[0], gb * a[1]); acc(a[1], gb * a[0])
+        elif n.op == "div":  # torch: grad / other, -grad * ((self / other) / other)
+            acc(a[0], gb / a[1]); acc(a[1], -(gb * (n / a[1])))
+        elif n.op == "neg":
+            acc(a[0], -gb)
+        elif n.op == "exp":
+            acc(a[0], gb * n)
+        elif n.op == "log":
+            acc(a[0], gb / a[0])
+        elif n.op == "pow":  # pow_vjp: g n a^(n-1), g a^n log(a)  (unmasked at a = 0: see the module docstring)
+            acc(a[0], gb * (a[1] * g.make("pow", (a[0], a[1] - 1.0))))
+            acc(a[1], gb * (n * g.make("log", (a[0],))))
+        elif n.op == "sigmoid":
+            acc(a[0], gb * (n * (1.0 - n)))
+        elif n.op == "tanh":
+            acc(a[0], gb * (1.0 - n * n))
+        elif n.op == "clamp":
+            acc(a[0], gb * g.make("cpass", (a[0],), n.val))
+        elif n.op == "cpass":
+            pass  # piecewise constant
+        else:
+            raise AssertionError(n.op)
+    return adj
+
+
+def evaluate(outputs, env):
+    """Evaluate DAG nodes with torch (float64 in the tests): env maps (leaf kind, index) -> value."""
+    vals = {}
+    for n in _topo([o for o in outputs if isinstance(o, Sym)]):
+        a = [vals[x.id] for x in n.args]
+        if n.op == "const": v = torch.tensor(n.val, dtype=torch.float64)
+        elif n.op in _LEAVES: v = env[(n.op, n.val)]
+        elif n.op == "add": v = a[0] + a[1]
+        elif n.op == "sub": v = a[0] - a[1]
+        elif n.op == "mul": v = a[0] * a[1]
+        elif n.op == "div": v = a[0] / a[1]
+        elif n.op == "neg": v = -a[0]
+        elif n.op == "exp": v = torch.exp(a[0])
+        elif n.op == "log": v = torch.log(a[0])
+        elif n.op == "pow": v = torch.pow(a[0], a[1])
+        elif n.op == "sigmoid": v = torch.sigmoid(a[0])
+        elif n.op == "tanh": v = torch.tanh(a[0])
+        elif n.op == "clamp": v = torch.clamp(a[0], n.val[0], n.val[1])
+        elif n.op == "cpass": v = ((a[0] >= n.val[0]) & (a[0] <= n.val[1])).to(a[0].dtype)
+        else: raise AssertionError(n.op)
+        vals[n.id] = v
+    return [vals[o.id] if isinstance(o, Sym) else torch.tensor(float(o), dtype=torch.float64) for o in outputs]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tracing
+# ---------------------------------------------------------------------------------------------------------------------
+class _Named(object):
+    """th / p: quantities by attribute (th.r) or by key (th["aYFP_PR"])."""
+
+    def __init__(self, values, what):
+        object.__setattr__(self, "_v", dict(values))
+        object.__setattr__(self, "_what", what)
+
+    def __getattr__(self, name):
+        try:
+            return self._v[name]
+        except KeyError:
+            raise ModelDefinitionError("unknown %s '%s' (defined: %s)" % (self._what, name, ", ".join(self._v))) from None
+
+    __getitem__ = __getattr__
+
+    def __setattr__(self, name, value):
+        raise ModelDefinitionError("%s are read-only" % self._what)
+
+
+class _Conditions(object):
+    def __init__(self, values):
+        self._v = list(values)
+
+    def __getitem__(self, q):
+        if not isinstance(q, int) or not 0 <= q < len(self._v):
+            raise ModelDefinitionError("treatment c[%r] out of range: the model declares n_conditions = %d" % (q, len(self._v)))
+        return self._v[q]
+
+    def __len__(self):
+        return len(self._v)
+
+
+class Trace(object):
+    """The three functions of a model class traced into one Graph."""
+
+    def __init__(self, cls):
+        inst = cls.__new__(cls)  # (the functions are methods; nothing of nn.Module is touched by them)
+        self.cls = cls
+        self.g = g = Graph()
+        N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
+        th = _Named([(n, g.leaf("th", s)) for s, n in enumerate(P)], "parameter")
+        cs = [g.leaf("c", q) for q in range(C)]
+        prepared = inst.prepare(th, _Conditions(cs))
+        if not isinstance(prepared, dict) or not all(isinstance(k, str) for k in prepared):
+            raise ModelDefinitionError("%s.prepare must return a dict {name: value}" % cls.__name__)
+        self.p_names = list(prepared)
+        self.p_exprs = [g._arg(prepared[k]) for k in self.p_names]
+        y0 = inst.initial_state(th, _Conditions(cs))
+        self.y0 = self._state_list(y0, "initial_state", N)
+        # rhs sees the effective parameters and the treatments; the kernel's rhs has no c[], so each treatment it reads is
+        # one more effective parameter (copied by prepare, no adjoint)
+        NPU = len(self.p_names)
+        p = _Named([(n, g.leaf("p", k)) for k, n in enumerate(self.p_names)], "effective parameter")
+        self.dy = self._state_list(inst.rhs(g.leaf("t", 0), [g.leaf("y", j) for j in range(N)], p,
+                                            _Conditions([g.leaf("p", NPU + q) for q in range(C)])), "rhs", N)
+        used = {n.val for n in _topo(self.dy) if n.op == "p"}
+        self.c_in_rhs = [q for q in range(C) if NPU + q in used]
+        # remap the treatments rhs reads to consecutive parameter indices behind the named ones
+        self.NP = NPU + len(self.c_in_rhs)
+        self.c_slot = {NPU + q: NPU + k for k, q in enumerate(self.c_in_rhs)}
+
+    def _state_list(self, v, what, N):
+        if not isinstance(v, (list, tuple)) or len(v) != N:
+            raise ModelDefinitionError("%s.%s must return a list of %d entries (one per species)" % (self.cls.__name__, what, N))
+        return [self.g._arg(x) for x in v]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# code generation
+# ---------------------------------------------------------------------------------------------------------------------
+def _lit(v):
+    f = float(np.float32(v))
+    if math.isnan(f): return "__builtin_nanf(\"\")"
+    if math.isinf(f): return "__builtin_inff()" if f > 0 else "(-__builtin_inff())"
+    s = repr(f)
+    if "e" not in s and "." not in s:
+        s += ".0"
+    return s + "f"
+
+
+class _Emitter(object):
+    """Straight-line C++ for some DAG outputs: one `const float` per operation node.  fast=True is the time loop (frcp,
+    fdiv, fexp, sigmoid_f, ftanh); fast=False is prepare / init (IEEE division, expf, tanhf); both use powf / logf."""
+
+    def __init__(self, fast, leaf_names, p_map=None):
+        self.fast, self.leaf_names, self.p_map = fast, leaf_names, p_map or {}
+        self.lines, self.names = [], {}
+
+    def ref(self, n):
+        if n.op == "const": return _lit(n.val)
+        if n.op in _LEAVES:
+            base = self.leaf_names[n.op]
+            idx = self.p_map.get(n.val, n.val) if n.op == "p" else n.val
+            return base if n.op == "t" else "%s[%d]" % (base, idx)
+        return self.names[n.id]
+
+    def expr(self, n):
+        a = [self.ref(x) for x in n.args]
+        f = self.fast
+        if n.op == "add": return "%s + %s" % tuple(a)
+        if n.op == "sub": return "%s - %s" % tuple(a)
+        if n.op == "mul": return "%s * %s" % tuple(a)
+        if n.op == "div":
+            if f and n.args[0].op == "const" and n.args[0].val == 1.0: return "frcp(%s)" % a[1]
+            return ("fdiv(%s, %s)" if f else "%s / %s") % tuple(a)
+        if n.op == "neg": return "-%s" % a[0]
+        if n.op == "exp": return ("fexp(%s)" if f else "expf(%s)") % a[0]
+        if n.op == "log": return "logf(%s)" % a[0]
+        if n.op == "pow":
+            if n.args[1].op == "const" and n.args[1].val == 2.0: return "%s * %s" % (a[0], a[0])
+            return "powf(%s, %s)" % tuple(a)
+        if n.op == "sigmoid": return ("sigmoid_f(%s)" if f else "1.f / (1.f + expf(-%s))") % a[0]
+        if n.op == "tanh": return ("ftanh(%s)" if f else "tanhf(%s)") % a[0]
+        if n.op == "clamp": return "clampf(%s, %s, %s)" % (a[0], _lit(n.val[0]), _lit(n.val[1]))
+        if n.op == "cpass": return "clamp_pass(%s, %s, %s)" % (a[0], _lit(n.val[0]), _lit(n.val[1]))
+        raise AssertionError(n.op)
+
+    def emit(self, assignments):
+        """assignments: [(lhs, '=' or '+=', node)] -> body lines."""
+        for n in _topo([x for _, _, x in assignments]):
+            if n.op in _LEAVES or n.id in self.names:
+                continue
+            name = "v%d" % len(self.names)
+            self.lines.append("    const float %s = %s;" % (name, self.expr(n)))
+            self.names[n.id] = name
+        for lhs, how, n in assignments:
+            self.lines.append("    %s %s %s;" % (lhs, how, self.ref(n)))
+        return self.lines
+
+
+def _leaf_free(node, allowed):
+    return all(n.op not in _LEAVES or n.op == "const" or n.op in allowed for n in _topo([node]))
+
+
+def generate_source(cls, neural=False):
+    """The C++ header of one model: the struct of the vihds_models.hpp contract (adjoints by reverse mode, forward values
+    recomputed inside them) and the switches csrc/generated/ode_generated_model.hip reads.  Deterministic: the same
+    definition gives byte-identical text; its hash (with the kernel headers') names the library."""
+    tr = cls._trace
+    g = tr.g
+    N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
+    NPU = len(tr.p_names)
+    obs_enum = OBSERVE_KINDS[cls.observe_kind][0]
+    sname = "GenModel_" + _ident(cls.model_key)
+
+    # prepare: named parameters, then the treatments rhs reads
+    prep = [("p[%d]" % k, "=", e) for k, e in enumerate(tr.p_exprs)]
+    prep += [("p[%d]" % (NPU + k), "=", g.leaf("c", q)) for k, q in enumerate(tr.c_in_rhs)]
+    # prepare_vjp: overwrites every slot (a slot prepare does not read gets 0)
+    pb = [g.leaf("seed", k) for k in range(NPU)]
+    adj = vjp(g, tr.p_exprs, pb)
+    prep_vjp = [("thb[%d]" % s, "=", adj.get(g.leaf("th", s).id, g.const(0.0))) for s in range(len(P))]
+    # init / init_vjp: the kernel calls init_vjp(yb, thb) after prepare_vjp, without theta or treatments -- so it adds,
+    # and the initial state must be affine in theta with constant coefficients (it is a copy in every reference model)
+    init = [("y[%d]" % j, "=", e) for j, e in enumerate(tr.y0)]
+    yb = [g.leaf("seed", j) for j in range(N)]
+    adj0 = vjp(g, tr.y0, yb)
+    init_vjp = []
+    for s in range(len(P)):
+        e = adj0.get(g.leaf("th", s).id)
+        if e is None:
+            continue
+        if not _leaf_free(e, ("seed",)):
+            raise ModelDefinitionError(
+                "%s.initial_state: the derivative with respect to '%s' depends on theta or the treatments; the kernels' "
+                "init_vjp sees the state adjoint only, so the initial state must be affine in the parameters with constant "
+                "coefficients (move nonlinear maps into prepare... or into a parameter of its own)" % (cls.__name__, P[s]))
+        init_vjp.append(("thb[%d]" % s, "+=", e))
+    # rhs / rhs_vjp
+    rhs = [("dy[%d]" % j, "=", e) for j, e in enumerate(tr.dy)]
+    v = [g.leaf("seed", j) for j in range(N)]
+    adj1 = vjp(g, tr.dy, v)
+    rhs_vjp = [("yb[%d]" % j, "+=", adj1[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj1]
+    rhs_vjp += [("pb[%d]" % k, "+=", adj1[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj1]
+
+    def body(assign, fast, seed, p_map=None):
+        names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed}
+        return "\n".join(_Emitter(fast, names, p_map).emit(assign))
+
+    names = ", ".join('"%s"' % n for n in P)
+    key = cls.model_key
+    out = [
+        "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
+            cls.__module__, cls.__qualname__, key),
+        "// Do not edit: the definition in Python is the source.",
+        "#pragma once",
+        "namespace vihds {",
+        "struct %s {" % sname,
+        "  static constexpr int N = %d;" % N,
+        "  static constexpr int NS = %d;" % N,
+        "  static constexpr bool NEURAL_PREC = false;",
+        "  static constexpr int NW = 0;",
+        "  static constexpr int NC = %d;" % C,
+        "  static constexpr int OBS = %s;" % obs_enum,
+        "  static constexpr int NSLOT = %d;" % len(P),
+        "  static constexpr int NP = %d;" % max(tr.NP, 1),
+        "  __host__ static const char* slot_name(int s) {",
+        "    static const char* n[] = {%s};" % names,
+        "    return n[s];",
+        "  }",
+        "  __device__ static void prepare(const float* th, const float* c, float* p) {",
+        body(prep, False, "pb", tr.c_slot),
+        "  }",
+        "  __device__ static void prepare_vjp(const float* th, const float* c, const float* p, const float* pb, float* thb) {",
+        body(prep_vjp, False, "pb"),
+        "  }",
+        "  __device__ static void init(const float* th, const float* c, float* y) {",
+        body(init, False, "yb"),
+        "  }",
+        "  __device__ static void init_vjp(const float* yb, float* thb) {",
+        body(init_vjp, False, "yb"),
+        "  }",
+        "  __device__ static void rhs(float t, const float* y, const float* p, const float*, float* dy) {",
+        body(rhs, True, "v", tr.c_slot),
+        "  }",
+        "  __device__ static void rhs_vjp(float t, const float* y, const float* p, const float*, const float* v, float* yb,",
+        "                                 float* pb) {",
+        body(rhs_vjp, True, "v", tr.c_slot),
+        "  }",
+        "};",
+        "}  // namespace vihds",
+        "#define VIHDS_GEN_CORE %s" % sname,
+        "#define VIHDS_GEN_NEURAL %d" % (1 if neural else 0),
+        "",
+    ]
+    return "\n".join(line for line in out if line != "") + "\n"
+
+
+def _ident(key):
+    return "".join(ch if ch.isalnum() else "_" for ch in key)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the side library
+# ---------------------------------------------------------------------------------------------------------------------
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
+
+
+def _kernel_headers_digest():
+    """The files a generated library is compiled from: the Makefile's HDRS (csrc/*.hpp and include/vihds_hip.h, whose
+    checksum is the layout guard vihds_model_register compares) and the generated translation unit."""
+    paths = [os.path.join(_CSRC, n) for n in sorted(os.listdir(_CSRC)) if n.endswith(".hpp")]
+    paths += [os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include", "vihds_hip.h"),
+              os.path.join(_CSRC, "generated", "ode_generated_model.hip")]
+    h = hashlib.sha256()
+    for path in paths:
+        with open(path, "rb") as f:
+            h.update(os.path.basename(path).encode() + b"\0" + f.read())
+    return h.hexdigest()
+
+
+def library_tag(source):
+    """Cache key of a generated library: the source and the kernel headers it is compiled with."""
+    return hashlib.sha256(source.encode() + _kernel_headers_digest().encode()).hexdigest()[:16]
+
+
+def library_path(tag):
+    return os.path.join(os.path.dirname(hip.library_path()), "libvihds_gen_%s.so" % tag)
+
+
+def ensure_library(source):
+    """Build libvihds_gen_<tag>.so next to libvihds_hip.so when it is missing (hipcc, about a minute, once: it stays in
+    vi-hds_amd/lib/), with the lock / opt-out of hip.ensure_blackbox_variant (VIHDS_BLACKBOX_JIT=0 switches building off).
+    Returns the library's path."""
+    tag = library_tag(source)
+    path = library_path(tag)
+    if os.path.exists(path):
+        return path
+    lib_dir = os.path.dirname(path)
+    header = os.path.join(lib_dir, "generated", "gen_%s.hpp" % tag)
+    cmd = ["make", "-C", _CSRC, "generated", "SRC=%s" % header, "TAG=%s" % tag]
+    if (os.environ.get("VIHDS_BLACKBOX_JIT", "1") == "0" or "VIHDS_HIP_LIB" in os.environ
+            or not os.path.exists(os.path.join(_CSRC, "generated", "ode_generated_model.hip"))):
+        raise RuntimeError("generated model needs %s (build: %s after writing the header)" % (path, " ".join(cmd)))
+    import fcntl
+    import subprocess
+
+    os.makedirs(os.path.dirname(header), exist_ok=True)
+    with open(os.path.join(lib_dir, ".blackbox_build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if not os.path.exists(path):
+                if not os.path.exists(header) or open(header).read() != source:
+                    tmp = header + ".tmp%d" % os.getpid()
+                    with open(tmp, "w") as f:
+                        f.write(source)
+                    os.replace(tmp, header)
+                sys.stderr.write("[vihds] building a generated model: %s\n" % " ".join(cmd))
+                res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+                if res.returncode != 0 or not os.path.exists(path):
+                    raise RuntimeError("building %s failed:\n%s" % (path, res.stdout[-3000:]))
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return path
+
+
+_REGISTERED = {}  # model_key -> (class, neural)
+
+
+def register_kernel(cls, neural=False):
+    """Compile (if needed) and register the kernels of a generated model class; add its key to hip.MODELS.  Returns the
+    model id.  A key is one model: registering it again with another definition or precision kind raises."""
+    key = cls.model_key
+    prev = _REGISTERED.get(key)
+    if prev is not None:
+        if prev != (cls, neural) and generate_source(*prev) != generate_source(cls, neural):
+            raise ModelDefinitionError("model_key '%s' is registered already with another definition" % key)
+        return hip.MODELS[key]
+    if key in hip.MODELS:
+        raise ModelDefinitionError("model_key '%s' is a built-in model: pick another key" % key)
+    source = generate_source(cls, neural)
+    path = ensure_library(source)
+    mid = hip.lib().vihds_model_register(path.encode())
+    if mid < 0:
+        hip.check(mid, "vihds_model_register(%s)" % path)
+    hip.MODELS[key] = mid
+    _REGISTERED[key] = (cls, neural)
+    return mid
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the plugin base class
+# ---------------------------------------------------------------------------------------------------------------------
+class GeneratedOdeModel(OdeModel):
+    """Base class of models defined in Python (module docstring).  A subclass that sets `model_key` is traced when the
+    class is defined: errors in the definition and the kernels' limits are reported there, not inside a launch."""
+
+    species = None
+    parameter_names = None
+    n_conditions = 0
+    observe_kind = "default"
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        # a subclass declares its theta names as `parameters`, which would hide nn.Module.parameters() (the optimiser and
+        # the training step walk the module's tensors through it): keep the names as `parameter_names`, the method as it is
+        declared = cls.__dict__.get("parameters")
+        if isinstance(declared, (list, tuple)):
+            cls.parameter_names = list(declared)
+            del cls.parameters
+        if cls.__dict__.get("model_key") is None and getattr(cls, "_trace", None) is not None:
+            cls._trace = Trace(cls)  # (a subclass that only changes __init__)
+            return
+        if cls.model_key is None:
+            return
+        _validate(cls)
+        cls._trace = Trace(cls)
+        generate_source(cls)  # (the checks that need the adjoints: an initial state the kernels can differentiate)
+
+    def __init__(self, config):
+        super(GeneratedOdeModel, self).__init__(config)
+        self.species = list(type(self).species)
+        self.n_species = len(self.species)
+
+    # the three functions of a model
+    def prepare(self, th, c):
+        raise NotImplementedError("prepare(th, c) -> {name: effective parameter}")
+
+    def initial_state(self, th, c):
+        raise NotImplementedError("initial_state(th, c) -> [value per species]")
+
+    def rhs(self, t, y, p, c):
+        raise NotImplementedError("rhs(t, y, p, c) -> [d species / dt]")
+
+    def condition_theta(self, theta, dev_1hot, writer, epoch):
+        return theta
+
+    # kernels
+    def _neural(self):
+        return bool(getattr(self.precisions, "dynamic", False))
+
+    def kernel_slots(self):
+        register_kernel(type(self), self._neural())
+        return super(GeneratedOdeModel, self).kernel_slots()
+
+    def neural_weights(self):
+        return self.precisions.flat_weights() if self._neural() else None
+
+    def problem_kwargs(self, config):
+        if self._neural():
+            return {"n_hidden_prec": max(int(config.params.n_hidden_decoder_precisions), 0)}
+        return {}
+
+    def summaries(self, writer, epoch):
+        if self._neural():
+            self.precisions.summaries(writer, epoch)
+
+    # the same definition as a PyTorch right-hand side
+    @classmethod
+    def torch_problem(cls, th, cond):
+        """(rhs, x0) in the convention of oracle.make_*: th maps parameter names to [B, S] tensors, cond is [B, C] (log(1 +
+        treatment), as the data holds it); rhs(t, state [B, S, N]) -> [B, S, N] of the species (no precision states)."""
+        inst = cls.__new__(cls)
+        N = len(cls.species)
+        B, S = th[cls.parameter_names[0]].shape
+        ref = th[cls.parameter_names[0]]
+        tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
+        cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+        thn = _Named([(n, th[n]) for n in cls.parameter_names], "parameter")
+        full = lambda v: v if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
+        p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
+        x0 = torch.stack([full(v) for v in inst.initial_state(thn, _Conditions(cs))], dim=2)
+
+        def rhs(t, state):
+            y = list(torch.unbind(state[:, :, :N], dim=2))
+            return torch.stack([full(v) for v in inst.rhs(t, y, p, _Conditions(cs))], dim=2)
+
+        return rhs, x0
+
+
+def _validate(cls):
+    name = cls.__name__
+    if not isinstance(cls.model_key, str) or not cls.model_key:
+        raise ModelDefinitionError("%s.model_key must be a non-empty string" % name)
+    if not cls.species or not all(isinstance(s, str) for s in cls.species):
+        raise ModelDefinitionError("%s.species must list the ODE states" % name)
+    if not cls.parameter_names or not all(isinstance(s, str) for s in cls.parameter_names):
+        raise ModelDefinitionError("%s.parameters must list the theta names the kernel reads" % name)
+    if len(set(cls.parameter_names)) != len(cls.parameter_names):
+        raise ModelDefinitionError("%s.parameters has duplicates" % name)
+    if cls.observe_kind not in OBSERVE_KINDS:
+        raise ModelDefinitionError("%s.observe_kind must be one of %s" % (name, sorted(OBSERVE_KINDS)))
+    need = OBSERVE_KINDS[cls.observe_kind][1]
+    if len(cls.species) < need:
+        raise ModelDefinitionError("%s: observe_kind '%s' reads %d species, the model has %d"
+                                   % (name, cls.observe_kind, need, len(cls.species)))
+    if len(cls.species) > MAX_STATES:
+        raise ModelDefinitionError("%s: %d species; generated models hold at most %d states"
+                                   % (name, len(cls.species), MAX_STATES))
+    # four more slots follow the model's own: the constant precisions, or the neural precisions' initial values
+    if len(cls.parameter_names) + 4 > hip.VIHDS_MAX_SLOTS:
+        raise ModelDefinitionError("%s: %d parameters; the kernels read at most %d slots (VIHDS_MAX_SLOTS, 4 of them for "
+                                   "the precisions)" % (name, len(cls.parameter_names), hip.VIHDS_MAX_SLOTS - 4))
+    if not isinstance(cls.n_conditions, int) or cls.n_conditions < 0:
+        raise ModelDefinitionError("%s.n_conditions must be an integer >= 0" % name)
