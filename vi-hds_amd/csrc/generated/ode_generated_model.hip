@@ -52,8 +52,8 @@ thread_local const ThetaStageArgs* g_theta_stage = nullptr;
 thread_local const SummArgs* g_summ = nullptr;
 template <class M>
 static int n_weights_of(int H) {
-  if constexpr (M::NEURAL_PREC) return M::n_weights(H);
-  else return 0;
+  if constexpr (M::NEURAL_PREC) return VIHDS_GEN_CORE::NW + M::n_weights(H);
+  else return VIHDS_GEN_CORE::NW;
 }
 static int n_weights_gen(int H) { return n_weights_of<GenM>(H); }
 static const char* const* slot_names_gen() {
@@ -73,7 +73,8 @@ static int launch_gen(bool backward, int solver, const OdeArgs& a, hipStream_t s
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
   using namespace vihds;
   static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, GenM::N, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
-                                   slot_names_gen(), n_weights_gen, launch_gen};
+                                   slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
+                                   net_fields<VIHDS_GEN_CORE>::value};
   return &r;
 }
 #endif

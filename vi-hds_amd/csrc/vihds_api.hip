@@ -116,6 +116,10 @@ struct ModelEntry {
   int (*n_cond)();  // treatments the model reads per data row (cond[b*C + q], q < n_cond)
   const char* (*slot_name)(int);
   bool neural_prec;
+  // a registered model whose generated struct has networks of its own (GenModelRecord): weights in front of the precision
+  // network's, dump fields in front of its fields
+  int n_net_weights = 0, net_fields = 0;
+  bool has_weights() const { return neural_prec || n_net_weights > 0; }
 };
 #define VIHDS_ENTRY(name, np) \
   { launch_##name, n_slots_##name, n_states_##name, n_cond_##name, slot_name_##name, np }
@@ -313,7 +317,8 @@ int vihds_model_register(const char* library_path) {
     return VIHDS_E_UNSUPPORTED;
   }
   if (r->n_slots + (r->neural_prec ? 0 : 4) > VIHDS_MAX_SLOTS || r->n_states < 1 || !r->launch || !r->slot_names ||
-      !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT)) {
+      !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT) || r->n_net_weights < 0 ||
+      r->net_fields < 0 || (r->n_net_weights > 0) != (r->net_fields > 0)) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
   }
@@ -325,6 +330,8 @@ int vihds_model_register(const char* library_path) {
   g_gen[k] = r;
   g_gen_entries[k] = gen_entry_of(k, std::make_integer_sequence<int, VIHDS_GEN_MODEL_MAX>{});
   g_gen_entries[k].neural_prec = r->neural_prec != 0;
+  g_gen_entries[k].n_net_weights = r->n_net_weights;
+  g_gen_entries[k].net_fields = r->net_fields;
   g_gen_count.store(k + 1, std::memory_order_release);  // (entry() sees the slot only once it is filled)
   by_path[resolved] = VIHDS_GEN_MODEL_BASE + k;
   return VIHDS_GEN_MODEL_BASE + k;
@@ -354,7 +361,7 @@ int vihds_model_n_weights(const vihds_ode_problem* p) {
   if (!p) return VIHDS_E_BADARG;
   const ModelEntry* e = entry(p->model);
   if (!e) return VIHDS_E_UNSUPPORTED;
-  if (!e->neural_prec) return 0;
+  if (!e->has_weights()) return 0;
   if (is_registered(p->model)) return g_gen[p->model - VIHDS_GEN_MODEL_BASE]->n_weights(p->n_hidden_prec);
   if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
     if (bb_builtin(p)) return bb_n_weights(p->n_const);
@@ -477,12 +484,13 @@ long long vihds_ode_bwd_aux_floats(const vihds_ode_problem* p) {
   }
   const ModelEntry* e = entry(p->model);
   if (!e) return VIHDS_E_UNSUPPORTED;
-  if (!e->neural_prec) return 0;
+  if (!e->has_weights()) return 0;
   if (vihds_ode_bwd_reduces_weights(p)) return relay_lanes_aux_floats(p->B * p->S, lane_model_species(p->model));  // one partial row per block
   // white-box + neural precisions: [8 + NIN][E][n], NIN = 1 + core states (optional: see vihds_ode_bwd)
   const long long stages = ode_stages(p->solver);
-  const long long fields = 8 + e->n_states() - 4 + 1 + (p->n_hidden_prec > 0 ? 2 * p->n_hidden_prec : 0);
-  return fields * (p->T - 1) * stages * p->B * p->S;
+  // (a registered model with networks of its own: their fields first -- vihds_gen_model.hpp)
+  const long long prec_fields = e->neural_prec ? 8 + e->n_states() - 4 + 1 + (p->n_hidden_prec > 0 ? 2 * p->n_hidden_prec : 0) : 0;
+  return (e->net_fields + prec_fields) * (p->T - 1) * stages * p->B * p->S;
 }
 int vihds_blackbox_dump_fields(void) { return bb_dump_fields(); }
 int vihds_problem_dump_fields(const vihds_ode_problem* p) {
@@ -545,7 +553,7 @@ int vihds_ode_fwd(const vihds_ode_problem* p, const float* theta, const float* c
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (logp && !obs) return fail(VIHDS_E_BADARG, "logp requested without obs");
-  if (e->neural_prec) {
+  if (e->has_weights()) {
     if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
     if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
       if (!bb_builtin(p) && !(sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
@@ -642,7 +650,7 @@ int vihds_ode_fwd_summaries(const vihds_ode_problem* p, const float* theta, cons
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (p->model == VIHDS_MODEL_DR_BLACKBOX || solver_is_adaptive(p->solver))
     return VIHDS_E_UNSUPPORTED;  // (dr_blackbox and the adaptive pairs keep vihds_ode_fwd + vihds_iw_summaries_states)
-  if (e->neural_prec) {
+  if (e->has_weights()) {
     if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
     if (p->n_hidden_prec > 256) return fail(VIHDS_E_UNSUPPORTED, "neural precisions: at most 256 hidden units");
   }
@@ -690,7 +698,7 @@ int vihds_ode_adaptive_grid(const vihds_ode_problem* p, const float* theta, cons
   const BbVariant* sized = nullptr;
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
-  if (e->neural_prec) {
+  if (e->has_weights()) {
     if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
     if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
       if (!bb_builtin(p) && !(sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
@@ -796,7 +804,7 @@ int vihds_ode_bwd(const vihds_ode_problem* p, const float* theta, const float* c
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (!obs) return fail(VIHDS_E_BADARG, "null obs");
-  if (e->neural_prec) {
+  if (e->has_weights()) {
     if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
     if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
       if (!bb_builtin(p) && !(sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
@@ -813,6 +821,8 @@ int vihds_ode_bwd(const vihds_ode_problem* p, const float* theta, const float* c
   // (white-box + hidden-layer precisions without aux: the state / theta adjoints only -- the three weight matrices have
   // no per-thread accumulators, they come from the dump; g_weights then receives nothing)
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && !aux) return fail(VIHDS_E_BADARG, "dr_blackbox backward needs the aux buffer");
+  if (e->n_net_weights > 0 && g_weights && !aux)
+    return fail(VIHDS_E_BADARG, "a generated model with networks forms its weight gradient from the aux dump: pass aux (vihds_ode_bwd_aux_floats)");
   a.traj_in = traj; a.g_traj = g_traj; a.g_xpred = g_xpred; a.g_logp = g_logp; a.g_theta = g_theta;
   rc = sized ? sized->launch(true, p->solver, a, (hipStream_t)stream, nullptr) : e->launch(true, p->solver, a, (hipStream_t)stream);
   if (rc) return fail(rc, "unknown solver");
@@ -888,7 +898,7 @@ int vihds_ode_bwd_elbo(const vihds_ode_problem* p, const float* theta, const flo
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (!obs) return fail(VIHDS_E_BADARG, "null obs");
   if (solver_is_adaptive(p->solver)) return fail(VIHDS_E_UNSUPPORTED, "vihds_ode_bwd_elbo: fixed-grid solvers");
-  if (e->neural_prec) {
+  if (e->has_weights()) {
     if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
     if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
       // (side libraries were built against the same headers: their kernels form the weights too)
@@ -904,6 +914,8 @@ int vihds_ode_bwd_elbo(const vihds_ode_problem* p, const float* theta, const flo
   a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs; a.weights = weights;
   a.g_weights = g_weights; a.aux = aux;
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && !aux) return fail(VIHDS_E_BADARG, "dr_blackbox backward needs the aux buffer");
+  if (e->n_net_weights > 0 && g_weights && !aux)
+    return fail(VIHDS_E_BADARG, "a generated model with networks forms its weight gradient from the aux dump: pass aux (vihds_ode_bwd_aux_floats)");
   a.traj_in = traj; a.g_theta = g_theta;
   a.iw_logp = logp; a.iw_log_p = log_p; a.iw_log_q = log_q;
   a.logp_grad_broadcast = 1;

@@ -31,9 +31,14 @@ struct GenModelRecord {
   int observe_kind; // ObserveKind
   int neural_prec;  // 1: WithPrec<> around the generated struct
   const char* const* slot_names;
-  int (*n_weights)(int n_hidden_prec);  // floats of the neural-precision weight buffer (vihds_model_n_weights)
+  int (*n_weights)(int n_hidden_prec);  // floats of the whole weight buffer: the networks', then the neural precisions' (vihds_model_n_weights)
   // ctl != nullptr: run the step-size controller of an adaptive solver instead of the integration (as BbVariant::launch)
   int (*launch)(bool backward, int solver, const OdeArgs& a, hipStream_t st, AdaptiveCtl* ctl);
+  // networks of the generated struct itself (0 / 0 without): their weights lead the buffer, their adjoint dump leads aux --
+  // net_fields floats per RHS evaluation and trajectory, field-major [net_fields][E][n], per network the inputs, the hidden
+  // pre-activation adjoints, the hidden activations and the output adjoints (vihds_ode_bwd_aux_floats adds them)
+  int n_net_weights;
+  int net_fields;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

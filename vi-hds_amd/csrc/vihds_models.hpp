@@ -18,6 +18,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+#include <utility>
+
 namespace vihds {
 
 enum ObserveKind { OBS_DEFAULT = 0, OBS_DIRECT = 1, OBS_INDUCER = 2 };
@@ -879,6 +882,24 @@ struct DegraderConstant {
 // weights buffer (NeuralPrecisions.flat_weights): Wp [4][NIN], bp [4], Wd [4][NIN], bd [4]   (NIN = NS + 1)
 // (every reference spec that pairs a white-box model with neural precisions sets n_hidden_decoder_precisions: 0)
 // ---------------------------------------------------------------------------------------------
+// A core generated with networks of its own (vihds/modelgen.py) declares NET_FIELDS: the floats its adjoint dumps per RHS
+// evaluation and trajectory for the weight-gradient contraction; its rhs_vjp takes the adjoint kernel's context.  0 for
+// every other model.
+template <class M, class = void>
+struct net_fields {
+  static constexpr int value = 0;
+};
+template <class M>
+struct net_fields<M, std::void_t<decltype(M::NET_FIELDS)>> {
+  static constexpr int value = M::NET_FIELDS;
+};
+
+// whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
+template <class Ctx, class = void>
+struct ctx_has_wb : std::false_type {};
+template <class Ctx>
+struct ctx_has_wb<Ctx, std::void_t<decltype(std::declval<Ctx&>().wb)>> : std::true_type {};
+
 template <class Core>
 struct WithPrec {
   static constexpr int NS = Core::N;
@@ -889,6 +910,10 @@ struct WithPrec {
   static constexpr int NP = Core::NP + 1;  // + the number of hidden units H (as integer bits; set by the kernels)
   static constexpr int NIN = Core::N + 1;
   static constexpr int NW = 2 * (4 * NIN + 4);  // weights without a hidden layer (H = 0)
+  // one weights buffer, two sections: the core's own networks (Core::NW floats, 0 for the hand-written cores), then the
+  // precision network.  Core::rhs gets the buffer as it is; everything here reads from W0 on.
+  static constexpr int W0 = Core::NW;
+  static constexpr int NET_FIELDS = net_fields<Core>::value;
   static constexpr bool NEURAL_PREC = true;
   static constexpr int O_WP = 0, O_BP = 4 * NIN, O_WD = 4 * NIN + 4, O_BD = 8 * NIN + 4;
   // With a hidden layer (reference precisions.py:63-74; params.n_hidden_decoder_precisions = H >= 1, the reference's
@@ -938,7 +963,7 @@ struct WithPrec {
     }
   }
   __device__ static void rhs(float t, const float* y, const float* p, const float* wg, float* dy) {
-    const weights_ptr w = (weights_ptr)wg;
+    const weights_ptr w = (weights_ptr)wg + W0;
     Core::rhs(t, y, p, wg, dy);
     __asm__ volatile("" ::: "memory");  // keep the weight loads inside the time loop (no hoist-and-spill)
     const int H = hidden_units(p);
@@ -964,8 +989,9 @@ struct WithPrec {
   template <class Ctx>
   __device__ static void rhs_vjp(float t, const float* y, const float* p, const float* wg, const float* v, float* yb,
                                  float* pb, Ctx& ctx) {
-    const weights_ptr w = (weights_ptr)wg;
-    Core::rhs_vjp(t, y, p, wg, v, yb, pb);
+    const weights_ptr w = (weights_ptr)wg + W0;
+    if constexpr (NET_FIELDS > 0) Core::rhs_vjp(t, y, p, wg, v, yb, pb, ctx);
+    else Core::rhs_vjp(t, y, p, wg, v, yb, pb);
     __asm__ volatile("" ::: "memory");
     const int H = hidden_units(p);
     if (H > 0) {
@@ -1042,12 +1068,12 @@ struct WithPrec {
         D[(size_t)(4 + j) * fs] = zdb;
         ctx.bsum[j] += zab;
         ctx.bsum[4 + j] += zdb;
-      } else {
+      } else if constexpr (ctx_has_wb<Ctx>::value) {
         ctx.wb[O_BP + j] += zab;
         ctx.wb[O_BD + j] += zdb;
       }
       VIHDS_UNROLL for (int i = 0; i < NIN; ++i) {
-        if constexpr (!Ctx::DUMP) {
+        if constexpr (!Ctx::DUMP && ctx_has_wb<Ctx>::value) {
           ctx.wb[O_WP + j * NIN + i] += zab * h[i];
           ctx.wb[O_WD + j * NIN + i] += zdb * h[i];
         }

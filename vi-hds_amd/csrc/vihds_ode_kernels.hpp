@@ -84,6 +84,23 @@ struct PrecDumpCtx {
   int e;           // evaluation counter
   float bsum[8];
 };
+// a generated core with networks of its own (net_fields<M> > 0), with constant precisions or inside WithPrec<>: the aux
+// buffer holds the networks' fields [NET_FIELDS][E][n] first, then (WithPrec<>) the precision network's [8 + NIN (+ 2 H)][E][n].
+// Nothing of the networks stays in registers: their bias gradients are row sums of the dump (vihds/ops.py).
+struct GenDumpCtx {
+  static constexpr bool DUMP = true;
+  float* dump;  // precision section (PrecDumpCtx's members, for WithPrec::rhs_vjp)
+  size_t n, fstride;
+  int e;
+  float bsum[8];
+  float* net_dump;  // &aux[i]
+  int net_e;
+};
+// ... without an aux buffer: state / theta adjoints only, no weight gradient of either section (as a hidden precision
+// layer without aux; vihds_ode_bwd refuses g_weights without aux for these models)
+struct NetSkipCtx {
+  static constexpr bool DUMP = false;
+};
 __host__ __device__ inline int ode_stages(int solver) {
   if (solver_is_adaptive(solver)) return adaptive_stages(solver);
   return solver == VIHDS_SOLVER_EULER ? 1 : (solver == VIHDS_SOLVER_RK4 ? 4 : 2);
@@ -112,12 +129,34 @@ struct bwd_ctx<M, true, true> {  // dr_blackbox
   }
 };
 
-template <class M, bool DUMP>
+template <class M, bool DUMP, bool NET = (net_fields<M>::value > 0)>
 struct bwd_ctx_sel {
   using impl = bwd_ctx<M>;
 };
 template <class M>
-struct bwd_ctx_sel<M, true> {
+struct bwd_ctx_sel<M, false, true> {
+  struct impl {
+    using type = NetSkipCtx;
+    __device__ static void init(type&, const OdeArgs&, int) {}
+  };
+};
+template <class M>
+struct bwd_ctx_sel<M, true, true> {
+  struct impl {
+    using type = GenDumpCtx;
+    __device__ static void init(type& c, const OdeArgs& a, int i) {
+      c.n = (size_t)a.n;
+      c.fstride = (size_t)(a.T - 1) * ode_stages(a.solver) * a.n;
+      c.net_dump = a.aux + i;
+      c.dump = a.aux + (size_t)net_fields<M>::value * c.fstride + i;
+      c.e = 0;
+      c.net_e = 0;
+      VIHDS_UNROLL for (int k = 0; k < 8; ++k) c.bsum[k] = 0.f;
+    }
+  };
+};
+template <class M>
+struct bwd_ctx_sel<M, true, false> {
   struct impl {
     using type = PrecDumpCtx;
     __device__ static void init(type& c, const OdeArgs& a, int i) {
@@ -618,22 +657,27 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.g_theta[(size_t)a.slot_row[M::NSLOT + j] * n + i] = precb[j];
     }
   }
-  if constexpr (!is_blackbox<M>::value && M::NW > 0) {
+  if constexpr (!is_blackbox<M>::value && M::NEURAL_PREC) {
     if (a.g_weights) {
-      if constexpr (DUMP) {
+      if constexpr (DUMP && net_fields<M>::value > 0) {
+        // a generated core with networks: nothing is added here -- the precision network's bias gradients are row sums of
+        // its dump fields 0..7 like the networks' own (vihds/ops.py), so the whole weight gradient is the same bits run to run
+      } else if constexpr (DUMP) {
         // only the biases are accumulated here; the weight matrices come from the dump (vihds_gram_blocks)
         VIHDS_UNROLL for (int q = 0; q < 8; ++q) {
           float v = live ? wtsb.bsum[q] : 0.f;
           VIHDS_UNROLL for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
           if ((threadIdx.x & 63) == 0)
-            atomicAdd(&a.g_weights[(q < 4 ? M::o_bp(a.n_hidden_prec) + q : M::o_bd(a.n_hidden_prec) + (q - 4))], v);
+            atomicAdd(&a.g_weights[M::W0 + (q < 4 ? M::o_bp(a.n_hidden_prec) + q : M::o_bd(a.n_hidden_prec) + (q - 4))], v);
         }
-      } else if (a.n_hidden_prec < 1) {
-        // shared-weight gradient: per-thread register accumulators -> wave shuffle tree -> one atomic per wave
-        VIHDS_UNROLL for (int q = 0; q < M::NW; ++q) {
-          float v = live ? wtsb.wb[q] : 0.f;
-          VIHDS_UNROLL for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-          if ((threadIdx.x & 63) == 0) atomicAdd(&a.g_weights[q], v);
+      } else if constexpr (ctx_has_wb<typename CtxImpl::type>::value) {
+        if (a.n_hidden_prec < 1) {
+          // shared-weight gradient: per-thread register accumulators -> wave shuffle tree -> one atomic per wave
+          VIHDS_UNROLL for (int q = 0; q < M::NW; ++q) {
+            float v = live ? wtsb.wb[q] : 0.f;
+            VIHDS_UNROLL for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+            if ((threadIdx.x & 63) == 0) atomicAdd(&a.g_weights[M::W0 + q], v);
+          }
         }
       }
     }
@@ -655,7 +699,7 @@ inline void launch_fwd_s(const OdeArgs& a, hipStream_t st) {
 template <class M, int SOLVER>
 inline void launch_bwd_s(const OdeArgs& a, hipStream_t st) {
   const int blk = pick_block(a.n);
-  if constexpr (M::NEURAL_PREC && !is_blackbox<M>::value) {
+  if constexpr ((M::NEURAL_PREC || net_fields<M>::value > 0) && !is_blackbox<M>::value) {
     if (a.aux) {  // dump mode: the caller contracts the weight gradients (vihds_ode_bwd, include/vihds_hip.h)
       hipLaunchKernelGGL((ode_bwd_kernel<M, SOLVER, true>), dim3((a.n + blk - 1) / blk), dim3(blk), 0, st, a);
       return;
@@ -701,12 +745,17 @@ namespace vihds {
 
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
-  if (const SummArgs* sm = g_summ) {  // vihds_ode_fwd_summaries: the evaluation's second forward pass
-    return backward ? VIHDS_E_BADARG : launch_fwd_summ<M, ONLY>(solver, a, *sm, st);
-  }
-  if (AdaptiveDevCtl* dc = g_adaptive_dev) {  // vihds_ode_adaptive_fwd / _bwd: the device-resident controller and its adjoint
-    dc->result = adaptive_device<M, ONLY>(solver, a, *dc, st);
-    return dc->result;
+  if constexpr (net_fields<M>::value > 0) {
+    // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers)
+    if (g_summ || g_adaptive_dev) return VIHDS_E_UNSUPPORTED;
+  } else {
+    if (const SummArgs* sm = g_summ) {  // vihds_ode_fwd_summaries: the evaluation's second forward pass
+      return backward ? VIHDS_E_BADARG : launch_fwd_summ<M, ONLY>(solver, a, *sm, st);
+    }
+    if (AdaptiveDevCtl* dc = g_adaptive_dev) {  // vihds_ode_adaptive_fwd / _bwd: the device-resident controller and its adjoint
+      dc->result = adaptive_device<M, ONLY>(solver, a, *dc, st);
+      return dc->result;
+    }
   }
   if (AdaptiveCtl* ctl = g_adaptive_ctl) {
     ctl->result = adaptive_grid<M, ONLY>(solver, a, ctl->times_host, ctl->rtol, ctl->atol, ctl->workspace, ctl->grid_host,

@@ -29,6 +29,9 @@ MODELS = {
     "inducer_constant_precisions": 14,
     "debug_constant": 15,
 }
+# registered generated models with networks of their own (modelgen.register_kernel): key -> [(n_inputs, n_hidden,
+# n_outputs)] in the weight buffer's order
+GENERATED_NETWORKS = {}
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8}

@@ -34,6 +34,22 @@ The adjoint of each operation is torch autograd's formula, with one exception ke
 pow(a, n) is g * a^n * log(a) everywhere, as csrc pow_vjp computes it for the built-in models.  At a = 0 that is NaN
 (0 * -inf) where autograd masks it to 0 (pow_backward_exponent, base 0 and exponent >= 0); clamp the base away from 0
 (as the reference models do: clamp(K, 1e-12, 1) * c) when the exponent is a parameter.
+
+Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
+
+        networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
+
+        def rhs(self, t, y, p, c):
+            o = self.net.latent([y[4], y[5], y[0], p.a, c[0]])      # list of n_outputs values, LINEAR output layer
+
+A network is Linear(n_inputs, n_hidden) -> activation -> Linear(n_hidden, n_outputs) with biases; heads and gates are
+composed from the operations above (the reference's NeuralStates, vihds/ode.py:119-138, is sigmoid(o[j]) - sigmoid(o[k]) * z).
+Its weights are nn.Parameters of the model instance (nets.<name>.hidden / .out); neural_weights() is one flat buffer: all
+networks in declaration order, each W1 [H][I], b1 [H], W2 [O][H], b2 [O], then the NeuralPrecisions weights when the model
+uses them.  The generated struct then has NW > 0: the forward MLP and its adjoint are emitted into it, weights are read as
+scalars through the constant address space, and the weight gradient comes from a field-major dump of the adjoint kernel
+(per evaluation and network: inputs [I], hidden pre-activation adjoints [H], hidden activations [H], output adjoints [O])
+contracted by vihds_gram_blocks -- fixed summation order, no atomics (ops.decoder_weight_grads).
 """
 import hashlib
 import math
@@ -49,10 +65,46 @@ from vihds.ode import OdeModel
 MAX_STATES = 32  # ODE states of a generated model (all of them live in registers of one thread)
 OBSERVE_KINDS = {"default": ("OBS_DEFAULT", 6), "direct": ("OBS_DIRECT", 4)}  # kernel enum, species observe() reads
 OPERATIONS = ("exp", "log", "pow", "sigmoid", "tanh", "clamp")
+# networks of a generated model (the hidden layer is walked one unit at a time, the inputs and outputs live in registers)
+MAX_NETWORKS, MAX_NET_INPUTS, MAX_NET_HIDDEN, MAX_NET_OUTPUTS = 2, 16, 32, 8
+NET_ACTIVATIONS = ("relu", "tanh")
 
 
 class ModelDefinitionError(TypeError):
     """A generated model's definition cannot be traced or breaks a limit of the kernels."""
+
+
+class Network(object):
+    """Linear(n_inputs, n_hidden) -> relu | tanh -> Linear(n_hidden, n_outputs), biases in both layers, raw outputs."""
+
+    def __init__(self, n_inputs, n_hidden, n_outputs, hidden="relu"):
+        self.n_inputs, self.n_hidden, self.n_outputs, self.hidden = n_inputs, n_hidden, n_outputs, hidden
+
+    @property
+    def sizes(self):
+        return (int(self.n_inputs), int(self.n_hidden), int(self.n_outputs))
+
+    @property
+    def n_weights(self):
+        I, H, O = self.sizes
+        return H * I + H + O * H + O
+
+    @property
+    def n_fields(self):  # floats the adjoint dumps per evaluation: x [I], hidden pre-activation adjoints [H], h [H], output adjoints [O]
+        I, H, O = self.sizes
+        return I + 2 * H + O
+
+    def tensor_shapes(self):
+        I, H, O = self.sizes
+        return [(H, I), (H,), (O, H), (O,)]
+
+    def __repr__(self):
+        return "Network(%d, %d, %d, hidden=%r)" % (self.sizes + (self.hidden,))
+
+
+def _class_networks(cls):
+    nets = getattr(cls, "networks", None)
+    return dict(nets) if nets else {}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -149,9 +201,10 @@ class Graph(object):
     """Hash-consed expression DAG: building a node that exists returns that node (common-subexpression elimination);
     operations on constants are folded; x+0, x*1, x*0, x/1, -(-x), pow(x, 1) simplify."""
 
-    def __init__(self):
+    def __init__(self, networks=()):
         self.nodes = []
         self._table = {}
+        self.networks = list(networks)  # Network objects; a "net" node's val is its index here
 
     def _intern(self, op, args, val):
         key = (op, tuple(a.id for a in args), val)
@@ -178,6 +231,11 @@ class Graph(object):
             raise ModelDefinitionError("unsupported operand %r of type %s in a generated model (Python numbers and model "
                                        "quantities only)" % (a, type(a).__name__))
         return self.const(a)
+
+    def net(self, k, inputs):
+        """Network k applied to `inputs`: the call node and one node per output (never folded or simplified)."""
+        call = self._intern("net", tuple(self._arg(a) for a in inputs), k)
+        return [self._intern("netout", (call,), j) for j in range(self.networks[k].sizes[2])]
 
     def make(self, op, args, val=None):
         args = tuple(self._arg(a) for a in args)
@@ -313,6 +371,7 @@ def vjp(g, outputs, seeds):
     operation's rule is torch autograd's formula (clamp: gradient where lo <= x <= hi; pow: csrc pow_vjp, unmasked at a
     zero base -- module docstring)."""
     adj = {}
+    net_adj = {}  # "net" node id -> {output index: adjoint}
 
     def acc(node, contrib):
         if node.op == "const":
@@ -324,11 +383,25 @@ def vjp(g, outputs, seeds):
             acc(o, g._arg(s))
     order = _topo([o for o in outputs if isinstance(o, Sym)])
     for n in reversed(order):
+        if n.op == "net":
+            # every output node has been visited: one adjoint node for the call (the kernel's net<k>_vjp, which also dumps
+            # what the weight gradient is contracted from) and one node per input adjoint
+            ob = net_adj.get(n.id)
+            if ob is not None:
+                I, _H, O = g.networks[n.val].sizes
+                back = g._intern("netbwd", n.args + tuple(ob.get(j, g.const(0.0)) for j in range(O)), n.val)
+                for i in range(I):
+                    acc(n.args[i], g._intern("netbwd_in", (back,), i))
+            continue
         if n.id not in adj or n.op in _LEAVES:
             continue
         gb = adj[n.id]
         a = n.args
-        if n.op == "add":
+        if n.op == "netout":
+            net_adj.setdefault(a[0].id, {})[n.val] = gb
+        elif n.op in ("netbwd", "netbwd_in"):
+            raise ModelDefinitionError("second derivatives of a network are not generated")
+        elif n.op == "add":
             acc(a[0], gb); acc(a[1], gb)
         elif n.op == "sub":
             acc(a[0], gb); acc(a[1], -gb)
@@ -358,9 +431,36 @@ def vjp(g, outputs, seeds):
     return adj
 
 
+def _net_act(net, z):
+    return torch.relu(z) if net.hidden == "relu" else torch.tanh(z)
+
+
+def net_forward_ref(net, W, x):
+    """The network on x [..., I] with W = (W1, b1, W2, b2): (hidden pre-activations, hidden activations, outputs)."""
+    W1, b1, W2, b2 = W
+    z = x @ W1.t() + b1
+    h = _net_act(net, z)
+    return z, h, h @ W2.t() + b2
+
+
+def net_vjp_ref(net, W, x, ob):
+    """What the generated adjoint computes, formula by formula: the input adjoint xb [..., I] and the four weight adjoints
+    as the contraction of the dump forms them (hidden pre-activation adjoints x inputs, output adjoints x hidden
+    activations, row sums for the biases).  ReLU passes the gradient where the pre-activation is > 0 (0 at 0, as torch)."""
+    W1, _b1, W2, _b2 = W
+    z, h, _ = net_forward_ref(net, W, x)
+    ob = ob.expand(x.shape[:-1] + ob.shape[-1:])
+    hb = ob @ W2
+    zb = hb * ((z > 0).to(z.dtype) if net.hidden == "relu" else (1.0 - h * h))
+    flat = lambda v: v.reshape(-1, v.shape[-1])  # noqa: E731
+    return zb @ W1, (flat(zb).t() @ flat(x), flat(zb).sum(0), flat(ob).t() @ flat(h), flat(ob).sum(0))
+
+
 def evaluate(outputs, env):
-    """Evaluate DAG nodes with torch (float64 in the tests): env maps (leaf kind, index) -> value."""
+    """Evaluate DAG nodes with torch (float64 in the tests): env maps (leaf kind, index) -> value; ("w", k) -> the (W1, b1,
+    W2, b2) of network k; the weight adjoints a "netbwd" node forms are left in env["wgrad"][k] when that dict exists."""
     vals = {}
+    stack = lambda a: torch.stack(torch.broadcast_tensors(*a), dim=-1)  # noqa: E731
     for n in _topo([o for o in outputs if isinstance(o, Sym)]):
         a = [vals[x.id] for x in n.args]
         if n.op == "const": v = torch.tensor(n.val, dtype=torch.float64)
@@ -377,6 +477,14 @@ def evaluate(outputs, env):
         elif n.op == "tanh": v = torch.tanh(a[0])
         elif n.op == "clamp": v = torch.clamp(a[0], n.val[0], n.val[1])
         elif n.op == "cpass": v = ((a[0] >= n.val[0]) & (a[0] <= n.val[1])).to(a[0].dtype)
+        elif n.op == "net": v = net_forward_ref(n.g.networks[n.val], env[("w", n.val)], stack(a))[2]
+        elif n.op == "netout": v = a[0][..., n.val]
+        elif n.op == "netbwd":
+            I = n.g.networks[n.val].sizes[0]
+            v, wg = net_vjp_ref(n.g.networks[n.val], env[("w", n.val)], stack(a[:I]), stack(a[I:]))
+            if "wgrad" in env:
+                env["wgrad"][n.val] = wg
+        elif n.op == "netbwd_in": v = a[0][..., n.val]
         else: raise AssertionError(n.op)
         vals[n.id] = v
     return [vals[o.id] if isinstance(o, Sym) else torch.tensor(float(o), dtype=torch.float64) for o in outputs]
@@ -417,13 +525,57 @@ class _Conditions(object):
         return len(self._v)
 
 
+class _Networks(object):
+    """`self.net` of the instance the three functions run on: one callable per declared network, `self.net.<name>(inputs)`
+    -> list of n_outputs values.  call(k, name, network, inputs) does the work (symbolic or torch)."""
+
+    def __init__(self, cls, call):
+        object.__setattr__(self, "_nets", _class_networks(cls))
+        object.__setattr__(self, "_call", call)
+        object.__setattr__(self, "_cls", cls.__name__)
+
+    def __getattr__(self, name):
+        nets = self._nets
+        if name not in nets:
+            raise ModelDefinitionError("unknown network '%s' (%s.networks declares: %s)"
+                                       % (name, self._cls, ", ".join(nets) or "none"))
+        k, net = list(nets).index(name), nets[name]
+
+        def apply(inputs):
+            if not isinstance(inputs, (list, tuple)) or len(inputs) != net.sizes[0]:
+                raise ModelDefinitionError("network '%s' takes a list of %d inputs (got %s)" % (
+                    name, net.sizes[0], len(inputs) if isinstance(inputs, (list, tuple)) else type(inputs).__name__))
+            return self._call(k, name, net, list(inputs))
+
+        return apply
+
+    __getitem__ = __getattr__
+
+    def __setattr__(self, name, value):
+        raise ModelDefinitionError("networks are read-only")
+
+
 class Trace(object):
     """The three functions of a model class traced into one Graph."""
 
     def __init__(self, cls):
         inst = cls.__new__(cls)  # (the functions are methods; nothing of nn.Module is touched by them)
         self.cls = cls
-        self.g = g = Graph()
+        self.networks = _class_networks(cls)
+        self.g = g = Graph(self.networks.values())
+        self._phase, self._called = "prepare", {}
+
+        def call(k, name, net, inputs):
+            if self._phase != "rhs":
+                raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only"
+                                           % (name, self._phase))
+            if name in self._called:
+                raise ModelDefinitionError("network '%s' is called twice: a network may be called at most once per rhs "
+                                           "evaluation (its adjoint dump has one slot per evaluation)" % name)
+            self._called[name] = True
+            return g.net(k, inputs)
+
+        object.__setattr__(inst, "net", _Networks(cls, call))
         N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
         th = _Named([(n, g.leaf("th", s)) for s, n in enumerate(P)], "parameter")
         cs = [g.leaf("c", q) for q in range(C)]
@@ -432,14 +584,22 @@ class Trace(object):
             raise ModelDefinitionError("%s.prepare must return a dict {name: value}" % cls.__name__)
         self.p_names = list(prepared)
         self.p_exprs = [g._arg(prepared[k]) for k in self.p_names]
+        self._phase = "initial_state"
         y0 = inst.initial_state(th, _Conditions(cs))
         self.y0 = self._state_list(y0, "initial_state", N)
+        self._phase = "rhs"
         # rhs sees the effective parameters and the treatments; the kernel's rhs has no c[], so each treatment it reads is
         # one more effective parameter (copied by prepare, no adjoint)
         NPU = len(self.p_names)
         p = _Named([(n, g.leaf("p", k)) for k, n in enumerate(self.p_names)], "effective parameter")
         self.dy = self._state_list(inst.rhs(g.leaf("t", 0), [g.leaf("y", j) for j in range(N)], p,
                                             _Conditions([g.leaf("p", NPU + q) for q in range(C)])), "rhs", N)
+        reached = {n.val for n in _topo(self.dy) if n.op == "net"}
+        for k, name in enumerate(self.networks):
+            if k not in reached:
+                raise ModelDefinitionError("%s: network '%s' is declared but %s" % (
+                    cls.__name__, name, "no derivative depends on its outputs" if name in self._called
+                    else "never called in rhs"))
         used = {n.val for n in _topo(self.dy) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]
         # remap the treatments rhs reads to consecutive parameter indices behind the named ones
@@ -507,12 +667,94 @@ class _Emitter(object):
         for n in _topo([x for _, _, x in assignments]):
             if n.op in _LEAVES or n.id in self.names:
                 continue
+            if n.op in ("net", "netout", "netbwd", "netbwd_in"):
+                self._emit_net(n)
+                continue
             name = "v%d" % len(self.names)
             self.lines.append("    const float %s = %s;" % (name, self.expr(n)))
             self.names[n.id] = name
         for lhs, how, n in assignments:
             self.lines.append("    %s %s %s;" % (lhs, how, self.ref(n)))
         return self.lines
+
+
+def _emit_net(self, n):
+    """Network nodes: the call nodes become one call of the struct's net<k>_forward / net<k>_vjp on small register arrays,
+    the output / input-adjoint nodes are elements of those arrays."""
+    k = n.val if n.op in ("net", "netbwd") else n.args[0].val
+    if n.op == "netout":
+        self.names[n.id] = "n%d_o[%d]" % (k, n.val)
+    elif n.op == "netbwd_in":
+        self.names[n.id] = "n%d_xb[%d]" % (k, n.val)
+    else:
+        I, _H, O = n.g.networks[k].sizes
+        refs = [self.ref(x) for x in n.args]
+        if n.op == "net":
+            self.lines += ["    const float n%d_x[%d] = {%s};" % (k, I, ", ".join(refs)),
+                           "    float n%d_o[%d];" % (k, O),
+                           "    net%d_forward(w, n%d_x, n%d_o);" % (k, k, k)]
+        else:
+            self.lines += ["    const float n%d_bx[%d] = {%s};" % (k, I, ", ".join(refs[:I])),
+                           "    const float n%d_ob[%d] = {%s};" % (k, O, ", ".join(refs[I:])),
+                           "    float n%d_xb[%d];" % (k, I),
+                           "    net%d_vjp<Ctx::DUMP>(w, n%d_bx, n%d_ob, n%d_xb, D, fs);" % (k, k, k, k)]
+        self.names[n.id] = "n%d" % k
+
+
+_Emitter._emit_net = _emit_net
+
+
+def _network_functions(networks):
+    """net<k>_forward / net<k>_vjp of every network as struct members: the hidden layer one unit at a time (register use
+    does not grow with n_hidden), the weights by uniform index through the constant address space (scalar loads)."""
+    out, w0, f0 = [], 0, 0
+    for k, net in enumerate(networks):
+        I, H, O = net.sizes
+        act = "fmaxf(z, 0.f)" if net.hidden == "relu" else "ftanh(z)"
+        dact = "(z > 0.f ? hub : 0.f)" if net.hidden == "relu" else "hub * (1.f - hu * hu)"
+        head = ["    const weights_ptr W1 = w + %d, b1 = W1 + %d, W2 = b1 + %d, b2 = W2 + %d;" % (w0, H * I, H, O * H)]
+        unit = ["      float z = b1[u];",
+                "      VIHDS_UNROLL for (int i = 0; i < %d; ++i) z = fmaf(W1[u * %d + i], x[i], z);" % (I, I),
+                "      const float hu = %s;" % act]
+        out += [
+            "  // network %d: %d -> %d (%s) -> %d; weights at %d (W1 [%d][%d], b1, W2 [%d][%d], b2), dump fields from %d" % (
+                k, I, H, net.hidden, O, w0, H, I, O, H, f0),
+            "  __device__ static void net%d_forward(weights_ptr w, const float* x, float* o) {" % k,
+            "    __asm__ volatile(\"\" ::: \"memory\");  // keep the weight loads inside the time loop (no hoist-and-spill)",
+        ] + head + [
+            "    VIHDS_UNROLL for (int j = 0; j < %d; ++j) o[j] = b2[j];" % O,
+            "    _Pragma(\"nounroll\") for (int u = 0; u < %d; ++u) {" % H,
+        ] + unit + [
+            "      VIHDS_UNROLL for (int j = 0; j < %d; ++j) o[j] = fmaf(W2[j * %d + u], hu, o[j]);" % (O, H),
+            "    }",
+            "  }",
+            "  // input adjoint xb; DUMP: fields x [%d] | hidden pre-activation adjoints [%d] | hidden activations [%d] | output" % (I, H, H),
+            "  // adjoints [%d] of this evaluation (D = its first float, fs = floats between fields)" % O,
+            "  template <bool DUMP>",
+            "  __device__ static void net%d_vjp(weights_ptr w, const float* x, const float* ob, float* xb, float* D, size_t fs) {" % k,
+            "    __asm__ volatile(\"\" ::: \"memory\");",
+        ] + head + [
+            "    VIHDS_UNROLL for (int i = 0; i < %d; ++i) xb[i] = 0.f;" % I,
+            "    if constexpr (DUMP) {",
+            "      VIHDS_UNROLL for (int i = 0; i < %d; ++i) D[(size_t)(%d + i) * fs] = x[i];" % (I, f0),
+            "      VIHDS_UNROLL for (int j = 0; j < %d; ++j) D[(size_t)(%d + j) * fs] = ob[j];" % (O, f0 + I + 2 * H),
+            "    }",
+            "    _Pragma(\"nounroll\") for (int u = 0; u < %d; ++u) {" % H,
+        ] + unit + [
+            "      float hub = 0.f;",
+            "      VIHDS_UNROLL for (int j = 0; j < %d; ++j) hub = fmaf(W2[j * %d + u], ob[j], hub);" % (O, H),
+            "      const float zub = %s;" % dact,
+            "      VIHDS_UNROLL for (int i = 0; i < %d; ++i) xb[i] = fmaf(W1[u * %d + i], zub, xb[i]);" % (I, I),
+            "      if constexpr (DUMP) {",
+            "        D[(size_t)(%d + u) * fs] = zub;" % (f0 + I),
+            "        D[(size_t)(%d + u) * fs] = hu;" % (f0 + I + H),
+            "      }",
+            "    }",
+            "  }",
+        ]
+        w0 += net.n_weights
+        f0 += net.n_fields
+    return out
 
 
 def _leaf_free(node, allowed):
@@ -566,6 +808,31 @@ def generate_source(cls, neural=False):
 
     names = ", ".join('"%s"' % n for n in P)
     key = cls.model_key
+    nets = list(tr.networks.values())
+    NW = sum(net.n_weights for net in nets)
+    if nets:
+        rhs_sig = ["  __device__ static void rhs(float t, const float* y, const float* p, const float* wg, float* dy) {",
+                   "    const weights_ptr w = (weights_ptr)wg;"]
+        # (Ctx: the adjoint kernel's context; Ctx::DUMP says whether this launch collects the weight gradient)
+        vjp_sig = ["  template <class Ctx>",
+                   "  __device__ static void rhs_vjp(float t, const float* y, const float* p, const float* wg, const float* v, float* yb,",
+                   "                                 float* pb, Ctx& ctx) {",
+                   "    const weights_ptr w = (weights_ptr)wg;",
+                   "    float* D = nullptr;",
+                   "    size_t fs = 0;",
+                   "    if constexpr (Ctx::DUMP) {",
+                   "      D = ctx.net_dump + (size_t)ctx.net_e * ctx.n;",
+                   "      fs = ctx.fstride;",
+                   "      ctx.net_e += 1;",
+                   "    }"]
+        net_decl = ["  static constexpr int NET_FIELDS = %d;  // floats the adjoint dumps per evaluation and trajectory" % sum(
+            net.n_fields for net in nets),
+                    "  typedef const __attribute__((address_space(4))) float* weights_ptr;"] + _network_functions(nets)
+    else:
+        rhs_sig = ["  __device__ static void rhs(float t, const float* y, const float* p, const float*, float* dy) {"]
+        vjp_sig = ["  __device__ static void rhs_vjp(float t, const float* y, const float* p, const float*, const float* v, float* yb,",
+                   "                                 float* pb) {"]
+        net_decl = []
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -576,11 +843,12 @@ def generate_source(cls, neural=False):
         "  static constexpr int N = %d;" % N,
         "  static constexpr int NS = %d;" % N,
         "  static constexpr bool NEURAL_PREC = false;",
-        "  static constexpr int NW = 0;",
+        "  static constexpr int NW = %d;" % NW,
         "  static constexpr int NC = %d;" % C,
         "  static constexpr int OBS = %s;" % obs_enum,
         "  static constexpr int NSLOT = %d;" % len(P),
         "  static constexpr int NP = %d;" % max(tr.NP, 1),
+    ] + net_decl + [
         "  __host__ static const char* slot_name(int s) {",
         "    static const char* n[] = {%s};" % names,
         "    return n[s];",
@@ -597,11 +865,10 @@ def generate_source(cls, neural=False):
         "  __device__ static void init_vjp(const float* yb, float* thb) {",
         body(init_vjp, False, "yb"),
         "  }",
-        "  __device__ static void rhs(float t, const float* y, const float* p, const float*, float* dy) {",
+    ] + rhs_sig + [
         body(rhs, True, "v", tr.c_slot),
         "  }",
-        "  __device__ static void rhs_vjp(float t, const float* y, const float* p, const float*, const float* v, float* yb,",
-        "                                 float* pb) {",
+    ] + vjp_sig + [
         body(rhs_vjp, True, "v", tr.c_slot),
         "  }",
         "};",
@@ -701,6 +968,8 @@ def register_kernel(cls, neural=False):
     if mid < 0:
         hip.check(mid, "vihds_model_register(%s)" % path)
     hip.MODELS[key] = mid
+    # what ops needs to contract the adjoint's dump: the networks' sizes, in the weight buffer's order
+    hip.GENERATED_NETWORKS[key] = [net.sizes for net in _class_networks(cls).values()]
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -716,6 +985,7 @@ class GeneratedOdeModel(OdeModel):
     parameter_names = None
     n_conditions = 0
     observe_kind = "default"
+    networks = None  # {name: Network}: learned terms of rhs (module docstring)
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -738,6 +1008,20 @@ class GeneratedOdeModel(OdeModel):
         super(GeneratedOdeModel, self).__init__(config)
         self.species = list(type(self).species)
         self.n_species = len(self.species)
+        # the networks' weights (created under the seed the caller set for the whole model, like every module here): the
+        # weight matrices as the reference's NeuralStates initialises them, the biases nn.Linear's default
+        nets = _class_networks(type(self))
+        if nets:
+            self.nets = torch.nn.ModuleDict()
+            for name, net in nets.items():
+                I, H, O = net.sizes
+                m = torch.nn.Module()
+                m.hidden, m.out = torch.nn.Linear(I, H), torch.nn.Linear(H, O)
+                torch.nn.init.xavier_uniform_(m.hidden.weight)
+                torch.nn.init.xavier_uniform_(m.out.weight)
+                self.nets[name] = m
+            self._flat_all = None
+            object.__setattr__(self, "net", _Networks(type(self), self._torch_call(self.network_weights)))
 
     # the three functions of a model
     def prepare(self, th, c):
@@ -760,8 +1044,24 @@ class GeneratedOdeModel(OdeModel):
         register_kernel(type(self), self._neural())
         return super(GeneratedOdeModel, self).kernel_slots()
 
+    def network_weights(self):
+        """{network name: (W1, b1, W2, b2)}: the nn.Parameters, as torch_problem takes them."""
+        return {name: (m.hidden.weight, m.hidden.bias, m.out.weight, m.out.bias) for name, m in self.nets.items()} \
+            if _class_networks(type(self)) else {}
+
+    def flat_weight_tensors(self):
+        """The kernels' weight buffer, tensor by tensor: every network in declaration order (W1, b1, W2, b2), then the
+        NeuralPrecisions weights."""
+        own = [t for w in self.network_weights().values() for t in w]
+        return own + super(GeneratedOdeModel, self).flat_weight_tensors()
+
     def neural_weights(self):
-        return self.precisions.flat_weights() if self._neural() else None
+        if not _class_networks(type(self)):
+            return self.precisions.flat_weights() if self._neural() else None
+        if self._flat_all is None:
+            from vihds import ops
+            object.__setattr__(self, "_flat_all", ops.FlatParameters())
+        return self._flat_all(self.flat_weight_tensors())
 
     def problem_kwargs(self, config):
         if self._neural():
@@ -769,15 +1069,42 @@ class GeneratedOdeModel(OdeModel):
         return {}
 
     def summaries(self, writer, epoch):
+        if writer is not None and _class_networks(type(self)):
+            from vihds.utils import variable_summaries
+
+            for name, m in self.nets.items():
+                for layer, mod in (("hidden", m.hidden), ("out", m.out)):
+                    variable_summaries(writer, epoch, mod.weight, "net_%s_%s_weights" % (name, layer), False)
+                    variable_summaries(writer, epoch, mod.bias, "net_%s_%s_bias" % (name, layer), False)
         if self._neural():
             self.precisions.summaries(writer, epoch)
 
     # the same definition as a PyTorch right-hand side
+    @staticmethod
+    def _torch_call(weights):
+        """The eager form of a network call; `weights` returns {name: (W1, b1, W2, b2)}."""
+        def call(_k, name, net, inputs):
+            W1, b1, W2, b2 = weights()[name]
+            xs = [v if isinstance(v, torch.Tensor) else torch.as_tensor(float(v), dtype=W1.dtype, device=W1.device)
+                  for v in inputs]
+            x = torch.stack(torch.broadcast_tensors(*xs), dim=-1).to(W1.dtype)
+            return list(torch.unbind(net_forward_ref(net, (W1, b1, W2, b2), x)[2], dim=-1))
+
+        return call
+
     @classmethod
-    def torch_problem(cls, th, cond):
+    def torch_problem(cls, th, cond, weights=None):
         """(rhs, x0) in the convention of oracle.make_*: th maps parameter names to [B, S] tensors, cond is [B, C] (log(1 +
-        treatment), as the data holds it); rhs(t, state [B, S, N]) -> [B, S, N] of the species (no precision states)."""
+        treatment), as the data holds it); rhs(t, state [B, S, N]) -> [B, S, N] of the species (no precision states).
+        weights: {network name: (W1 [H][I], b1 [H], W2 [O][H], b2 [O])} for a model with networks (an instance's
+        network_weights(), or tensors of the caller's own that require grad: autograd then gives the weight gradients)."""
         inst = cls.__new__(cls)
+        nets = _class_networks(cls)
+        if nets:
+            if weights is None or any(n not in weights for n in nets):
+                raise ValueError("%s.torch_problem needs weights={%s}" % (cls.__name__, ", ".join("'%s': (W1, b1, W2, b2)" % n
+                                                                                           for n in nets)))
+            object.__setattr__(inst, "net", _Networks(cls, cls._torch_call(lambda: weights)))
         N = len(cls.species)
         B, S = th[cls.parameter_names[0]].shape
         ref = th[cls.parameter_names[0]]
@@ -820,3 +1147,19 @@ def _validate(cls):
                                    "the precisions)" % (name, len(cls.parameter_names), hip.VIHDS_MAX_SLOTS - 4))
     if not isinstance(cls.n_conditions, int) or cls.n_conditions < 0:
         raise ModelDefinitionError("%s.n_conditions must be an integer >= 0" % name)
+    nets = getattr(cls, "networks", None)
+    if nets is None:
+        return
+    if not isinstance(nets, dict) or not all(isinstance(k, str) and k.isidentifier() and isinstance(v, Network)
+                                             for k, v in nets.items()):
+        raise ModelDefinitionError("%s.networks must be a dict {name: Network(...)}" % name)
+    if len(nets) > MAX_NETWORKS:
+        raise ModelDefinitionError("%s: %d networks; a generated model holds at most %d" % (name, len(nets), MAX_NETWORKS))
+    for k, net in nets.items():
+        for what, v, top in (("n_inputs", net.n_inputs, MAX_NET_INPUTS), ("n_hidden", net.n_hidden, MAX_NET_HIDDEN),
+                             ("n_outputs", net.n_outputs, MAX_NET_OUTPUTS)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
+                raise ModelDefinitionError("%s: network '%s' has %s = %r; supported: 1 .. %d" % (name, k, what, v, top))
+        if net.hidden not in NET_ACTIVATIONS:
+            raise ModelDefinitionError("%s: network '%s' has hidden = %r; supported: %s"
+                                       % (name, k, net.hidden, ", ".join(NET_ACTIVATIONS)))

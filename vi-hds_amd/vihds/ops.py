@@ -115,6 +115,9 @@ class OdeProblemSpec:
         else:
             self.n_states = hip.lib().vihds_model_n_states(hip.MODELS[model])
             self.n_species = hip.lib().vihds_model_n_species(hip.MODELS[model])
+        # a generated model's own networks [(n_inputs, n_hidden, n_outputs)]: their weights lead the weight buffer, their
+        # dump fields lead the adjoint's aux buffer (decoder_weight_grads)
+        self.networks = list(hip.GENERATED_NETWORKS.get(model, ()))
         self.covers_all_rows = len({row_of[s] for s in self.slots}) == n_rows
         self.unwritten_rows = sorted(set(range(n_rows)) - {row_of[s] for s in self.slots})  # rows the adjoint leaves alone
         self.cache = {}  # device-side constants derived from this spec
@@ -285,6 +288,8 @@ class OdeSolveObserve(torch.autograd.Function):
             g_logp = _c(g_logp)
         g_traj, g_xpred = _c(g_traj), _c(g_xpred)
         aux = torch.empty(n_aux, device=theta.device, dtype=torch.float32) if n_aux > 0 else None
+        if ctx.spec.networks and aux is None:
+            g_w = None  # (no dump, no weight gradient: the library refuses the one without the other)
         rc = _launch("ode_bwd", lambda: hip.lib().vihds_ode_bwd(
             ctypes.byref(ctx.prob), hip.ptr(theta), hip.ptr(cond), hip.ptr(dev1hot), hip.ptr(times), hip.ptr(obs),
             hip.ptr(weights), hip.ptr(traj), hip.ptr(g_traj), hip.ptr(g_xpred), hip.ptr(g_logp), hip.ptr(g_theta),
@@ -297,7 +302,7 @@ class OdeSolveObserve(torch.autograd.Function):
             if blackbox:
                 g_w = blackbox_weight_grads(ctx.spec, ctx.prob, aux, theta, cond, dev1hot)
             else:
-                neural_precision_weight_grads(ctx.spec, ctx.prob, aux, g_w)
+                decoder_weight_grads(ctx.spec, ctx.prob, aux, g_w)
         grads = (None, g_theta, None, None, None, None, g_w)
         if len(ctx.needs_input_grad) > 7:
             g_off = None
@@ -627,6 +632,63 @@ class ThetaOdeFused(torch.autograd.Function):
         return (g(q), None, None, None, None, None, None, None, None, None, None, None, None, None, g(w), g(W), g(bvec), None)
 
 
+def _gram_into(F, C, rects, X, g_w):
+    """vihds_gram_blocks over the dump X = [F][C] (a view of the aux buffer) into g_w (a view of the gradient buffer)."""
+    n_scr = hip.lib().vihds_gram_scratch_floats(C, len(rects), rects)
+    if n_scr <= 0:
+        raise RuntimeError("vihds_gram_scratch_floats: %s" % hip.lib().vihds_last_error().decode())
+    scratch = torch.empty(n_scr, device=X.device, dtype=torch.float32)
+    rc = hip.lib().vihds_gram_blocks(F, C, len(rects), rects, hip.ptr(X), hip.ptr(scratch), hip.ptr(g_w),
+                                     hip.current_stream())
+    hip.check(rc, "vihds_gram_blocks")
+
+
+def _rects(plan):
+    rects = (hip.GramRect * len(plan))()
+    for k, (a0, na, b0, nb, d0, sa) in enumerate(plan):
+        (rects[k].a0, rects[k].na, rects[k].b0, rects[k].nb, rects[k].dest0, rects[k].dest_stride_a,
+         rects[k].dest_stride_b) = (a0, na, b0, nb, d0, sa, 1)
+    return rects
+
+
+def decoder_weight_grads(spec, prob, aux, g_w):
+    """The weight gradient of a thread-per-trajectory adjoint from its dump.  A generated model's own networks come first,
+    in the dump ([fields][E][n], per network x [I] | hidden pre-activation adjoints [H] | hidden activations [H] | output
+    adjoints [O]) and in the buffer (W1 [H][I], b1 [H], W2 [O][H], b2 [O]): W1 and W2 are two rectangles of
+    vihds_gram_blocks per network, the biases row sums of the adjoint fields -- every sum in a fixed order, so the result
+    is the same bits run to run.  The precision network's section (neural_precision_weight_grads) follows."""
+    if not spec.networks:
+        return neural_precision_weight_grads(spec, prob, aux, g_w)
+    neural = spec.n_species < spec.n_states
+    F_all = sum(I + 2 * H + O for I, H, O in spec.networks)
+    if neural:
+        F_all += 8 + (spec.n_species + 1) + 2 * max(int(spec.proto.n_hidden_prec), 0)
+    C = aux.numel() // F_all
+    f0 = w0 = 0
+    for k, (I, H, O) in enumerate(spec.networks):
+        F = I + 2 * H + O
+        key = ("net_rects", k)
+        if key not in spec.cache:
+            spec.cache[key] = _rects([(I, H, 0, I, 0, I), (I + 2 * H, O, I + H, H, H * I + H, H)])
+        X, g = aux[f0 * C:(f0 + F) * C], g_w[w0:w0 + H * I + H + O * H + O]
+        _gram_into(F, C, spec.cache[key], X, g)
+        X = X.view(F, C)
+        g[H * I:H * I + H] = X[I:I + H].sum(1)
+        g[H * I + H + O * H:] = X[I + 2 * H:].sum(1)
+        f0, w0 = f0 + F, w0 + g.numel()
+    if neural:
+        # (the adjoint of such a model adds no bias sums with atomics: they are row sums of the dump's fields 0..3 / 4..7)
+        g, X = g_w[w0:], aux[f0 * C:]
+        neural_precision_weight_grads(spec, prob, X, g)
+        NIN, Hp = spec.n_species + 1, max(int(spec.proto.n_hidden_prec), 0)
+        o_bp = 4 * NIN if Hp < 1 else Hp * NIN + Hp + 4 * Hp
+        o_bd = o_bp + 4 + (4 * NIN if Hp < 1 else 4 * Hp)
+        sums = X.view(-1, C)[:8].sum(1)
+        g[o_bp:o_bp + 4] = sums[:4]
+        g[o_bd:o_bd + 4] = sums[4:]
+    return g_w
+
+
 def neural_precision_weight_grads(spec, prob, aux, g_w):
     """White-box model + neural precisions: the two weight matrices of NeuralPrecisions (reference precisions.py:55-61,
     76-87; buffer order Wp [4][NIN], bp [4], Wd [4][NIN], bd [4]) from the adjoint kernel's dump [8+NIN][E][n] --
@@ -634,7 +696,7 @@ def neural_precision_weight_grads(spec, prob, aux, g_w):
     into g_w by vihds_gram_blocks; the biases were already added to g_w by the kernel."""
     NIN = spec.n_states - 4 + 1
     H = max(int(spec.proto.n_hidden_prec), 0)
-    F, n = 8 + NIN + 2 * H, prob.B * prob.S
+    F = 8 + NIN + 2 * H
     C = aux.numel() // F
     key = "prec_rects"
     if key not in spec.cache:
@@ -1471,7 +1533,7 @@ class GeneralTail(StepTail):
                     if blackbox:
                         gw = blackbox_weight_grads(spec, prob, aux, theta, cond, dev1hot)
                     else:
-                        gw = neural_precision_weight_grads(spec, prob, aux, g_w)
+                        gw = decoder_weight_grads(spec, prob, aux, g_w)
                 extras = [(fo, size, gw, fo, None, 1, 0) for (_f, _c2, fo, size) in chunks]
         # ---- the tail
         opt = self.optimizer
