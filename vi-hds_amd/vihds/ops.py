@@ -6,6 +6,7 @@ is no fallback: tensors must live on a HIP device.
 """
 import ctypes
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -65,6 +66,16 @@ def _require_cuda(*tensors):
 
 def _c(t):
     return None if t is None else t.contiguous()
+
+
+def saved_state(node, function):
+    """The saved tensors of one of `function`'s nodes (its ctx, or the backward node another class was handed) by the names
+    in `function.SAVED` (at the head of the class, in the order of its one save_for_backward call; a count that no longer
+    matches fails here): the only reader of saved_tensors."""
+    tensors = node.saved_tensors
+    assert len(tensors) == len(function.SAVED), "%s saved %d tensors, SAVED names %d" % (
+        function.__name__, len(tensors), len(function.SAVED))
+    return SimpleNamespace(**dict(zip(function.SAVED, tensors)))
 
 
 class OdeProblemSpec:
@@ -176,6 +187,8 @@ class AdaptiveOdeSolve(torch.autograd.Function):
     synchronises; with check=False nothing waits and the pair of launches can be captured in a hipGraph.  weights: the
     precision network of a *_precisions model (no hidden layer); its gradient comes back from the adjoint launch."""
 
+    SAVED = ("theta", "cond", "times", "dev1hot", "ws", "weights")
+
     @staticmethod
     def forward(ctx, spec, theta, cond, times, dev1hot, rtol, atol, max_steps, check, stats, weights=None):
         _require_cuda(theta, cond, times)
@@ -207,15 +220,15 @@ class AdaptiveOdeSolve(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_traj):
-        theta, cond, times, dev1hot, ws, weights = ctx.saved_tensors
-        g_theta = torch.empty_like(theta) if ctx.spec.covers_all_rows else torch.zeros_like(theta)
+        s = saved_state(ctx, AdaptiveOdeSolve)
+        g_theta = torch.empty_like(s.theta) if ctx.spec.covers_all_rows else torch.zeros_like(s.theta)
         if g_traj is None:
-            return (None, torch.zeros_like(theta)) + (None,) * 9
+            return (None, torch.zeros_like(s.theta)) + (None,) * 9
         g_traj = _c(g_traj)
-        g_w = torch.zeros_like(weights) if weights is not None else None
+        g_w = torch.zeros_like(s.weights) if s.weights is not None else None
         rc = _launch("ode_adaptive_bwd", lambda: hip.lib().vihds_ode_adaptive_bwd_w(
-            ctypes.byref(ctx.prob), hip.ptr(theta), hip.ptr(cond), hip.ptr(dev1hot), hip.ptr(weights), hip.ptr(times),
-            ctx.max_steps, hip.ptr(ws), hip.ptr(g_traj), hip.ptr(g_theta), hip.ptr(g_w), hip.current_stream()))
+            ctypes.byref(ctx.prob), hip.ptr(s.theta), hip.ptr(s.cond), hip.ptr(s.dev1hot), hip.ptr(s.weights), hip.ptr(s.times),
+            ctx.max_steps, hip.ptr(s.ws), hip.ptr(g_traj), hip.ptr(g_theta), hip.ptr(g_w), hip.current_stream()))
         hip.check(rc, "vihds_ode_adaptive_bwd")
         return (None, g_theta) + (None,) * 8 + (g_w,)
 
@@ -236,6 +249,8 @@ class OdeSolveObserve(torch.autograd.Function):
     row_offset is its token [n*D + n]; backward hands it the layer's weight and bias gradients from ONE launch
     (vihds_offset_rows_bwd) that also routes the row gradients.
     """
+
+    SAVED = ("theta", "cond", "times", "obs", "traj", "dev1hot", "weights")
 
     @staticmethod
     def forward(ctx, spec, theta, cond, times, obs, dev1hot, weights, row_offset=None, row_offset_map=None,
@@ -266,7 +281,8 @@ class OdeSolveObserve(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_traj, g_xpred, g_logp):
-        theta, cond, times, obs, traj, dev1hot, weights = ctx.saved_tensors
+        s = saved_state(ctx, OdeSolveObserve)
+        theta, dev1hot, weights = s.theta, s.dev1hot, s.weights
         # the kernel writes every slot row; rows that are not slots (if any) must read as zero -- unless they are exactly
         # the rows the "linear" row-offset launch below assigns (dr_blackbox: the sampled y rows)
         rom = ctx.row_offset_map
@@ -291,18 +307,16 @@ class OdeSolveObserve(torch.autograd.Function):
         if ctx.spec.networks and aux is None:
             g_w = None  # (no dump, no weight gradient: the library refuses the one without the other)
         rc = _launch("ode_bwd", lambda: hip.lib().vihds_ode_bwd(
-            ctypes.byref(ctx.prob), hip.ptr(theta), hip.ptr(cond), hip.ptr(dev1hot), hip.ptr(times), hip.ptr(obs),
-            hip.ptr(weights), hip.ptr(traj), hip.ptr(g_traj), hip.ptr(g_xpred), hip.ptr(g_logp), hip.ptr(g_theta),
+            ctypes.byref(ctx.prob), hip.ptr(theta), hip.ptr(s.cond), hip.ptr(dev1hot), hip.ptr(s.times), hip.ptr(s.obs),
+            hip.ptr(weights), hip.ptr(s.traj), hip.ptr(g_traj), hip.ptr(g_xpred), hip.ptr(g_logp), hip.ptr(g_theta),
             hip.ptr(g_w), hip.ptr(aux), hip.current_stream()))
         hip.check(rc, "vihds_ode_bwd")
-        if aux is not None and ctx.needs_input_grad[6] and not blackbox and hip.lib().vihds_ode_bwd_reduces_weights(
-                ctypes.byref(ctx.prob)):
-            pass  # (lane-split relay adjoint: the call above has already added the weight gradients up into g_w)
-        elif aux is not None and ctx.needs_input_grad[6]:
+        if aux is not None and ctx.needs_input_grad[6]:
             if blackbox:
-                g_w = blackbox_weight_grads(ctx.spec, ctx.prob, aux, theta, cond, dev1hot)
-            else:
+                g_w = blackbox_weight_grads(ctx.spec, ctx.prob, aux, theta, s.cond, dev1hot)
+            elif not hip.lib().vihds_ode_bwd_reduces_weights(ctypes.byref(ctx.prob)):
                 decoder_weight_grads(ctx.spec, ctx.prob, aux, g_w)
+            # (else a lane-split relay adjoint: the call above has already added the weight gradients up into g_w)
         grads = (None, g_theta, None, None, None, None, g_w)
         if len(ctx.needs_input_grad) > 7:
             g_off = None
@@ -408,11 +422,57 @@ class EncoderUnsupported(RuntimeError):
     caller uses the nn.Module encoder instead."""
 
 
+def _packed_opts(q_rows):
+    """vihds_theta_opts of the packed theta stage, forward or backward."""
+    opts = hip.ThetaOpts()
+    opts.q_rows, opts.q_prec_is_log = hip.ptr(q_rows), 1
+    return opts
+
+
+def _theta_stage(q_all, q_rows, u):
+    """What every launch of the packed theta stage (q's [2P,B] table of means and LOG-precisions in the row order `q_rows`)
+    takes besides the tables: its vihds_theta_opts and the draws.  u: the [B,S,P] standard normals, or a KernelNormal -- the
+    kernel then draws them into the tensor returned here.  Returns (opts, u, rng_state or None, P, B, S)."""
+    P, B = q_all.shape[0] // 2, q_all.shape[1]
+    opts, rng_state = _packed_opts(q_rows), None
+    if isinstance(u, KernelNormal):
+        rng_state = u.state
+        opts.rng, opts.S_total, opts.s_offset = rng_state.data_ptr(), u.S_total, u.s_offset
+        u = torch.empty(u.shape, device=q_all.device, dtype=torch.float32)
+    else:
+        _require_cuda(u)
+        u = _c(u)
+    if u.dim() != 3 or u.shape[0] != B or u.shape[2] != P:
+        raise RuntimeError("u must be [B,S,P]")
+    return opts, u, rng_state, P, B, u.shape[1]
+
+
+def _theta_outputs(n_rows, B, S, dev):
+    """theta [n_rows,B,S], log_q [B,S], log_p [B,S] for a theta-stage launch to fill."""
+    return (torch.empty((n_rows, B, S), device=dev, dtype=torch.float32),
+            torch.empty((B, S), device=dev, dtype=torch.float32), torch.empty((B, S), device=dev, dtype=torch.float32))
+
+
+def _theta_bwd_packed(s, g_theta, g_log_q, g_log_p, opts):
+    """vihds_theta_bwd on a packed theta stage's saved state `s`: the ONE [2P,B] gradient (d/d mu, d/d log_prec) in q's row
+    order.  opts: _packed_opts', with whatever the caller added (an IWAE job, the scale of g_theta)."""
+    P, B, S = s.q_all.shape[0] // 2, s.q_all.shape[1], s.u.shape[1]
+    g_all = torch.empty_like(s.q_all)
+    rc = hip.lib().vihds_theta_bwd(P, B, S, hip.ptr(s.kind), hip.ptr(s.q_all), hip.ptr(s.q_all), hip.ptr(s.p_mu),
+                                   hip.ptr(s.p_prec), hip.ptr(s.clip_lo), hip.ptr(s.clip_hi), hip.ptr(s.u),
+                                   hip.ptr(_c(g_theta)), hip.ptr(_c(g_log_q)), hip.ptr(_c(g_log_p)), hip.ptr(g_all),
+                                   hip.ptr(g_all), ctypes.byref(opts), hip.current_stream())
+    hip.check(rc, "vihds_theta_bwd")
+    return g_all
+
+
 class OdeLogLikFused(torch.autograd.Function):
     """Training fast path (vihds_ode_logp_grad): per-species log-likelihood [4,B,S] and, in the same launch, the theta
     gradient for a unit upstream gradient; neither trajectory nor x_predict is produced.  backward: the ELBO hands
     back ONE [B,S] weight for all four signals (a stride-0 expand, see IwaeLoss), and the adjoint is linear in it:
     g_theta = w * g_unit.  Any other upstream gradient falls back to the two-kernel path."""
+
+    SAVED = ("theta", "cond", "times", "obs", "dev1hot", "g_unit")
 
     @staticmethod
     def forward(ctx, spec, theta, cond, times, obs, dev1hot):
@@ -437,12 +497,12 @@ class OdeLogLikFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_logp):
-        theta, cond, times, obs, dev1hot, g_unit = ctx.saved_tensors
+        s = saved_state(ctx, OdeLogLikFused)
         if g_logp.dim() == 3 and g_logp.stride(0) == 0:
-            return None, g_unit * g_logp[0], None, None, None, None
+            return None, s.g_unit * g_logp[0], None, None, None, None
         with torch.enable_grad():  # per-species weights: the general adjoint needs the trajectory after all
-            th = theta.detach().requires_grad_(True)
-            _traj, _xpred, logp = OdeSolveObserve.apply(ctx.spec, th, cond, times, obs, dev1hot, None)
+            th = s.theta.detach().requires_grad_(True)
+            _traj, _xpred, logp = OdeSolveObserve.apply(ctx.spec, th, s.cond, s.times, s.obs, s.dev1hot, None)
             (g_theta,) = torch.autograd.grad(logp, th, g_logp)
         return None, g_theta, None, None, None, None
 
@@ -454,29 +514,21 @@ class DecoderStepFused(torch.autograd.Function):
     w_std, z or None, rng_state or None, relevance, is_default).  Returns (theta, log_q, log_p, u, logp).
     backward: one theta_bwd launch consuming g_unit scaled by the IWAE weight inside the kernel."""
 
+    SAVED = ("q_all", "kind", "p_mu", "p_prec", "clip_lo", "clip_hi", "u", "q_rows", "g_unit", "theta", "cond", "times", "obs",
+             "dev1hot")
+
     @staticmethod
     def forward(ctx, q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, n_rows, q_rows, spec, cond, times, obs, dev1hot,
                 cond_job):
         _require_cuda(q_all, kind, p_mu, p_prec, clip_lo, clip_hi, q_rows, cond, times, obs)
         q_all, cond, times, obs = _c(q_all), _c(cond), _c(times), _c(obs)
         dev1hot = _c(dev1hot)
-        P, B = q_all.shape[0] // 2, q_all.shape[1]
-        opts = hip.ThetaOpts()
-        opts.q_rows, opts.q_prec_is_log = hip.ptr(q_rows), 1
-        if isinstance(u, KernelNormal):
-            rng, u = u, torch.empty(u.shape, device=q_all.device, dtype=torch.float32)
-            opts.rng, opts.S_total, opts.s_offset = rng.state.data_ptr(), rng.S_total, rng.s_offset
-        else:
-            _require_cuda(u)
-            u = _c(u)
-        S, T = u.shape[1], times.shape[0]
+        opts, u, _rng_state, P, B, S = _theta_stage(q_all, q_rows, u)
         if n_rows != spec.n_rows:
             raise RuntimeError("theta has %d rows, problem expects %d" % (n_rows, spec.n_rows))
-        prob = spec.bind(B, S, T)
+        prob = spec.bind(B, S, times.shape[0])
         dev = q_all.device
-        theta = torch.empty((n_rows, B, S), device=dev, dtype=torch.float32)
-        log_q = torch.empty((B, S), device=dev, dtype=torch.float32)
-        log_p = torch.empty((B, S), device=dev, dtype=torch.float32)
+        theta, log_q, log_p = _theta_outputs(n_rows, B, S, dev)
         logp = torch.empty((4, B, S), device=dev, dtype=torch.float32)
         g_unit = torch.empty_like(theta) if spec.covers_all_rows else torch.zeros_like(theta)
         co = None
@@ -502,11 +554,8 @@ class DecoderStepFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_theta, g_log_q, g_log_p, _g_u, g_logp):
-        (q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, q_rows, g_unit, theta, cond, times, obs,
-         dev1hot) = ctx.saved_tensors
-        P, B, S = q_all.shape[0] // 2, q_all.shape[1], u.shape[1]
-        opts = hip.ThetaOpts()
-        opts.q_rows, opts.q_prec_is_log = hip.ptr(q_rows), 1
+        s = saved_state(ctx, DecoderStepFused)
+        g_unit, opts = s.g_unit, _packed_opts(s.q_rows)
         keep = job = ijob = None
         if g_logp is not None and g_logp.dim() == 3 and g_logp.stride(0) == 0:
             job = _PENDING_IWAE.pop(g_logp[0].data_ptr(), None)  # a deferred IwaeLoss node upstream (fused_iwae_backward)
@@ -522,30 +571,22 @@ class DecoderStepFused(torch.autograd.Function):
             g_th, g_log_q, g_log_p = g_unit, None, None
         elif job is not None:
             _run_iwae_job(job)  # some other combination of upstream gradients: the ordinary launch, then as usual
-        if ijob is not None:
-            pass
-        elif g_logp is None:
-            g_th = _c(g_theta)
-        elif g_logp.dim() == 3 and g_logp.stride(0) == 0 and g_theta is None:
-            keep = _c(g_logp[0])
-            g_th, opts.g_theta_scale = g_unit, keep.data_ptr()  # the kernel applies the IWAE weight
-        else:
-            if g_logp.dim() == 3 and g_logp.stride(0) == 0:
-                g_ode = g_unit * g_logp[0]
-            else:  # per-species weights: general adjoint through the trajectory
-                with torch.enable_grad():
-                    th = theta.detach().requires_grad_(True)
-                    _t, _x, lp = OdeSolveObserve.apply(ctx.spec, th, cond, times, obs, dev1hot, None)
-                    (g_ode,) = torch.autograd.grad(lp, th, g_logp)
-            g_th = g_ode if g_theta is None else g_ode + g_theta
-        g_log_q, g_log_p = _c(g_log_q), _c(g_log_p)
-        g_all = torch.empty_like(q_all)
-        rc = hip.lib().vihds_theta_bwd(P, B, S, hip.ptr(kind), hip.ptr(q_all), hip.ptr(q_all), hip.ptr(p_mu),
-                                       hip.ptr(p_prec), hip.ptr(clip_lo), hip.ptr(clip_hi), hip.ptr(u),
-                                       hip.ptr(g_th), hip.ptr(g_log_q), hip.ptr(g_log_p), hip.ptr(g_all),
-                                       hip.ptr(g_all), ctypes.byref(opts), hip.current_stream())
-        hip.check(rc, "vihds_theta_bwd")
-        return (g_all,) + (None,) * 14
+        if ijob is None:
+            if g_logp is None:
+                g_th = _c(g_theta)
+            elif g_logp.dim() == 3 and g_logp.stride(0) == 0 and g_theta is None:
+                keep = _c(g_logp[0])
+                g_th, opts.g_theta_scale = g_unit, keep.data_ptr()  # the kernel applies the IWAE weight
+            else:
+                if g_logp.dim() == 3 and g_logp.stride(0) == 0:
+                    g_ode = g_unit * g_logp[0]
+                else:  # per-species weights: general adjoint through the trajectory
+                    with torch.enable_grad():
+                        th = s.theta.detach().requires_grad_(True)
+                        _t, _x, lp = OdeSolveObserve.apply(ctx.spec, th, s.cond, s.times, s.obs, s.dev1hot, None)
+                        (g_ode,) = torch.autograd.grad(lp, th, g_logp)
+                g_th = g_ode if g_theta is None else g_ode + g_theta
+        return (_theta_bwd_packed(s, g_th, g_log_q, g_log_p, opts),) + (None,) * 14
 
 
 class ThetaOdeFused(torch.autograd.Function):
@@ -555,30 +596,21 @@ class ThetaOdeFused(torch.autograd.Function):
     step's backward is ops.GeneralTail (which reads this node's saved tensors).  Returns (theta, log_q, log_p, u, traj, logp).
     backward (a caller that runs autograd after all): the unfused ops are replayed on the saved draws and differentiated."""
 
+    SAVED = ("q_all", "kind", "p_mu", "p_prec", "clip_lo", "clip_hi", "u", "q_rows", "theta", "cond", "times", "obs", "traj",
+             "dev1hot", "weights", "off_w", "off_b")
+
     @staticmethod
     def forward(ctx, q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, n_rows, q_rows, spec, cond, times, obs, dev1hot, weights,
                 off_w, off_b, off_rows):
         _require_cuda(q_all, kind, p_mu, p_prec, clip_lo, clip_hi, q_rows, cond, times, obs)
         q_all, cond, times, obs, dev1hot = _c(q_all), _c(cond), _c(times), _c(obs), _c(dev1hot)
-        P, B = q_all.shape[0] // 2, q_all.shape[1]
-        opts = hip.ThetaOpts()
-        opts.q_rows, opts.q_prec_is_log = hip.ptr(q_rows), 1
-        rng_state = None
-        if isinstance(u, KernelNormal):
-            rng, u = u, torch.empty(u.shape, device=q_all.device, dtype=torch.float32)
-            opts.rng, opts.S_total, opts.s_offset = rng.state.data_ptr(), rng.S_total, rng.s_offset
-            rng_state = rng.state
-        else:
-            _require_cuda(u)
-            u = _c(u)
-        S, T = u.shape[1], times.shape[0]
+        opts, u, rng_state, P, B, S = _theta_stage(q_all, q_rows, u)
+        T = times.shape[0]
         if n_rows != spec.n_rows:
             raise RuntimeError("theta has %d rows, problem expects %d" % (n_rows, spec.n_rows))
         prob = spec.bind(B, S, T)
         dev = q_all.device
-        theta = torch.empty((n_rows, B, S), device=dev, dtype=torch.float32)
-        log_q = torch.empty((B, S), device=dev, dtype=torch.float32)
-        log_p = torch.empty((B, S), device=dev, dtype=torch.float32)
+        theta, log_q, log_p = _theta_outputs(n_rows, B, S, dev)
         traj = torch.empty((T, spec.n_states, B, S), device=dev, dtype=torch.float32)
         logp = torch.empty((4, B, S), device=dev, dtype=torch.float32)
         off = None
@@ -607,20 +639,20 @@ class ThetaOdeFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_theta, g_log_q, g_log_p, _g_u, g_traj, g_logp):
-        (q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, q_rows, _theta, cond, times, obs, _traj, dev1hot, weights, off_w,
-         off_b) = ctx.saved_tensors
+        s = saved_state(ctx, ThetaOdeFused)
         with torch.enable_grad():
-            q = q_all.detach().requires_grad_(True)
-            w = weights.detach().requires_grad_(True) if weights is not None else None
-            W = off_w.detach().requires_grad_(True) if off_w is not None else None
-            bvec = off_b.detach().requires_grad_(True) if off_b is not None else None
-            th, lq, lp, _u = ThetaSampleLogProbPacked.apply(q, kind, p_mu, p_prec, clip_lo, clip_hi, u, ctx.n_rows, q_rows)
+            q = s.q_all.detach().requires_grad_(True)
+            w = s.weights.detach().requires_grad_(True) if s.weights is not None else None
+            W = s.off_w.detach().requires_grad_(True) if s.off_w is not None else None
+            bvec = s.off_b.detach().requires_grad_(True) if s.off_b is not None else None
+            th, lq, lp, _u = ThetaSampleLogProbPacked.apply(q, s.kind, s.p_mu, s.p_prec, s.clip_lo, s.clip_hi, s.u, ctx.n_rows,
+                                                            s.q_rows)
             token, rom = None, None
             if ctx.row_offset_map is not None:
                 src, dst, n, _ = ctx.row_offset_map
-                token = OffsetRows.apply(W, bvec, dev1hot, th.detach(), src, dst)
+                token = OffsetRows.apply(W, bvec, s.dev1hot, th.detach(), src, dst)
                 rom = ctx.row_offset_map
-            tr, _xp, lg = OdeSolveObserve.apply(ctx.spec, th, cond, times, obs, dev1hot, w, token, rom, False)
+            tr, _xp, lg = OdeSolveObserve.apply(ctx.spec, th, s.cond, s.times, s.obs, s.dev1hot, w, token, rom, False)
             outs, gouts = [], []
             for o, g in ((th, g_theta), (lq, g_log_q), (lp, g_log_p), (tr, g_traj), (lg, g_logp)):
                 if g is not None:
@@ -862,6 +894,8 @@ class ThetaSampleLogProb(torch.autograd.Function):
     returns theta [n_rows,B,S] (rows P.. are zero, for the caller to fill), log_q [B,S], log_p [B,S]
     """
 
+    SAVED = ("q_mu", "q_prec", "kind", "p_mu", "p_prec", "clip_lo", "clip_hi", "u")
+
     @staticmethod
     def forward(ctx, q_mu, q_prec, kind, p_mu, p_prec, clip_lo, clip_hi, u, n_rows):
         _require_cuda(q_mu, q_prec, kind, p_mu, p_prec, clip_lo, clip_hi, u)
@@ -871,9 +905,7 @@ class ThetaSampleLogProb(torch.autograd.Function):
         if u.shape[0] != B or u.shape[2] != P:
             raise RuntimeError("u must be [B,S,P]")
         # rows P.. are reserved for the caller (filled in place, e.g. by the device-conditioner kernel)
-        theta = torch.empty((max(n_rows, P), B, S), device=u.device, dtype=torch.float32)
-        log_q = torch.empty((B, S), device=u.device, dtype=torch.float32)
-        log_p = torch.empty((B, S), device=u.device, dtype=torch.float32)
+        theta, log_q, log_p = _theta_outputs(max(n_rows, P), B, S, u.device)
         rc = hip.lib().vihds_theta_fwd(P, B, S, hip.ptr(kind), hip.ptr(q_mu), hip.ptr(q_prec), hip.ptr(p_mu),
                                        hip.ptr(p_prec), hip.ptr(clip_lo), hip.ptr(clip_hi), hip.ptr(u),
                                        hip.ptr(theta), hip.ptr(log_q), hip.ptr(log_p), None, hip.current_stream())
@@ -884,14 +916,14 @@ class ThetaSampleLogProb(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_theta, g_log_q, g_log_p):
-        q_mu, q_prec, kind, p_mu, p_prec, clip_lo, clip_hi, u = ctx.saved_tensors
-        P, B = q_mu.shape
-        S = u.shape[1]
+        s = saved_state(ctx, ThetaSampleLogProb)
+        P, B = s.q_mu.shape
+        S = s.u.shape[1]
         g_theta, g_log_q, g_log_p = _c(g_theta), _c(g_log_q), _c(g_log_p)
-        g_mu = torch.empty_like(q_mu)
-        g_prec = torch.empty_like(q_prec)
-        rc = hip.lib().vihds_theta_bwd(P, B, S, hip.ptr(kind), hip.ptr(q_mu), hip.ptr(q_prec), hip.ptr(p_mu),
-                                       hip.ptr(p_prec), hip.ptr(clip_lo), hip.ptr(clip_hi), hip.ptr(u),
+        g_mu = torch.empty_like(s.q_mu)
+        g_prec = torch.empty_like(s.q_prec)
+        rc = hip.lib().vihds_theta_bwd(P, B, S, hip.ptr(s.kind), hip.ptr(s.q_mu), hip.ptr(s.q_prec), hip.ptr(s.p_mu),
+                                       hip.ptr(s.p_prec), hip.ptr(s.clip_lo), hip.ptr(s.clip_hi), hip.ptr(s.u),
                                        hip.ptr(g_theta), hip.ptr(g_log_q), hip.ptr(g_log_p), hip.ptr(g_mu),
                                        hip.ptr(g_prec), None, hip.current_stream())
         hip.check(rc, "vihds_theta_bwd")
@@ -901,6 +933,9 @@ class ThetaSampleLogProb(torch.autograd.Function):
 class EncoderQTables(torch.autograd.Function):
     """Encoder.evaluate_q (reference encoders.py:383-404) in one forward and two backward launches
     (csrc/vihds_encoder.hip): returns the level-blocked [2P,B] table of means and log-precisions."""
+
+    SAVED = ("delta_obs", "inputs", "dev_1hot", "conv_w", "lin_w", "local_w", "local_b", "gcond_w", "global_free", "pooled",
+             "hidden")
 
     @staticmethod
     def forward(ctx, shape, delta_obs, inputs, dev_1hot, conv_w, conv_b, lin_w, lin_b, local_w, local_b, gcond_w,
@@ -929,17 +964,15 @@ class EncoderQTables(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_all):
-        s = ctx.shape
-        delta_obs, inputs, dev_1hot, conv_w, lin_w, local_w, local_b, gcond_w, global_free, pooled, hidden = \
-            ctx.saved_tensors
+        s, e = ctx.shape, saved_state(ctx, EncoderQTables)
         g_all = _c(g_all)
         dev = g_all.device
         # all parameter gradients are carved out of ONE buffer, in the order Encoder.parameters() lists them (the
         # module's own global_free first, then conv.weight, conv.bias, lin.weight, lin.bias, local heads, gcond heads):
         # a sharded step can then all-reduce the buffer in place instead of flattening and scattering
         # (vihds/parallel.py)
-        shapes = [None if global_free is None else global_free.shape, conv_w.shape, (s.F,), lin_w.shape, (s.H,)] + \
-                 [None if t is None else t.shape for t in (local_w, local_b, gcond_w)]
+        shapes = [None if e.global_free is None else e.global_free.shape, e.conv_w.shape, (s.F,), e.lin_w.shape, (s.H,)] + \
+                 [None if t is None else t.shape for t in (e.local_w, e.local_b, e.gcond_w)]
         sizes = [0 if sh is None else int(torch.Size(sh).numel()) for sh in shapes]
         arena = torch.empty(sum(sizes), device=dev, dtype=torch.float32)
         views, off = [], 0
@@ -949,9 +982,9 @@ class EncoderQTables(torch.autograd.Function):
         g_glob, g_conv_w, g_conv_b, g_lin_w, g_lin_b, g_local_w, g_local_b, g_gcond_w = views
         g_pre = torch.empty((s.B, s.H), device=dev)
         g_conv = torch.empty((s.B, s.F, s.L - s.K + 1), device=dev)
-        rc = hip.lib().vihds_encoder_bwd(ctypes.byref(s), hip.ptr(g_all), hip.ptr(delta_obs), hip.ptr(inputs),
-                                         hip.ptr(dev_1hot), hip.ptr(lin_w), hip.ptr(local_w), hip.ptr(pooled),
-                                         hip.ptr(hidden), hip.ptr(g_pre), hip.ptr(g_conv), hip.ptr(g_conv_w),
+        rc = hip.lib().vihds_encoder_bwd(ctypes.byref(s), hip.ptr(g_all), hip.ptr(e.delta_obs), hip.ptr(e.inputs),
+                                         hip.ptr(e.dev_1hot), hip.ptr(e.lin_w), hip.ptr(e.local_w), hip.ptr(e.pooled),
+                                         hip.ptr(e.hidden), hip.ptr(g_pre), hip.ptr(g_conv), hip.ptr(g_conv_w),
                                          hip.ptr(g_conv_b), hip.ptr(g_lin_w), hip.ptr(g_lin_b), hip.ptr(g_local_w),
                                          hip.ptr(g_local_b), hip.ptr(g_gcond_w), hip.ptr(g_glob),
                                          hip.current_stream())
@@ -991,27 +1024,14 @@ class ThetaSampleLogProbPacked(torch.autograd.Function):
     autograd needs no slice / exp / mul nodes between the encoder heads and the kernel.  `u` is either the [B,S,P]
     tensor of standard normals or a KernelNormal (the kernel then draws them and the tensor is an output)."""
 
+    SAVED = ("q_all", "kind", "p_mu", "p_prec", "clip_lo", "clip_hi", "u", "q_rows")
+
     @staticmethod
     def forward(ctx, q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, n_rows, q_rows):
         _require_cuda(q_all, kind, p_mu, p_prec, clip_lo, clip_hi, q_rows)
         q_all = _c(q_all)
-        P = q_all.shape[0] // 2
-        B = q_all.shape[1]
-        opts = hip.ThetaOpts()
-        opts.q_rows = hip.ptr(q_rows)
-        opts.q_prec_is_log = 1
-        if isinstance(u, KernelNormal):
-            rng, u = u, torch.empty(u.shape, device=q_all.device, dtype=torch.float32)
-            opts.rng, opts.S_total, opts.s_offset = rng.state.data_ptr(), rng.S_total, rng.s_offset
-        else:
-            _require_cuda(u)
-            u = _c(u)
-        S = u.shape[1]
-        if u.shape[0] != B or u.shape[2] != P:
-            raise RuntimeError("u must be [B,S,P]")
-        theta = torch.empty((max(n_rows, P), B, S), device=u.device, dtype=torch.float32)
-        log_q = torch.empty((B, S), device=u.device, dtype=torch.float32)
-        log_p = torch.empty((B, S), device=u.device, dtype=torch.float32)
+        opts, u, _rng_state, P, B, S = _theta_stage(q_all, q_rows, u)
+        theta, log_q, log_p = _theta_outputs(max(n_rows, P), B, S, u.device)
         rc = hip.lib().vihds_theta_fwd(P, B, S, hip.ptr(kind), hip.ptr(q_all), hip.ptr(q_all), hip.ptr(p_mu),
                                        hip.ptr(p_prec), hip.ptr(clip_lo), hip.ptr(clip_hi), hip.ptr(u),
                                        hip.ptr(theta), hip.ptr(log_q), hip.ptr(log_p), ctypes.byref(opts),
@@ -1024,19 +1044,8 @@ class ThetaSampleLogProbPacked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_theta, g_log_q, g_log_p, _g_u):
-        q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, q_rows = ctx.saved_tensors
-        P, B, S = q_all.shape[0] // 2, q_all.shape[1], u.shape[1]
-        g_theta, g_log_q, g_log_p = _c(g_theta), _c(g_log_q), _c(g_log_p)
-        g_all = torch.empty_like(q_all)
-        opts = hip.ThetaOpts()
-        opts.q_rows = hip.ptr(q_rows)
-        opts.q_prec_is_log = 1
-        rc = hip.lib().vihds_theta_bwd(P, B, S, hip.ptr(kind), hip.ptr(q_all), hip.ptr(q_all), hip.ptr(p_mu),
-                                       hip.ptr(p_prec), hip.ptr(clip_lo), hip.ptr(clip_hi), hip.ptr(u),
-                                       hip.ptr(g_theta), hip.ptr(g_log_q), hip.ptr(g_log_p), hip.ptr(g_all),
-                                       hip.ptr(g_all), ctypes.byref(opts), hip.current_stream())
-        hip.check(rc, "vihds_theta_bwd")
-        return g_all, None, None, None, None, None, None, None, None
+        s = saved_state(ctx, ThetaSampleLogProbPacked)
+        return (_theta_bwd_packed(s, g_theta, g_log_q, g_log_p, _packed_opts(s.q_rows)),) + (None,) * 8
 
 
 class IwaeRows(torch.autograd.Function):
@@ -1069,6 +1078,8 @@ class IwaeRows(torch.autograd.Function):
 class _LseFromLogw(torch.autograd.Function):
     """lse[b] given log_w and the (possibly cross-rank combined) lse; backward = softmax weights kernel."""
 
+    SAVED = ("log_w", "lse")
+
     @staticmethod
     def forward(ctx, log_w, lse):
         ctx.save_for_backward(log_w, lse)
@@ -1076,11 +1087,11 @@ class _LseFromLogw(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_lse):
-        log_w, lse = ctx.saved_tensors
-        B, S = log_w.shape
+        s = saved_state(ctx, _LseFromLogw)
+        B, S = s.log_w.shape
         g_lse = _c(g_lse)
-        g_logw = torch.empty_like(log_w)
-        rc = hip.lib().vihds_iwae_bwd(B, S, hip.ptr(log_w), hip.ptr(lse), hip.ptr(g_lse), hip.ptr(g_logw),
+        g_logw = torch.empty_like(s.log_w)
+        rc = hip.lib().vihds_iwae_bwd(B, S, hip.ptr(s.log_w), hip.ptr(s.lse), hip.ptr(g_lse), hip.ptr(g_logw),
                                       hip.current_stream())
         hip.check(rc, "vihds_iwae_bwd")
         return g_logw, None
@@ -1137,6 +1148,8 @@ class IwaeLoss(torch.autograd.Function):
     small batches the forward kernel also writes the gradient for a unit upstream gradient, so a backward seeded with
     unit_gradient() launches nothing here."""
 
+    SAVED = ("log_w", "lse", "ug", "ugn")  # (IwaeLossSharded saves the same four and shares the backward)
+
     @staticmethod
     def forward(ctx, logp, log_p, log_q, n_total, defer=False):
         _require_cuda(logp, log_p, log_q)
@@ -1186,16 +1199,17 @@ class IwaeLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g1, _g2):
         if g_loss is None:
             return None, None, None, None, None
-        log_w, lse, ug, ugn = ctx.saved_tensors
+        s = saved_state(ctx, IwaeLoss)
+        log_w, ug = s.log_w, s.ug
         B, S = log_w.shape
         unit = _UNIT.get(str(log_w.device))
         if ug is not None and unit is not None and g_loss.data_ptr() == unit.data_ptr():
-            return ug.unsqueeze(0).expand(4, -1, -1), ug if ctx.has[0] else None, ugn, None, None
+            return ug.unsqueeze(0).expand(4, -1, -1), ug if ctx.has[0] else None, s.ugn, None, None
         if getattr(ctx, "deferred", None) is not None and _PENDING_IWAE.pop(ug.data_ptr(), None) is not None:
             _run_iwae_job(ctx.deferred)  # general upstream gradient: the forward's kernel after all
         g_logw = torch.empty_like(log_w)
         g_neg = torch.empty_like(log_w) if ctx.has[1] else None
-        rc = hip.lib().vihds_iwae_loss_bwd(B, S, hip.ptr(log_w), hip.ptr(lse), hip.ptr(_c(g_loss)), hip.ptr(g_logw),
+        rc = hip.lib().vihds_iwae_loss_bwd(B, S, hip.ptr(log_w), hip.ptr(s.lse), hip.ptr(_c(g_loss)), hip.ptr(g_logw),
                                            hip.ptr(g_neg), hip.current_stream())
         hip.check(rc, "vihds_iwae_loss_bwd")
         return g_logw.unsqueeze(0).expand(4, -1, -1), g_logw if ctx.has[0] else None, g_neg, None, None
@@ -1232,33 +1246,74 @@ class StepTail(object):
         self.optimizer = optimizer
         self._arena = {}
 
+    def _updated(self):
+        """The tensors this path updates."""
+        return [t for t in self.tensors if t is not None]
+
     def applicable(self):
-        """Single parameter group holding exactly the encoder's tensors, HipAdam on the GPU."""
+        """HipAdam on the GPU with a single parameter group holding exactly the tensors this path updates."""
         from vihds.optim import HipAdam
 
         opt = self.optimizer
         if not isinstance(opt, HipAdam) or len(opt.param_groups) != 1:
             return False
         group = [p for p in opt.param_groups[0]["params"] if p.requires_grad]
-        mine = [t for t in self.tensors if t is not None]
+        mine = self._updated()
         return len(group) == len(mine) and {id(p) for p in group} == {id(t) for t in mine} and all(t.is_cuda for t in mine)
 
-    def launch(self, dec_node, enc_node, job, apply_adam=True):
-        """apply_adam False (row replicas): the second launch only forms the gradient sums into the arena -- the caller
-        all-reduces them and runs the Adam launch on the result."""
-        (q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, q_rows, g_unit, _theta, _cond, _times, _obs,
-         _dev1hot) = dec_node.saved_tensors
-        delta_obs, inputs, dev_1hot, _cw, lin_w, local_w, _lb, _gw, _gf, pooled, hidden = enc_node.saved_tensors
-        s = enc_node.shape
-        P, B, S = q_all.shape[0] // 2, q_all.shape[1], u.shape[1]
-        dev = q_all.device
-        opt = self.optimizer
-        group = opt.param_groups[0]
-        st = opt._group_state(0, group)
+    def _adam_offsets(self):
+        """HipAdam's flat state of the one group and {id(parameter): its offset in the flat m / v}."""
+        st = self.optimizer._group_state(0, self.optimizer.param_groups[0])
         offsets, off = {}, 0
         for prm in st["params"]:
             offsets[id(prm)] = off
             off += prm.numel()
+        return st, offsets
+
+    def _args(self, th, g_theta_unit, job, enc, work, gview, adam, apply_adam):
+        """hip.StepTailArgs with everything both tails set.  th: the theta stage's saved state; g_theta_unit: the theta
+        gradient the rows kernel weights; job: the IWAE job (IwaeLoss.forward's keys); enc: EncoderQTables' saved state;
+        work = (g_all, g_pre, g_conv); gview(t): where parameter t's gradient goes; adam: _adam_offsets().  Returns the
+        struct and [(encoder tensor, its gradient view)]."""
+        a = hip.StepTailArgs()
+        a.P, a.S = th.q_all.shape[0] // 2, th.u.shape[1]
+        a.kind, a.q_all, a.q_rows = hip.ptr(th.kind), hip.ptr(th.q_all), hip.ptr(th.q_rows)
+        a.p_mu, a.p_prec, a.clip_lo, a.clip_hi = hip.ptr(th.p_mu), hip.ptr(th.p_prec), hip.ptr(th.clip_lo), hip.ptr(th.clip_hi)
+        a.u, a.g_theta_unit = hip.ptr(th.u), hip.ptr(g_theta_unit)
+        a.iwae.logp, a.iwae.log_p, a.iwae.log_q = hip.ptr(job["logp"]), hip.ptr(job["log_p"]), hip.ptr(job["log_q"])
+        a.iwae.n_iwae_total = job["n_total"]
+        a.iwae.log_w, a.iwae.lse, a.iwae.loss = hip.ptr(job["log_w"]), hip.ptr(job["rows"][2]), hip.ptr(job["loss"])
+        g_all, g_pre, g_conv = work
+        a.g_all, a.g_pre, a.g_conv = hip.ptr(g_all), hip.ptr(g_pre), hip.ptr(g_conv)
+        a.delta_obs, a.inputs, a.dev1hot = hip.ptr(enc.delta_obs), hip.ptr(enc.inputs), hip.ptr(enc.dev_1hot)
+        a.lin_w, a.local_w = hip.ptr(enc.lin_w), hip.ptr(enc.local_w)
+        a.pooled, a.hidden = hip.ptr(enc.pooled), hip.ptr(enc.hidden)
+        st, offsets = adam
+        grads = []
+        for k, t in enumerate(self.tensors):
+            if t is None:
+                continue
+            if not t.is_contiguous():
+                raise RuntimeError("vihds_step_tail needs contiguous parameters")
+            grads.append((t, gview(t)))
+            a.param[k], a.grad[k], a.mv_offset[k] = t.data_ptr(), grads[-1][1].data_ptr(), offsets[id(t)]
+        group = self.optimizer.param_groups[0]
+        lr = group["lr"]
+        a.m, a.v, a.state = st["m"].data_ptr(), st["v"].data_ptr(), (st["state"].data_ptr() if apply_adam else None)
+        a.lr_dev = hip.ptr(lr) if isinstance(lr, torch.Tensor) else None
+        a.lr = 0.0 if isinstance(lr, torch.Tensor) else float(lr)
+        a.beta1, a.beta2 = group["betas"]
+        a.eps = group["eps"]
+        return a, grads
+
+    def launch(self, dec_node, enc_node, job, apply_adam=True):
+        """apply_adam False (row replicas): the second launch only forms the gradient sums into the arena -- the caller
+        all-reduces them and runs the Adam launch on the result."""
+        dec, enc = saved_state(dec_node, DecoderStepFused), saved_state(enc_node, EncoderQTables)
+        s = enc_node.shape
+        P, B = dec.q_all.shape[0] // 2, dec.q_all.shape[1]
+        dev = dec.q_all.device
+        adam = self._adam_offsets()
         key = (B, str(dev))
         if key not in self._arena or torch.cuda.is_current_stream_capturing():
             # (a capture gets buffers of its own from the graph's pool: they must stay put for every replay)
@@ -1273,40 +1328,17 @@ class StepTail(object):
                 self._arena[key] = bufs
         else:
             bufs = self._arena[key]
-        arena, sizes, g_all, g_pre, g_conv = bufs
-        a = hip.StepTailArgs()
-        a.P, a.S = P, S
-        a.kind, a.q_all, a.q_rows = hip.ptr(kind), hip.ptr(q_all), hip.ptr(q_rows)
-        a.p_mu, a.p_prec, a.clip_lo, a.clip_hi = hip.ptr(p_mu), hip.ptr(p_prec), hip.ptr(clip_lo), hip.ptr(clip_hi)
-        a.u, a.g_theta_unit = hip.ptr(u), hip.ptr(g_unit)
-        a.iwae.logp, a.iwae.log_p, a.iwae.log_q = hip.ptr(job["logp"]), hip.ptr(job["log_p"]), hip.ptr(job["log_q"])
-        a.iwae.n_iwae_total = job["n_total"]
-        a.iwae.log_w, a.iwae.lse, a.iwae.loss = hip.ptr(job["log_w"]), hip.ptr(job["rows"][2]), hip.ptr(job["loss"])
-        a.g_all = hip.ptr(g_all)
-        a.delta_obs, a.inputs, a.dev1hot = hip.ptr(delta_obs), hip.ptr(inputs), hip.ptr(dev_1hot)
-        a.lin_w, a.local_w, a.pooled, a.hidden = hip.ptr(lin_w), hip.ptr(local_w), hip.ptr(pooled), hip.ptr(hidden)
-        a.g_pre, a.g_conv = hip.ptr(g_pre), hip.ptr(g_conv)
-        views, o = [], 0
-        for k, t in enumerate(self.tensors):
-            if t is None:
-                views.append(None)
-                continue
-            if not t.is_contiguous():
-                raise RuntimeError("vihds_step_tail needs contiguous parameters")
-            views.append(arena[o:o + sizes[k]].view(t.shape))
-            a.param[k], a.grad[k], a.mv_offset[k] = t.data_ptr(), views[-1].data_ptr(), offsets[id(t)]
-            o += sizes[k]
-        lr = group["lr"]
-        a.m, a.v, a.state = st["m"].data_ptr(), st["v"].data_ptr(), (st["state"].data_ptr() if apply_adam else None)
-        a.lr_dev = hip.ptr(lr) if isinstance(lr, torch.Tensor) else None
-        a.lr = 0.0 if isinstance(lr, torch.Tensor) else float(lr)
-        a.beta1, a.beta2 = group["betas"]
-        a.eps = group["eps"]
+        arena, sizes = bufs[:2]
+        views, o = {}, 0  # the arena is laid out in self.tensors order
+        for t, n in zip(self.tensors, sizes):
+            if t is not None:
+                views[id(t)] = arena[o:o + n].view(t.shape)
+            o += n
+        a, grads = self._args(dec, dec.g_unit, job, enc, bufs[2:], lambda t: views[id(t)], adam, apply_adam)
         rc = _launch("step_tail", lambda: hip.lib().vihds_step_tail(ctypes.byref(s), ctypes.byref(a), hip.current_stream()))
         hip.check(rc, "vihds_step_tail")
-        for t, v in zip(self.tensors, views):
-            if t is not None:
-                t.grad = v
+        for t, v in grads:
+            t.grad = v
         return job["loss"]
 
 
@@ -1331,23 +1363,19 @@ class GeneralTail(StepTail):
         self._sides = {}
         self.inkernel_iwae = True  # (False: vihds_iwae_loss_fwd + vihds_ode_bwd -- the same numbers, one launch more)
 
-    def applicable(self):
-        """HipAdam, one parameter group = the encoder's tensors + every decoder-side parameter, each of which this path
-        updates (the flat weight buffer's tensors, the offset layer)."""
-        from vihds.optim import HipAdam
-
-        opt = self.optimizer
-        if not isinstance(opt, HipAdam) or len(opt.param_groups) != 1:
-            return False
-        group = [p for p in opt.param_groups[0]["params"] if p.requires_grad]
-        mine = [t for t in self.tensors if t is not None] + list(self.flat_tensors)
+    def _updated(self):
+        """The encoder's tensors + the decoder side's: the flat weight buffer's tensors, the offset layer."""
+        mine = super(GeneralTail, self)._updated() + list(self.flat_tensors)
         if self.offset is not None:
             mine += [self.offset.weight, self.offset.bias]
-        decoder = [p for p in self.ode.parameters() if p.requires_grad]
-        covered = {id(t) for t in mine}
-        if any(id(p) not in covered for p in decoder):
-            return False
-        return (len(group) == len(mine) and {id(p) for p in group} == covered and all(t.is_cuda for t in mine)
+        return mine
+
+    def applicable(self):
+        """As StepTail, and: no decoder-side parameter this path would leave out, no more runs of the flat weight buffer than
+        the update launch takes."""
+        covered = {id(t) for t in self._updated()}
+        return (super(GeneralTail, self).applicable()
+                and all(id(p) in covered for p in self.ode.parameters() if p.requires_grad)
                 and len(self._chunks_static()) <= hip.TAIL_MAX_EXTRA)
 
     def _chunks_static(self):
@@ -1383,79 +1411,87 @@ class GeneralTail(StepTail):
 
     @staticmethod
     def forward_state(theta_node, ode_node):
-        """The step's forward state as GeneralTail.launch takes it, from ThetaSampleLogProbPacked's and OdeSolveObserve's
-        backward nodes -- or from the one node of ThetaOdeFused (pass it twice)."""
+        """The step's forward state as GeneralTail.launch takes it, by name: the saved tensors of ThetaSampleLogProbPacked's
+        and OdeSolveObserve's backward nodes -- or of the one node of ThetaOdeFused (pass it twice) -- plus spec, prob, rom
+        (the row-offset map), logp and rng_advance (the generator state the fused forward left for the tail to step)."""
         if type(ode_node).__name__ == "ThetaOdeFusedBackward":
-            (q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, q_rows, theta, cond, times, obs, traj, dev1hot, weights, _ow,
-             _ob) = ode_node.saved_tensors
-            rng = ode_node.rng_state
+            fwd = saved_state(ode_node, ThetaOdeFused)
+            fwd.rng_advance = ode_node.rng_state
         else:
-            q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, q_rows = theta_node.saved_tensors
-            theta, cond, times, obs, traj, dev1hot, weights = ode_node.saved_tensors
-            rng = None
-        return {"q_all": q_all, "kind": kind, "p_mu": p_mu, "p_prec": p_prec, "clip_lo": clip_lo, "clip_hi": clip_hi, "u": u,
-                "q_rows": q_rows, "theta": theta, "cond": cond, "times": times, "obs": obs, "traj": traj, "dev1hot": dev1hot,
-                "weights": weights, "spec": ode_node.spec, "prob": ode_node.prob, "rom": ode_node.row_offset_map,
-                "logp": ode_node.logp_out, "rng_advance": rng}
+            fwd = SimpleNamespace(rng_advance=None, **vars(saved_state(theta_node, ThetaSampleLogProbPacked)),
+                                  **vars(saved_state(ode_node, OdeSolveObserve)))
+        fwd.spec, fwd.prob, fwd.rom, fwd.logp = ode_node.spec, ode_node.prob, ode_node.row_offset_map, ode_node.logp_out
+        return fwd
 
     def launch(self, fwd, enc_node, log_q, log_p, n_total, apply_adam=True):
         """fwd: forward_state(...) of the step; enc_node: EncoderQTables' backward node.  Returns the loss tensor (-ELBO), or
-        None when the step is outside this path's regime (time-fastest trajectory layout, an offset that is not the
-        one-launch linear form)."""
-        q_all, kind, p_mu, p_prec, clip_lo, clip_hi, u, q_rows = (fwd[k] for k in ("q_all", "kind", "p_mu", "p_prec", "clip_lo",
-                                                                                   "clip_hi", "u", "q_rows"))
-        theta, cond, times, obs, traj, dev1hot, weights = (fwd[k] for k in ("theta", "cond", "times", "obs", "traj", "dev1hot",
-                                                                            "weights"))
-        delta_obs, inputs, dev_1hot_e, _cw, lin_w, local_w, _lb, _gw, _gf, pooled, hidden = enc_node.saved_tensors
-        spec, prob, rom = fwd["spec"], fwd["prob"], fwd["rom"]
-        s = enc_node.shape
-        P, B, S = q_all.shape[0] // 2, q_all.shape[1], u.shape[1]
-        dev = q_all.device
-        R = theta.shape[0]
-        blackbox = spec.model == "dr_blackbox"
-        shift = (0, 0, 0)
-        off_n = off_row0 = 0
-        if rom is not None:
-            # (the sampled rows must not be rows the adjoint writes: their gradient is then exactly the conditioned rows'.
-            # Other rows the adjoint leaves alone stay zero in the persistent buffer below)
-            if (len(rom) != 4 or self.offset is None
-                    or any(r not in spec.unwritten_rows for r in range(rom[0], rom[0] + rom[2]))):
-                return None
-            src, dst, n_off, _ = rom
-            shift, off_n, off_row0 = (src, n_off, dst - src), n_off, dst
-        elif self.offset is not None:
+        None when the step is outside this path's regime (_offset_rows, _decline_reason) -- decided before anything is
+        queued: the caller then runs cost() + autograd + optimizer.step()."""
+        enc, s = saved_state(enc_node, EncoderQTables), enc_node.shape
+        if enc.dev_1hot is None:
+            enc.dev_1hot = fwd.dev1hot
+        off = self._offset_rows(fwd)
+        if off is None:
             return None
-        L = hip.lib()
-        logp = fwd["logp"]
-        key = (B, S, R, str(dev))
-        # ---- everything vihds_step_tail (or the bookkeeping below) would refuse is looked at HERE, before the adjoint is
-        # queued: a refusal is a decline (None: the caller runs cost() + autograd + optimizer.step()), remembered per shape --
-        # never an exception after vihds_ode_bwd_elbo has already run (ADVICE r05)
+        B, S, R = fwd.q_all.shape[1], fwd.u.shape[1], fwd.theta.shape[0]
+        key = (B, S, R, str(fwd.q_all.device))
+        if self._decline_reason(key, fwd, s, off[1]) is not None:
+            return None
+        bf = self._buffers(key, fwd, s, off[1])
+        job = {"logp": _c(fwd.logp.detach()), "log_p": _c(log_p.detach()), "log_q": _c(log_q.detach()),
+               "n_total": int(n_total), "log_w": bf["log_w"], "rows": bf["rows"], "loss": bf["loss"]}
+        aux, g_w = self._adjoint(fwd, bf, job)
+        extras, side = self._weight_grad_extras(fwd, bf, aux, g_w)
+        return self._tail(fwd, enc, s, bf, job, off, extras, side, apply_adam)
+
+    def _offset_rows(self, fwd):
+        """(g_shift triple, off_n, off_row0) of the step's row-offset map; None (decline) for an offset that is not the
+        one-launch linear form of this model's offset layer."""
+        rom = fwd.rom
+        if rom is None:
+            return None if self.offset is not None else ((0, 0, 0), 0, 0)
+        # (the sampled rows must not be rows the adjoint writes: their gradient is then exactly the conditioned rows'.
+        # Other rows the adjoint leaves alone stay zero in the persistent buffer of _buffers)
+        if (len(rom) != 4 or self.offset is None
+                or any(r not in fwd.spec.unwritten_rows for r in range(rom[0], rom[0] + rom[2]))):
+            return None
+        src, dst, n_off, _ = rom
+        return (src, n_off, dst - src), n_off, dst
+
+    def _decline_reason(self, key, fwd, s, off_n):
+        """Everything vihds_step_tail (or the bookkeeping of _tail) would refuse is looked at HERE, before the adjoint is
+        queued: a refusal is a decline, remembered per shape -- never an exception after vihds_ode_bwd_elbo has already run
+        (ADVICE r05).  Returns why, or None."""
         if key in self._declined:
-            return None
+            return self._declined[key]
         why = None
         if off_n > 0 and s.D <= 0:
             why = "an offset layer without device columns in the encoder's shape"
         elif off_n * (s.D + 1) > 256:  # (vihds_api.hip: the offset layer's update is one block of the update launch)
             why = "offset layer of %d x %d weights: more than one block of the update launch" % (off_n, s.D)
-        elif weights is not None:
+        elif fwd.weights is not None:
             fo = 0
             for t in self.flat_tensors:
-                if t.data_ptr() != weights.data_ptr() + 4 * fo or not t.is_contiguous():
+                if t.data_ptr() != fwd.weights.data_ptr() + 4 * fo or not t.is_contiguous():
                     why = "the decoder's parameters are not views of its flat weight buffer"
                     break
                 fo += t.numel()
-            if (why is None and not blackbox and len(self._chunks_static()) != 1
-                    and bool(L.vihds_ode_bwd_reduces_weights(ctypes.byref(prob)))):
+            if (why is None and fwd.spec.model != "dr_blackbox" and len(self._chunks_static()) != 1
+                    and bool(hip.lib().vihds_ode_bwd_reduces_weights(ctypes.byref(fwd.prob)))):
                 why = "the precision network's tensors are not one run of Adam's flat state"
         if why is None and any(t is not None and not t.is_contiguous() for t in self.tensors):
             why = "a non-contiguous encoder parameter"
         if why is not None:
             self._declined[key] = why
-            return None
-        # ---- work buffers: allocated once per shape OUTSIDE any capture (the warm-up steps come first) and reused
-        capturing = torch.cuda.is_current_stream_capturing()
+        return why
+
+    def _buffers(self, key, fwd, s, off_n):
+        """Work buffers: allocated once per shape OUTSIDE any capture (the warm-up steps come first) and reused."""
         if key not in self._bufs:
+            L, prob, weights = hip.lib(), fwd.prob, fwd.weights
+            blackbox = fwd.spec.model == "dr_blackbox"
+            B, S, R, _ = key
+            P, dev = fwd.q_all.shape[0] // 2, fwd.q_all.device
             n_aux = int(L.vihds_ode_bwd_aux_floats(ctypes.byref(prob)))
             lanes_reduce = (weights is not None and not blackbox and bool(L.vihds_ode_bwd_reduces_weights(ctypes.byref(prob))))
             if not blackbox and weights is None:
@@ -1477,17 +1513,21 @@ class GeneralTail(StepTail):
                 "g_w": torch.zeros(max(n_flat, 1), device=dev),
                 "rowsum": torch.empty((max(off_n, 1), B), device=dev),
             }
-            if capturing:
+            if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("GeneralTail: first use of a shape inside a graph capture (the warm-up steps allocate)")
             self._bufs[key] = bufs
-        bf = self._bufs[key]
-        logp_c, log_p_c, log_q_c = _c(logp.detach()), _c(log_p.detach()), _c(log_q.detach())
-        rows = bf["rows"]
-        # ---- the ODE adjoint, its log-likelihood gradient = the importance weights broadcast over the four signals
+        return self._bufs[key]
+
+    def _adjoint(self, fwd, bf, job):
+        """The ODE adjoint, its log-likelihood gradient = the importance weights broadcast over the four signals.  Returns
+        (aux, g_w): the adjoint's dump and the weight-gradient buffer it adds to, where this step has them."""
+        L, prob, rows = hip.lib(), fwd.prob, bf["rows"]
+        theta, cond, times, obs, traj, dev1hot, weights = (fwd.theta, fwd.cond, fwd.times, fwd.obs, fwd.traj, fwd.dev1hot,
+                                                           fwd.weights)
         prob.logp_grad_broadcast = 1
         g_theta = bf["g_theta"]
         aux = bf["aux"] if bf["n_aux"] > 0 else None
-        g_w = bf["g_w"] if (weights is not None and not blackbox and not bf["lanes_reduce"]) else None
+        g_w = bf["g_w"] if (weights is not None and fwd.spec.model != "dr_blackbox" and not bf["lanes_reduce"]) else None
         if g_w is not None:
             g_w.zero_()  # (thread-per-trajectory kernels ADD the bias gradients; the contraction below adds the matrices)
         if self.inkernel_iwae:
@@ -1495,13 +1535,14 @@ class GeneralTail(StepTail):
             # rows kernel recomputes them for the theta adjoint and leaves log_w, lse and -ELBO
             rc = _launch("ode_bwd", lambda: L.vihds_ode_bwd_elbo(
                 ctypes.byref(prob), hip.ptr(theta), hip.ptr(cond), hip.ptr(dev1hot), hip.ptr(times), hip.ptr(obs),
-                hip.ptr(weights), hip.ptr(traj), hip.ptr(logp_c), hip.ptr(log_p_c), hip.ptr(log_q_c), hip.ptr(g_theta),
-                hip.ptr(g_w), hip.ptr(aux), hip.current_stream()))
+                hip.ptr(weights), hip.ptr(traj), hip.ptr(job["logp"]), hip.ptr(job["log_p"]), hip.ptr(job["log_q"]),
+                hip.ptr(g_theta), hip.ptr(g_w), hip.ptr(aux), hip.current_stream()))
             hip.check(rc, "vihds_ode_bwd_elbo")
         else:
             # IWAE launch: loss, log_w, lse and the unit-upstream gradient d loss / d log_w (training.py:135-149)
-            ticket = _iwae_ticket(dev)
-            rc = L.vihds_iwae_loss_fwd(B, S, int(n_total), hip.ptr(logp_c), hip.ptr(log_p_c), hip.ptr(log_q_c),
+            B, S = bf["log_w"].shape
+            ticket = _iwae_ticket(theta.device)
+            rc = L.vihds_iwae_loss_fwd(B, S, job["n_total"], hip.ptr(job["logp"]), hip.ptr(job["log_p"]), hip.ptr(job["log_q"]),
                                        hip.ptr(bf["log_w"]), hip.ptr(rows[0]), hip.ptr(rows[1]), hip.ptr(rows[2]),
                                        hip.ptr(bf["loss"]), hip.ptr(bf["ug"]), None, hip.ptr(ticket), hip.current_stream())
             hip.check(rc, "vihds_iwae_loss_fwd")
@@ -1510,73 +1551,54 @@ class GeneralTail(StepTail):
                 hip.ptr(weights), hip.ptr(traj), None, None, hip.ptr(bf["ug"]), hip.ptr(g_theta), hip.ptr(g_w), hip.ptr(aux),
                 hip.current_stream()))
             hip.check(rc, "vihds_ode_bwd")
-        extras = []  # (flat offset, size, grad_src tensor, src offset, map, nparts, stride)
+        return aux, g_w
+
+    def _weight_grad_extras(self, fwd, bf, aux, g_w):
+        """The decoder networks' weight gradients as the update launch's extra chunks, one per run of _chunks_static:
+        [(first tensor's index in flat_tensors, flat offset, size, grad_src tensor, src offset, map, nparts, stride)], and
+        the side stream their contraction was queued on (None: nothing to wait for)."""
+        if fwd.weights is None:
+            return [], None
         chunks = self._chunks_static()
-        side = None
-        if weights is not None:
-            if bf["lanes_reduce"]:
-                NIN = spec.n_species + 1
-                nwg = 4 * (2 * NIN + 2)
-                nblk = bf["n_aux"] // nwg
-                assert len(chunks) == 1
-                extras = [(0, chunks[0][3], aux, 0, self._lane_map(NIN, dev), nblk, nwg)]
+        dev = fwd.theta.device
+        if bf["lanes_reduce"]:
+            NIN = fwd.spec.n_species + 1
+            nwg = 4 * (2 * NIN + 2)
+            assert len(chunks) == 1
+            return [(chunks[0][0], 0, chunks[0][3], aux, 0, self._lane_map(NIN, dev), bf["n_aux"] // nwg, nwg)], None
+        # the weight-gradient contraction / reductions (dr_blackbox: Gram-tile sums + the tail launch, ~19 us) feed
+        # only the tail's UPDATE launch: they run on a second stream beside the rows launch and join before the update
+        # (in a captured step: a parallel branch of the hipGraph)
+        main = torch.cuda.current_stream()
+        side = self._side_stream(dev)
+        # (a THIRD stream for dr_blackbox's tail launch beside its Gram reduce was measured slower: 0.380 against 0.360
+        # ms/step at config 4, three runs each on one box)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            if fwd.spec.model == "dr_blackbox":
+                gw = blackbox_weight_grads(fwd.spec, fwd.prob, aux, fwd.theta, fwd.cond, fwd.dev1hot)
             else:
-                # the weight-gradient contraction / reductions (dr_blackbox: Gram-tile sums + the tail launch, ~19 us) feed
-                # only the tail's UPDATE launch: they run on a second stream beside the rows launch and join before the update
-                # (in a captured step: a parallel branch of the hipGraph)
-                main = torch.cuda.current_stream()
-                side = self._side_stream(dev)
-                # (a THIRD stream for dr_blackbox's tail launch beside its Gram reduce was measured slower: 0.380 against 0.360
-                # ms/step at config 4, three runs each on one box)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    if blackbox:
-                        gw = blackbox_weight_grads(spec, prob, aux, theta, cond, dev1hot)
-                    else:
-                        gw = decoder_weight_grads(spec, prob, aux, g_w)
-                extras = [(fo, size, gw, fo, None, 1, 0) for (_f, _c2, fo, size) in chunks]
-        # ---- the tail
-        opt = self.optimizer
-        group = opt.param_groups[0]
-        st = opt._group_state(0, group)
-        offsets, off = {}, 0
-        for prm in st["params"]:
-            offsets[id(prm)] = off
-            off += prm.numel()
-        arena = bf["arena"]
+                gw = decoder_weight_grads(fwd.spec, fwd.prob, aux, g_w)
+        return [(first, fo, size, gw, fo, None, 1, 0) for (first, _n, fo, size) in chunks], side
+
+    def _tail(self, fwd, enc, s, bf, job, off, extras, side, apply_adam):
+        """The two vihds_step_tail launches (one call, or rows / join the side stream / update) and the .grad views."""
+        L = hip.lib()
+        adam = self._adam_offsets()
+        offsets, arena = adam[1], bf["arena"]  # the arena is laid out like Adam's flat m / v
 
         def gview(t):
             return arena[offsets[id(t)]:offsets[id(t)] + t.numel()].view(t.shape)
 
-        a = hip.StepTailArgs()
-        a.P, a.S = P, S
-        a.kind, a.q_all, a.q_rows = hip.ptr(kind), hip.ptr(q_all), hip.ptr(q_rows)
-        a.p_mu, a.p_prec, a.clip_lo, a.clip_hi = hip.ptr(p_mu), hip.ptr(p_prec), hip.ptr(clip_lo), hip.ptr(clip_hi)
-        a.u, a.g_theta_unit = hip.ptr(u), hip.ptr(g_theta)
-        a.iwae.logp, a.iwae.log_p, a.iwae.log_q = hip.ptr(logp_c), hip.ptr(log_p_c), hip.ptr(log_q_c)
-        a.iwae.n_iwae_total = int(n_total)
-        a.iwae.log_w, a.iwae.lse, a.iwae.loss = hip.ptr(bf["log_w"]), hip.ptr(rows[2]), hip.ptr(bf["loss"])
-        a.g_all = hip.ptr(bf["g_all"])
-        a.delta_obs, a.inputs, a.dev1hot = hip.ptr(delta_obs), hip.ptr(inputs), hip.ptr(dev_1hot_e if dev_1hot_e is not None else dev1hot)
-        a.lin_w, a.local_w, a.pooled, a.hidden = hip.ptr(lin_w), hip.ptr(local_w), hip.ptr(pooled), hip.ptr(hidden)
-        a.g_pre, a.g_conv = hip.ptr(bf["g_pre"]), hip.ptr(bf["g_conv"])
-        grads = []
-        for k, t in enumerate(self.tensors):
-            if t is None:
-                continue
-            if not t.is_contiguous():
-                raise RuntimeError("vihds_step_tail needs contiguous parameters")
-            view = gview(t)
-            grads.append((t, view))
-            a.param[k], a.grad[k], a.mv_offset[k] = t.data_ptr(), view.data_ptr(), offsets[id(t)]
+        a, grads = self._args(fwd, bf["g_theta"], job, enc, (bf["g_all"], bf["g_pre"], bf["g_conv"]), gview, adam, apply_adam)
         a.g_theta_weighted = 1
-        a.rng_advance = hip.ptr(fwd["rng_advance"])  # (ThetaOdeFused read the generator's step and left the increment to us)
+        a.rng_advance = hip.ptr(fwd.rng_advance)  # (ThetaOdeFused read the generator's step and left the increment to us)
+        shift, off_n, off_row0 = off
         a.g_shift_lo, a.g_shift_n, a.g_shift = shift
-        flat0 = weights.data_ptr() if weights is not None else 0
+        flat0 = fwd.weights.data_ptr() if fwd.weights is not None else 0
         a.n_extra = len(extras)
         keep = []
-        for x, (fo, size, src, so, mp, nparts, stride) in enumerate(extras):
-            first = chunks[x][0]
+        for x, (first, fo, size, src, so, mp, nparts, stride) in enumerate(extras):
             e = a.extra[x]
             e.param = flat0 + 4 * fo
             e.grad = arena.data_ptr() + 4 * offsets[id(self.flat_tensors[first])]
@@ -1600,12 +1622,6 @@ class GeneralTail(StepTail):
             a.off_mv_w, a.off_mv_b = offsets[id(W)], offsets[id(bvec)]
             a.off_rowsum = hip.ptr(bf["rowsum"])
             grads += [(W, gW), (bvec, gb)]
-        lr = group["lr"]
-        a.m, a.v, a.state = st["m"].data_ptr(), st["v"].data_ptr(), (st["state"].data_ptr() if apply_adam else None)
-        a.lr_dev = hip.ptr(lr) if isinstance(lr, torch.Tensor) else None
-        a.lr = 0.0 if isinstance(lr, torch.Tensor) else float(lr)
-        a.beta1, a.beta2 = group["betas"]
-        a.eps = group["eps"]
         if side is None:
             rc = _launch("step_tail", lambda: L.vihds_step_tail(ctypes.byref(s), ctypes.byref(a), hip.current_stream()))
             hip.check(rc, "vihds_step_tail")
@@ -1664,7 +1680,7 @@ class IwaeLossSharded(torch.autograd.Function):
         rc = hip.lib().vihds_iwae_combine(world, B, S, int(n_total), hip.ptr(gathered), hip.ptr(log_w), hip.ptr(lse),
                                           hip.ptr(loss), hip.ptr(ug), hip.ptr(ugn), hip.current_stream())
         hip.check(rc, "vihds_iwae_combine")
-        ctx.save_for_backward(log_w, lse, ug, ugn)
+        ctx.save_for_backward(log_w, lse, ug, ugn)  # (IwaeLoss.SAVED: its backward is this class's too)
         ctx.has = (log_p is not None, log_q is not None)
         ctx.mark_non_differentiable(log_w, lse)
         ctx.set_materialize_grads(False)

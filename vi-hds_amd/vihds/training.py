@@ -31,6 +31,12 @@ def log_prob_observations(model, x_predict, x_obs, precisions, use_laplace=False
     return torch.sum(log_prob_gaussian(torch.unsqueeze(x_obs, 1), x_predict, precisions), 3)
 
 
+def _node_of(tensor, function):
+    """tensor.grad_fn when that is the backward node of the ops Function `function`, else None."""
+    node = getattr(tensor, "grad_fn", None)
+    return node if type(node).__name__ == function.__name__ + "Backward" else None
+
+
 def _delta_obs(obs):
     return (obs[:, :, 1:] - obs[:, :, :-1]).contiguous()
 
@@ -502,8 +508,8 @@ class Training:
             if zero_grad:
                 self.optimizer.zero_grad(set_to_none=True)
             return loss.detach()
-        node = getattr(getattr(getattr(batch_results, "solution", None), "logp_buffer", None), "grad_fn", None)
-        if type(node).__name__ == "ThetaOdeFusedBackward" and node.rng_state is not None:
+        node = _node_of(getattr(getattr(batch_results, "solution", None), "logp_buffer", None), ops.ThetaOdeFused)
+        if node is not None and node.rng_state is not None:
             # (the fused forward left the generator's step to the tail, which did not take this step after all)
             from vihds import hip
 
@@ -559,28 +565,31 @@ class Training:
         apply (the caller then runs autograd's backward and optimizer.step())."""
         if not self.fused_tail or self.shard is not None or len(ops._PENDING_IWAE) != 1:
             return None
-        sol = getattr(batch_results, "solution", None)
-        dec_node = getattr(getattr(sol, "logp_buffer", None), "grad_fn", None)
+        dec_node = _node_of(getattr(getattr(batch_results, "solution", None), "logp_buffer", None), ops.DecoderStepFused)
         packed = getattr(q, "_packed_q", None)
-        enc_node = getattr(packed[1], "grad_fn", None) if packed is not None else None
-        if (type(dec_node).__name__ != "DecoderStepFusedBackward" or type(enc_node).__name__ != "EncoderQTablesBackward"):
+        enc_node = _node_of(packed[1], ops.EncoderQTables) if packed is not None else None
+        if dec_node is None or enc_node is None:
             return None
         if self._tail is None:
             self._tail = ops.StepTail(self.model.encoder, self.optimizer)
             self._tail_ok = self._tail.applicable()
         if not self._tail_ok:
             return None
-        q_all, u = dec_node.saved_tensors[0], dec_node.saved_tensors[6]
-        key = (q_all.shape, u.shape[1])
-        if key not in self._tail_shapes:  # (the library declines shapes past its LDS budget: the five-launch path then)
-            from vihds import hip
-
-            self._tail_shapes[key] = bool(hip.lib().vihds_step_tail_supported(enc_node.shape, q_all.shape[0] // 2, u.shape[1]))
-        if not self._tail_shapes[key]:
+        dec = ops.saved_state(dec_node, ops.DecoderStepFused)
+        if not self._tail_shape_supported(enc_node.shape, dec.q_all, dec.u):  # (the five-launch path then)
             return None
         (job,) = ops._PENDING_IWAE.values()
         ops._PENDING_IWAE.clear()
         return self._tail.launch(dec_node, enc_node, job, apply_adam=self.replica is None)
+
+    def _tail_shape_supported(self, enc_shape, q_all, u):
+        """vihds_step_tail_supported (the library declines shapes past its LDS budget), asked once per shape."""
+        key = (q_all.shape, u.shape[1])
+        if key not in self._tail_shapes:
+            from vihds import hip
+
+            self._tail_shapes[key] = bool(hip.lib().vihds_step_tail_supported(enc_shape, q_all.shape[0] // 2, u.shape[1]))
+        return self._tail_shapes[key]
 
     def _general_tail(self, batch_results, theta, q, p):
         """params.fused_step_tail for the models WITHOUT a fused decoder step (anything but dr_constant: relay / degrader /
@@ -592,15 +601,13 @@ class Training:
             return None
         sol = getattr(batch_results, "solution", None)
         logp = getattr(sol, "logp_buffer", None)
-        ode_node = getattr(logp, "grad_fn", None)
         packed = getattr(theta, "_packed", None)
-        theta_node = getattr(packed, "grad_fn", None)
         pq = getattr(q, "_packed_q", None)
-        enc_node = getattr(pq[1], "grad_fn", None) if pq is not None else None
-        fused_fwd = type(ode_node).__name__ == "ThetaOdeFusedBackward" and type(theta_node).__name__ == "ThetaOdeFusedBackward"
-        if (not (fused_fwd or (type(ode_node).__name__ == "OdeSolveObserveBackward"
-                               and type(theta_node).__name__ == "ThetaSampleLogProbPackedBackward"))
-                or type(enc_node).__name__ != "EncoderQTablesBackward" or not getattr(sol, "has_logp", False)):
+        enc_node = _node_of(pq[1], ops.EncoderQTables) if pq is not None else None
+        ode_node, theta_node = _node_of(logp, ops.ThetaOdeFused), _node_of(packed, ops.ThetaOdeFused)
+        if ode_node is None or theta_node is None:  # (not the fused forward: the theta kernel, then vihds_ode_fwd)
+            ode_node, theta_node = _node_of(logp, ops.OdeSolveObserve), _node_of(packed, ops.ThetaSampleLogProbPacked)
+        if ode_node is None or theta_node is None or enc_node is None or not getattr(sol, "has_logp", False):
             return None
         if self._gtail is None:
             self._gtail = ops.GeneralTail(self.model.encoder, self.optimizer, self.model.decoder.ode_model)
@@ -610,15 +617,7 @@ class Training:
                 return None
         fwd = ops.GeneralTail.forward_state(theta_node, ode_node)
         # the integrator must have read the sampling kernel's own buffer (nothing re-bound into a copy on the way)
-        if fwd["theta"].data_ptr() != packed.data_ptr():
-            return None
-        q_all, u = fwd["q_all"], fwd["u"]
-        key = (q_all.shape, u.shape[1])
-        if key not in self._tail_shapes:
-            from vihds import hip
-
-            self._tail_shapes[key] = bool(hip.lib().vihds_step_tail_supported(enc_node.shape, q_all.shape[0] // 2, u.shape[1]))
-        if not self._tail_shapes[key]:
+        if fwd.theta.data_ptr() != packed.data_ptr() or not self._tail_shape_supported(enc_node.shape, fwd.q_all, fwd.u):
             return None
         return self._gtail.launch(fwd, enc_node, q.log_prob(theta), p.log_prob(theta), logp.shape[2],
                                   apply_adam=self.replica is None)
