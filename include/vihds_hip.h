@@ -4,7 +4,8 @@
  * This is the drop-in boundary.  The reference is pure Python/PyTorch, so the binding
  * a maintainer adds is a ctypes stub; every entry point takes plain pointers and sizes, is
  * asynchronous on the given HIP stream, allocates nothing, keeps no global state besides a thread-local
- * error string, and returns 0 on success or a negative code (VIHDS_E_*).
+ * error string (the library's only thread-local: what an entry point asks of a model's kernels is passed down as an
+ * argument), and returns 0 on success or a negative code (VIHDS_E_*).
  *
  * Memory layout (all fp32, all buffers caller-owned device memory):
  *   n_traj = B*S trajectories, flat index i = b*S + s (IWAE sample fastest).

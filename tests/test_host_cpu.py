@@ -380,7 +380,7 @@ def test_sized_blackbox_libraries_load_on_their_own():
         pytest.skip("no size-set library built")
     for path in libs:
         code = ("import ctypes, os; h = ctypes.CDLL(%r, mode=os.RTLD_NOW | os.RTLD_LOCAL); "
-                "assert h.vihds_bb_variant_v2" % path)
+                "assert h.vihds_bb_variant_v3" % path)
         out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
         assert out.returncode == 0, (path, out.stderr[-400:])
 

@@ -21,7 +21,7 @@ struct GenSel<true> {
   using type = WithPrec<VIHDS_GEN_CORE>;
 };
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
-typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, AdaptiveCtl*);
+typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
 
 #define VIHDS_GEN_CAT2(a, b) a##b
@@ -29,27 +29,18 @@ typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, AdaptiveCtl
 
 #ifdef VIHDS_ONLY_SOLVER
 extern "C" int VIHDS_GEN_CAT(vihds_gen_launch_, VIHDS_ONLY_SOLVER)(bool backward, int solver, const vihds::OdeArgs& a,
-                                                                  hipStream_t st, vihds::AdaptiveCtl* ctl) {
-  using namespace vihds;
-  g_adaptive_ctl = ctl;
-  const int rc = launch_ode<GenM>(backward, solver, a, st);
-  g_adaptive_ctl = nullptr;
-  return rc;
+                                                                  hipStream_t st, const vihds::LaunchMode& mode) {
+  return vihds::launch_ode<vihds::GenM>(backward, solver, a, st, mode);
 }
 #else
 #define VIHDS_GEN_DECL(k) \
-  extern "C" int vihds_gen_launch_##k(bool, int, const vihds::OdeArgs&, hipStream_t, vihds::AdaptiveCtl*);
+  extern "C" int vihds_gen_launch_##k(bool, int, const vihds::OdeArgs&, hipStream_t, const vihds::LaunchMode&);
 VIHDS_GEN_DECL(0) VIHDS_GEN_DECL(1) VIHDS_GEN_DECL(2) VIHDS_GEN_DECL(3) VIHDS_GEN_DECL(4) VIHDS_GEN_DECL(5)
 VIHDS_GEN_DECL(6) VIHDS_GEN_DECL(7) VIHDS_GEN_DECL(8)
 static_assert(VIHDS_SOLVER_COUNT == 9, "one object per solver: extend the table and the Makefile");
 namespace vihds {
-// this library's own thread-locals (it does not link against libvihds_hip.so).  Only g_adaptive_ctl is ever set here (by
-// the launch functions above, from their argument): the wrapper in vihds_api.hip declines the sampling stage, the one-pass
-// summaries and the device-resident adaptive solver for registered models before it calls in.
-thread_local AdaptiveCtl* g_adaptive_ctl = nullptr;
-thread_local AdaptiveDevCtl* g_adaptive_dev = nullptr;
-thread_local const ThetaStageArgs* g_theta_stage = nullptr;
-thread_local const SummArgs* g_summ = nullptr;
+// (the wrapper in vihds_api.hip declines the sampling stage, the one-pass summaries and the device-resident adaptive solver
+// for registered models before it calls in: of the launch modes only the host-driven controller arrives here)
 template <class M>
 static int n_weights_of(int H) {
   if constexpr (M::NEURAL_PREC) return VIHDS_GEN_CORE::NW + M::n_weights(H);
@@ -61,12 +52,12 @@ static const char* const* slot_names_gen() {
   for (int s = 0; s < GenM::NSLOT; ++s) n[s] = GenM::slot_name(s);
   return n;
 }
-static int launch_gen(bool backward, int solver, const OdeArgs& a, hipStream_t st, AdaptiveCtl* ctl) {
+static int launch_gen(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   static const gen_launch_fn table[VIHDS_SOLVER_COUNT] = {vihds_gen_launch_0, vihds_gen_launch_1, vihds_gen_launch_2,
                                                           vihds_gen_launch_3, vihds_gen_launch_4, vihds_gen_launch_5,
                                                           vihds_gen_launch_6, vihds_gen_launch_7, vihds_gen_launch_8};
   if (solver < 0 || solver >= VIHDS_SOLVER_COUNT) return VIHDS_E_BADARG;
-  return table[solver](backward, solver, a, st, ctl);
+  return table[solver](backward, solver, a, st, mode);
 }
 }  // namespace vihds
 

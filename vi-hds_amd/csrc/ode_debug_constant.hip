@@ -3,11 +3,7 @@
 #include "vihds_ode_kernels.hpp"
 
 namespace vihds {
-int launch_debug_constant(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
-  return launch_ode<DebugConstant>(backward, solver, a, st);
+int launch_debug_constant(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+  return launch_ode<DebugConstant>(backward, solver, a, st, mode);
 }
-int n_slots_debug_constant() { return DebugConstant::NSLOT; }
-int n_states_debug_constant() { return DebugConstant::N; }
-int n_cond_debug_constant() { return DebugConstant::NC; }
-const char* slot_name_debug_constant(int s) { return DebugConstant::slot_name(s); }
 }  // namespace vihds

@@ -1,5 +1,4 @@
-// dr_blackbox kernels for the configuration of the reference's specs/dr_blackbox_icml.yaml:17-31
-// (n_latent_species 2, n_hidden_decoder 25, n_hidden_decoder_precisions 20, n_z 5, n_x 5, n_y 2).
+// dr_blackbox kernels for the configuration of the reference's specs/dr_blackbox_icml.yaml (BlackboxIcml, vihds_blackbox.hpp).
 #include "vihds_ode_kernels.hpp"
 #include "vihds_blackbox_split.hpp"
 
@@ -7,10 +6,10 @@
 // with -fno-slp-vectorize (its VALU stream is faster unpacked: 99.0 -> 94.4 us at config 4); everything else -- the adjoint,
 // which is faster with LLVM's packed fp32 (213.8 vs 226.6 us), the other variants, the tables -- as part 2 without the flag.
 namespace vihds {
-using BB = Blackbox<2, 25, 20, 5, 5, 2>;
+using BB = BlackboxIcml;
 #if defined(VIHDS_BB_PART) && VIHDS_BB_PART == 1
-int launch_dr_blackbox_split_fwd(int solver, const OdeArgs& a, hipStream_t st) {
-  return launch_bb_split_dir<BbMfma, false>(solver, a, st, g_theta_stage);
+int launch_dr_blackbox_split_fwd(int solver, const OdeArgs& a, hipStream_t st, const ThetaStageArgs* ts) {
+  return launch_bb_split_dir<BbMfma, false>(solver, a, st, ts);
 }
 }  // namespace vihds
 #ifdef VIHDS_BB_STAMPS
@@ -19,25 +18,21 @@ extern "C" int vihds_debug_bb_fwd_stamps(unsigned long long* buf) {
 }
 #endif
 #else
-int launch_dr_blackbox_split_fwd(int solver, const OdeArgs& a, hipStream_t st);
-int launch_dr_blackbox(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
+int launch_dr_blackbox_split_fwd(int solver, const OdeArgs& a, hipStream_t st, const ThetaStageArgs* ts);
+int launch_dr_blackbox(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   // kernel_variant 1 = VALU, one thread per trajectory (vihds_blackbox.hpp); otherwise the MFMA formulation
+  const bool per_thread = a.kernel_variant == 1 || solver_is_adaptive(solver) || mode.grid;
   // (vihds_theta_ode_fwd: the sampling stage exists in the cooperating-wavefront forward only)
-  if (g_theta_stage && (backward || a.kernel_variant == 1 || solver_is_adaptive(solver) || g_adaptive_ctl))
-    return VIHDS_E_UNSUPPORTED;
-  if (a.kernel_variant == 1 || solver_is_adaptive(solver) || g_adaptive_ctl) return launch_ode<BB>(backward, solver, a, st);
+  if (mode.theta && (backward || per_thread)) return VIHDS_E_UNSUPPORTED;
+  if (per_thread) return launch_ode<BB>(backward, solver, a, st, mode);
   // otherwise the two networks on two wavefronts and the Gram tiles on two more (vihds_blackbox_split.hpp)
   if (!backward) {
-    const int rc = launch_dr_blackbox_split_fwd(solver, a, st);
+    const int rc = launch_dr_blackbox_split_fwd(solver, a, st, mode.theta);
     // (a time grid too long for the cooperating-wavefront forward's staged inputs: the thread-per-trajectory forward)
-    return (rc == VIHDS_E_UNSUPPORTED && !g_theta_stage) ? launch_ode<BB>(false, solver, a, st) : rc;
+    return (rc == VIHDS_E_UNSUPPORTED && !mode.theta) ? launch_ode<BB>(false, solver, a, st, mode) : rc;
   }
   return launch_bb_split_dir<BbMfma, true>(solver, a, st);
 }
-int n_slots_dr_blackbox() { return BB::NSLOT; }
-int n_states_dr_blackbox() { return BB::N; }
-int n_cond_dr_blackbox() { return BB::NC; }
-const char* slot_name_dr_blackbox(int s) { return BB::slot_name(s); }
 int bb_n_weights(int n_const) { return BB::n_weights(n_const); }
 // kernel_variant 0 (anything but 1) with a fixed-grid solver: the matrix-core adjoint with the Gram tiles on chip
 static bool bb_gram_mode(int solver, int kernel_variant) {

@@ -3,11 +3,7 @@
 #include "vihds_ode_kernels.hpp"
 
 namespace vihds {
-int launch_inducer_constant(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
-  return launch_ode<InducerConstant>(backward, solver, a, st);
+int launch_inducer_constant(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+  return launch_ode<InducerConstant>(backward, solver, a, st, mode);
 }
-int n_slots_inducer_constant() { return InducerConstant::NSLOT; }
-int n_states_inducer_constant() { return InducerConstant::N; }
-int n_cond_inducer_constant() { return InducerConstant::NC; }
-const char* slot_name_inducer_constant(int s) { return InducerConstant::slot_name(s); }
 }  // namespace vihds

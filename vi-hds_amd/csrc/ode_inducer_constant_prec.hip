@@ -3,11 +3,7 @@
 #include "vihds_ode_kernels.hpp"
 
 namespace vihds {
-int launch_inducer_constant_prec(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
-  return launch_ode<WithPrec<InducerConstant>>(backward, solver, a, st);
+int launch_inducer_constant_prec(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+  return launch_ode<WithPrec<InducerConstant>>(backward, solver, a, st, mode);
 }
-int n_slots_inducer_constant_prec() { return WithPrec<InducerConstant>::NSLOT; }
-int n_states_inducer_constant_prec() { return WithPrec<InducerConstant>::N; }
-int n_cond_inducer_constant_prec() { return WithPrec<InducerConstant>::NC; }
-const char* slot_name_inducer_constant_prec(int s) { return WithPrec<InducerConstant>::slot_name(s); }
 }  // namespace vihds

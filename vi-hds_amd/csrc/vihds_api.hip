@@ -23,20 +23,11 @@
 #include "vihds_gen_model.hpp"
 
 #include "vihds_relay_lanes.hpp"
-#include "vihds_relay_lanes.hpp"
 
 namespace vihds {
-thread_local AdaptiveCtl* g_adaptive_ctl = nullptr;
-thread_local AdaptiveDevCtl* g_adaptive_dev = nullptr;
-thread_local const ThetaStageArgs* g_theta_stage = nullptr;
-thread_local const SummArgs* g_summ = nullptr;
 // per-model translation units (ode_<model>.hip)
-#define VIHDS_DECL(name)                                                        \
-  int launch_##name(bool backward, int solver, const OdeArgs& a, hipStream_t st); \
-  int n_slots_##name();                                                         \
-  int n_states_##name();                                                        \
-  int n_cond_##name();                                                          \
-  const char* slot_name_##name(int s);
+typedef int (*launch_fn)(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode);
+#define VIHDS_DECL(name) int launch_##name(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 VIHDS_DECL(dr_constant_v1)
 VIHDS_DECL(dr_constant_v2)
 VIHDS_DECL(auto_constant)
@@ -110,36 +101,40 @@ void launch_iw_summaries(int, int, int, int, int, const float*, const float*, co
                          const float*, const int*, float*, float*, float*, float*, hipStream_t);
 
 struct ModelEntry {
-  int (*launch)(bool, int, const OdeArgs&, hipStream_t);
-  int (*n_slots)();
-  int (*n_states)();
-  int (*n_cond)();  // treatments the model reads per data row (cond[b*C + q], q < n_cond)
-  const char* (*slot_name)(int);
+  launch_fn launch;
+  int n_slots, n_states;
+  int n_cond;  // treatments the model reads per data row (cond[b*C + q], q < n_cond)
+  const char* (*slot_name_of)(int);  // a built-in model's names ...
+  const char* const* slot_names;     // ... a registered model's (GenModelRecord)
   bool neural_prec;
   // a registered model whose generated struct has networks of its own (GenModelRecord): weights in front of the precision
   // network's, dump fields in front of its fields
   int n_net_weights = 0, net_fields = 0;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
+  const char* slot_name(int s) const { return slot_names ? slot_names[s] : slot_name_of(s); }
 };
-#define VIHDS_ENTRY(name, np) \
-  { launch_##name, n_slots_##name, n_states_##name, n_cond_##name, slot_name_##name, np }
+// the entry of a built-in model: its sizes and names from the model struct M (vihds_models.hpp), its launcher from its unit
+template <class M>
+static ModelEntry entry_of(launch_fn launch) {
+  return {launch, M::NSLOT, M::N, M::NC, M::slot_name, nullptr, M::NEURAL_PREC};
+}
 static const ModelEntry kModels[VIHDS_MODEL_COUNT] = {
-    VIHDS_ENTRY(dr_constant_v1, false),     // VIHDS_MODEL_DR_CONSTANT
-    VIHDS_ENTRY(dr_constant_v2, false),     // VIHDS_MODEL_DR_CONSTANT_V2
-    VIHDS_ENTRY(auto_constant, false),      // VIHDS_MODEL_AUTO_CONSTANT
-    VIHDS_ENTRY(prpr_constant, false),      // VIHDS_MODEL_PRPR_CONSTANT
-    VIHDS_ENTRY(relay_constant, false),     // VIHDS_MODEL_RELAY_CONSTANT
-    VIHDS_ENTRY(degrader_constant, false),  // VIHDS_MODEL_DEGRADER_CONSTANT
-    VIHDS_ENTRY(dr_constant_prec_v1, true),     // VIHDS_MODEL_DR_CONSTANT_PRECISIONS
-    VIHDS_ENTRY(dr_constant_prec_v2, true),     // VIHDS_MODEL_DR_CONSTANT_PRECISIONS_V2
-    VIHDS_ENTRY(auto_constant_prec, true),      // VIHDS_MODEL_AUTO_CONSTANT_PRECISIONS
-    VIHDS_ENTRY(prpr_constant_prec, true),      // VIHDS_MODEL_PRPR_CONSTANT_PRECISIONS
-    VIHDS_ENTRY(relay_constant_prec, true),     // VIHDS_MODEL_RELAY_CONSTANT_PRECISIONS
-    VIHDS_ENTRY(degrader_constant_prec, true),  // VIHDS_MODEL_DEGRADER_CONSTANT_PRECISIONS
-    VIHDS_ENTRY(dr_blackbox, true),             // VIHDS_MODEL_DR_BLACKBOX
-    VIHDS_ENTRY(inducer_constant, false),       // VIHDS_MODEL_INDUCER_CONSTANT
-    VIHDS_ENTRY(inducer_constant_prec, true),   // VIHDS_MODEL_INDUCER_CONSTANT_PRECISIONS
-    VIHDS_ENTRY(debug_constant, false),         // VIHDS_MODEL_DEBUG_CONSTANT
+    entry_of<DrConstant<1>>(launch_dr_constant_v1),                      // VIHDS_MODEL_DR_CONSTANT
+    entry_of<DrConstant<2>>(launch_dr_constant_v2),                      // VIHDS_MODEL_DR_CONSTANT_V2
+    entry_of<AutoConstant>(launch_auto_constant),                        // VIHDS_MODEL_AUTO_CONSTANT
+    entry_of<PrprConstant>(launch_prpr_constant),                        // VIHDS_MODEL_PRPR_CONSTANT
+    entry_of<RelayConstant>(launch_relay_constant),                      // VIHDS_MODEL_RELAY_CONSTANT
+    entry_of<DegraderConstant>(launch_degrader_constant),                // VIHDS_MODEL_DEGRADER_CONSTANT
+    entry_of<WithPrec<DrConstant<1>>>(launch_dr_constant_prec_v1),       // VIHDS_MODEL_DR_CONSTANT_PRECISIONS
+    entry_of<WithPrec<DrConstant<2>>>(launch_dr_constant_prec_v2),       // VIHDS_MODEL_DR_CONSTANT_PRECISIONS_V2
+    entry_of<WithPrec<AutoConstant>>(launch_auto_constant_prec),         // VIHDS_MODEL_AUTO_CONSTANT_PRECISIONS
+    entry_of<WithPrec<PrprConstant>>(launch_prpr_constant_prec),         // VIHDS_MODEL_PRPR_CONSTANT_PRECISIONS
+    entry_of<WithPrec<RelayConstant>>(launch_relay_constant_prec),       // VIHDS_MODEL_RELAY_CONSTANT_PRECISIONS
+    entry_of<WithPrec<DegraderConstant>>(launch_degrader_constant_prec), // VIHDS_MODEL_DEGRADER_CONSTANT_PRECISIONS
+    entry_of<BlackboxIcml>(launch_dr_blackbox),                          // VIHDS_MODEL_DR_BLACKBOX
+    entry_of<InducerConstant>(launch_inducer_constant),                  // VIHDS_MODEL_INDUCER_CONSTANT
+    entry_of<WithPrec<InducerConstant>>(launch_inducer_constant_prec),   // VIHDS_MODEL_INDUCER_CONSTANT_PRECISIONS
+    entry_of<DebugConstant>(launch_debug_constant),                      // VIHDS_MODEL_DEBUG_CONSTANT
 };
 
 static thread_local char g_err[256] = "";
@@ -159,29 +154,24 @@ static int check_hip(const char* what) {
 static const char* kPrecNames[4] = {"prec_x", "prec_rfp", "prec_yfp", "prec_cfp"};
 
 // ---- registered models (vihds_gen_model.hpp): ids VIHDS_GEN_MODEL_BASE + k -------------------------------------------
-// ModelEntry holds plain function pointers, so every registration slot k has its own set of wrappers over g_gen[k].  The
-// switches below are thread-locals of THIS library, invisible to the side library: the wrapper declines the sampling stage,
-// the one-pass summaries and the device-resident adaptive solver (none of them exists for a registered model) and hands the
-// host-driven adaptive controller over as an argument.
+// ModelEntry::launch is a plain function pointer, so every registration slot k has its own wrapper over g_gen[k]: it declines
+// the sampling stage, the one-pass summaries and the device-resident adaptive solver (none of them exists for a registered
+// model) and passes the rest of the mode -- the host-driven adaptive controller -- on.
 static const GenModelRecord* g_gen[VIHDS_GEN_MODEL_MAX];
 static ModelEntry g_gen_entries[VIHDS_GEN_MODEL_MAX];
 static std::atomic<int> g_gen_count{0};
 template <int K>
 struct GenSlot {
-  static int launch(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
-    if (g_theta_stage || g_summ || g_adaptive_dev) return VIHDS_E_UNSUPPORTED;
-    return g_gen[K]->launch(backward, solver, a, st, g_adaptive_ctl);
+  static int launch(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+    if (mode.theta || mode.summ || mode.dev) return VIHDS_E_UNSUPPORTED;
+    return g_gen[K]->launch(backward, solver, a, st, mode);
   }
-  static int n_slots() { return g_gen[K]->n_slots; }
-  static int n_states() { return g_gen[K]->n_states; }
-  static int n_cond() { return g_gen[K]->n_cond; }
-  static const char* slot_name(int s) { return g_gen[K]->slot_names[s]; }
 };
 template <int... K>
-static ModelEntry gen_entry_of(int k, std::integer_sequence<int, K...>) {
-  static const ModelEntry table[] = {{GenSlot<K>::launch, GenSlot<K>::n_slots, GenSlot<K>::n_states, GenSlot<K>::n_cond,
-                                      GenSlot<K>::slot_name, false}...};
-  return table[k];
+static ModelEntry gen_entry_of(int k, const GenModelRecord* r, std::integer_sequence<int, K...>) {
+  static const launch_fn table[] = {GenSlot<K>::launch...};
+  return {table[k], r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, r->n_net_weights,
+          r->net_fields};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -228,7 +218,7 @@ static const BbVariant* bb_sized(const vihds_ode_problem* p) {
   const BbVariant* v = nullptr;
   if (void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL)) {
     typedef const BbVariant* (*entry_fn)(void);
-    if (entry_fn f = (entry_fn)dlsym(h, "vihds_bb_variant_v2")) v = f();
+    if (entry_fn f = (entry_fn)dlsym(h, "vihds_bb_variant_v3")) v = f();
     if (v && (v->L != p->n_latent_states || v->HS != p->n_hidden_states || v->HP != p->n_hidden_prec || v->NLAT != nlat))
       v = nullptr;
   }
@@ -254,10 +244,10 @@ static long long bb_sized_dump_floats(const BbVariant* v, const vihds_ode_proble
 static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& a, const BbVariant* v = nullptr) {
   if (p->B <= 0 || p->S <= 0 || p->T < 2) return fail(VIHDS_E_BADARG, "B, S must be > 0 and T >= 2");
   if ((long long)p->B * p->S > 0x7fffffffLL) return fail(VIHDS_E_BADARG, "B*S exceeds int range");
-  if (p->C < e->n_cond()) return fail(VIHDS_E_BADARG, "the model reads more treatments per row than C provides");
+  if (p->C < e->n_cond) return fail(VIHDS_E_BADARG, "the model reads more treatments per row than C provides");
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && p->n_const < p->C + p->D)
     return fail(VIHDS_E_BADARG, "dr_blackbox: n_const must cover the C treatments and the D-wide device one-hot");
-  const int ns = v ? v->n_slots : e->n_slots() + (e->neural_prec ? 0 : 4);
+  const int ns = v ? v->n_slots : e->n_slots + (e->neural_prec ? 0 : 4);
   std::memset(&a, 0, sizeof(a));
   a.B = p->B; a.S = p->S; a.T = p->T; a.C = p->C; a.n = p->B * p->S;
   a.solver = p->solver; a.kernel_variant = p->kernel_variant; a.logp_grad_broadcast = p->logp_grad_broadcast; a.D = p->D; a.n_const = p->n_const; a.init_latent = p->init_latent; a.init_prec = p->init_prec;
@@ -266,6 +256,47 @@ static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& 
     if (p->slot_row[q] < 0 || p->slot_row[q] >= p->n_rows) return fail(VIHDS_E_BADARG, "slot_row out of range");
     a.slot_row[q] = p->slot_row[q];
   }
+  return VIHDS_OK;
+}
+static void set_inputs(OdeArgs& a, const float* theta, const float* cond, const float* dev1hot, const float* times,
+                       const float* obs, const float* weights) {
+  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs; a.weights = weights;
+}
+// A model with neural blocks gets its weights; dr_blackbox is built in or has its side library (then *sized) and gets cond and
+// dev1hot; the precision network of any other model has at most 256 hidden units where the entry point's kernels hold that
+// limit (limit_hidden).
+static int check_weights(const vihds_ode_problem* p, const ModelEntry* e, const float* weights, const float* cond,
+                         const float* dev1hot, bool limit_hidden, const BbVariant** sized) {
+  if (!e->has_weights()) return VIHDS_OK;
+  if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
+  if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
+    // (side libraries were built against the same headers: their kernels take every argument the built-in ones do)
+    if (!bb_builtin(p) && !(*sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
+    if (!dev1hot || (p->C > 0 && !cond)) return fail(VIHDS_E_BADARG, "dr_blackbox needs cond and dev1hot");
+  } else if (limit_hidden && p->n_hidden_prec > 256) {
+    return fail(VIHDS_E_UNSUPPORTED, "neural precisions: at most 256 hidden units");
+  }
+  return VIHDS_OK;
+}
+static vihds_theta_opts theta_opts(const vihds_theta_opts* o) {
+  vihds_theta_opts d = {nullptr, 0, nullptr, 0, 0, nullptr, nullptr};
+  return o ? *o : d;
+}
+// The sampling stage of a decoder launch: P, the seven tables, the options and the sample window.  (The conditioner of
+// vihds_theta_ode_logp_grad and the offset layer of vihds_theta_ode_fwd are their callers'.)
+static int theta_stage_args(const vihds_ode_problem* p, int P, const int* kind, const float* q_mu, const float* q_prec,
+                            const float* p_mu, const float* p_prec, const float* clip_lo, const float* clip_hi, float* u,
+                            const vihds_theta_opts* opts, float* theta, float* log_q, float* log_p, ThetaStageArgs& t) {
+  const vihds_theta_opts o = theta_opts(opts);
+  std::memset(&t, 0, sizeof(t));
+  t.P = P; t.kind = kind; t.q_mu = q_mu; t.q_prec = q_prec; t.q_rows = o.q_rows; t.prec_is_log = o.q_prec_is_log;
+  t.p_mu = p_mu; t.p_prec = p_prec; t.clip_lo = clip_lo; t.clip_hi = clip_hi; t.u = u; t.rng = o.rng;
+  t.S_total = p->S; t.s_off = 0;
+  if (o.S_total > 0) {
+    if (o.s_offset < 0 || o.s_offset + p->S > o.S_total) return fail(VIHDS_E_BADARG, "bad sample window");
+    t.S_total = o.S_total; t.s_off = o.s_offset;
+  }
+  t.theta = theta; t.n_rows = p->n_rows; t.log_q = log_q; t.log_p = log_p;
   return VIHDS_OK;
 }
 }  // namespace vihds
@@ -328,10 +359,7 @@ int vihds_model_register(const char* library_path) {
     return fail(VIHDS_E_UNSUPPORTED, "vihds_model_register: too many registered models in this process");
   }
   g_gen[k] = r;
-  g_gen_entries[k] = gen_entry_of(k, std::make_integer_sequence<int, VIHDS_GEN_MODEL_MAX>{});
-  g_gen_entries[k].neural_prec = r->neural_prec != 0;
-  g_gen_entries[k].n_net_weights = r->n_net_weights;
-  g_gen_entries[k].net_fields = r->net_fields;
+  g_gen_entries[k] = gen_entry_of(k, r, std::make_integer_sequence<int, VIHDS_GEN_MODEL_MAX>{});
   g_gen_count.store(k + 1, std::memory_order_release);  // (entry() sees the slot only once it is filled)
   by_path[resolved] = VIHDS_GEN_MODEL_BASE + k;
   return VIHDS_GEN_MODEL_BASE + k;
@@ -339,20 +367,20 @@ int vihds_model_register(const char* library_path) {
 
 int vihds_model_n_states(int model) {
   const ModelEntry* e = entry(model);
-  return e ? e->n_states() : VIHDS_E_UNSUPPORTED;
+  return e ? e->n_states : VIHDS_E_UNSUPPORTED;
 }
 int vihds_model_n_species(int model) {
   const ModelEntry* e = entry(model);
-  return e ? e->n_states() - (e->neural_prec ? 4 : 0) : VIHDS_E_UNSUPPORTED;
+  return e ? e->n_states - (e->neural_prec ? 4 : 0) : VIHDS_E_UNSUPPORTED;
 }
 int vihds_model_n_slots(int model) {
   const ModelEntry* e = entry(model);
-  return e ? e->n_slots() + (e->neural_prec ? 0 : 4) : VIHDS_E_UNSUPPORTED;
+  return e ? e->n_slots + (e->neural_prec ? 0 : 4) : VIHDS_E_UNSUPPORTED;
 }
 const char* vihds_model_slot_name(int model, int slot) {
   const ModelEntry* e = entry(model);
   if (!e || slot < 0) return nullptr;
-  const int ns = e->n_slots();
+  const int ns = e->n_slots;
   if (slot < ns) return e->slot_name(slot);
   if (!e->neural_prec && slot < ns + 4) return kPrecNames[slot - ns];
   return nullptr;
@@ -368,15 +396,10 @@ int vihds_model_n_weights(const vihds_ode_problem* p) {
     const BbVariant* v = bb_sized(p);
     return v ? v->n_weights(p->n_const) : VIHDS_E_UNSUPPORTED;
   }
-  const int n_in = e->n_states() - 4 + 1;
+  const int n_in = e->n_states - 4 + 1;
   const int H = p->n_hidden_prec;
   if (H > 0) return H * n_in + H + 2 * (4 * H + 4);  // hidden layer (reference precisions.py:63-74): Wh, bh, Wp, bp, Wd, bd
   return 2 * (4 * n_in + 4);
-}
-
-static vihds_theta_opts theta_opts(const vihds_theta_opts* o) {
-  vihds_theta_opts d = {nullptr, 0, nullptr, 0, 0, nullptr, nullptr};
-  return o ? *o : d;
 }
 
 int vihds_ode_logp_grad(const vihds_ode_problem* p, const float* theta, const float* cond, const float* dev1hot,
@@ -389,7 +412,7 @@ int vihds_ode_logp_grad(const vihds_ode_problem* p, const float* theta, const fl
   OdeArgs a;
   if (int rc = build_args(p, e, a)) return rc;
   if (p->C < 2) return fail(VIHDS_E_BADARG, "dr_constant needs two treatments");
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs;
+  set_inputs(a, theta, cond, dev1hot, times, obs, nullptr);
   a.logp = logp; a.g_theta = g_theta_unit;
   a.newton_hist = g_newton_hist;
   const int rc = p->model == VIHDS_MODEL_DR_CONSTANT
@@ -420,17 +443,9 @@ int vihds_theta_ode_logp_grad(const vihds_ode_problem* p, int P, const int* kind
   OdeArgs a;
   if (int rc = build_args(p, e, a)) return rc;
   if (p->C < 2) return fail(VIHDS_E_BADARG, "dr_constant needs two treatments");
-  const vihds_theta_opts o = theta_opts(opts);
   ThetaStageArgs t;
-  std::memset(&t, 0, sizeof(t));
-  t.P = P; t.kind = kind; t.q_mu = q_mu; t.q_prec = q_prec; t.q_rows = o.q_rows; t.prec_is_log = o.q_prec_is_log;
-  t.p_mu = p_mu; t.p_prec = p_prec; t.clip_lo = clip_lo; t.clip_hi = clip_hi; t.u = u; t.rng = o.rng;
-  t.S_total = p->S; t.s_off = 0;
-  if (o.S_total > 0) {
-    if (o.s_offset < 0 || o.s_offset + p->S > o.S_total) return fail(VIHDS_E_BADARG, "bad sample window");
-    t.S_total = o.S_total; t.s_off = o.s_offset;
-  }
-  t.theta = theta; t.n_rows = p->n_rows; t.log_q = log_q; t.log_p = log_p;
+  if (int rc = theta_stage_args(p, P, kind, q_mu, q_prec, p_mu, p_prec, clip_lo, clip_hi, u, opts, theta, log_q, log_p, t))
+    return rc;
   if (co && co->E > 0) {
     if (!dev1hot || !co->relevance || !co->is_default || (!co->z && !co->rng) || p->D <= 0)
       return fail(VIHDS_E_BADARG, "conditioner: missing input");
@@ -438,7 +453,7 @@ int vihds_theta_ode_logp_grad(const vihds_ode_problem* p, int P, const int* kind
     t.E = co->E; t.cond_row0 = co->first_row; t.w_mean = co->w_mean; t.w_std = co->w_std; t.z = co->z;
     t.crng = co->rng; t.rel = co->relevance; t.is_default = co->is_default;
   }
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs;
+  set_inputs(a, theta, cond, dev1hot, times, obs, nullptr);
   a.logp = logp; a.g_theta = g_theta_unit;
   a.newton_hist = g_newton_hist;
   const int rc = p->model == VIHDS_MODEL_DR_CONSTANT
@@ -489,7 +504,7 @@ long long vihds_ode_bwd_aux_floats(const vihds_ode_problem* p) {
   // white-box + neural precisions: [8 + NIN][E][n], NIN = 1 + core states (optional: see vihds_ode_bwd)
   const long long stages = ode_stages(p->solver);
   // (a registered model with networks of its own: their fields first -- vihds_gen_model.hpp)
-  const long long prec_fields = e->neural_prec ? 8 + e->n_states() - 4 + 1 + (p->n_hidden_prec > 0 ? 2 * p->n_hidden_prec : 0) : 0;
+  const long long prec_fields = e->neural_prec ? 8 + e->n_states - 4 + 1 + (p->n_hidden_prec > 0 ? 2 * p->n_hidden_prec : 0) : 0;
   return (e->net_fields + prec_fields) * (p->T - 1) * stages * p->B * p->S;
 }
 int vihds_blackbox_dump_fields(void) { return bb_dump_fields(); }
@@ -553,22 +568,14 @@ int vihds_ode_fwd(const vihds_ode_problem* p, const float* theta, const float* c
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (logp && !obs) return fail(VIHDS_E_BADARG, "logp requested without obs");
-  if (e->has_weights()) {
-    if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
-    if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
-      if (!bb_builtin(p) && !(sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
-      if (!dev1hot || (p->C > 0 && !cond)) return fail(VIHDS_E_BADARG, "dr_blackbox needs cond and dev1hot");
-    } else if (p->n_hidden_prec > 256) {
-      return fail(VIHDS_E_UNSUPPORTED, "neural precisions: at most 256 hidden units");
-    }
-  }
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
   OdeArgs a;
   int rc = build_args(p, e, a, sized);
   if (rc) return rc;
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs; a.weights = weights;
+  set_inputs(a, theta, cond, dev1hot, times, obs, weights);
   a.traj = traj; a.xpred = xpred; a.logp = logp;
-  rc = sized ? sized->launch(false, p->solver, a, (hipStream_t)stream, nullptr) : e->launch(false, p->solver, a, (hipStream_t)stream);
+  rc = (sized ? sized->launch : e->launch)(false, p->solver, a, (hipStream_t)stream, LaunchMode{});
   if (rc) return fail(rc, "unknown solver");
   return check_hip("vihds_ode_fwd launch");
 }
@@ -624,12 +631,8 @@ int vihds_ode_fwd_summaries_supported(const vihds_ode_problem* p) {
   if (e->neural_prec && p->n_hidden_prec > 256) return 0;
   // ... and the forward launch of this problem is the thread-per-trajectory kernel (whose integration the second pass
   // repeats bit for bit): asked for, or an evaluation-sized launch
-  static const long long lane_max = [] {
-    const char* ev = std::getenv("VIHDS_LANE_SPLIT_MAX_N");
-    return ev ? std::atoll(ev) : 16384LL;
-  }();
   const long long n = (long long)p->B * p->S;
-  return p->kernel_variant == 1 || (p->kernel_variant == 0 && n > lane_max);
+  return p->kernel_variant == 1 || (p->kernel_variant == 0 && n > lane_split_max_n());
 }
 long long vihds_ode_fwd_summaries_workspace_floats(const vihds_ode_problem* p) {
   if (!p) return VIHDS_E_BADARG;
@@ -650,16 +653,13 @@ int vihds_ode_fwd_summaries(const vihds_ode_problem* p, const float* theta, cons
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (p->model == VIHDS_MODEL_DR_BLACKBOX || solver_is_adaptive(p->solver))
     return VIHDS_E_UNSUPPORTED;  // (dr_blackbox and the adaptive pairs keep vihds_ode_fwd + vihds_iw_summaries_states)
-  if (e->has_weights()) {
-    if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
-    if (p->n_hidden_prec > 256) return fail(VIHDS_E_UNSUPPORTED, "neural precisions: at most 256 hidden units");
-  }
+  const BbVariant* sized = nullptr;  // (stays null: dr_blackbox left above)
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
   OdeArgs a;
   int rc = build_args(p, e, a, nullptr);
   if (rc) return rc;
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = nullptr; a.weights = weights;
-  a.traj = nullptr; a.xpred = nullptr; a.logp = nullptr;
+  set_inputs(a, theta, cond, dev1hot, times, nullptr, weights);  // (no obs and no outputs of the launch itself)
   a.kernel_variant = 1;  // (every model's launcher sends this to launch_ode: the thread-per-trajectory kernels)
   const int ns = summ_species(p, e);
   if (ns < 0) return ns;
@@ -667,9 +667,9 @@ int vihds_ode_fwd_summaries(const vihds_ode_problem* p, const float* theta, cons
   sa.log_w = log_w; sa.lse = lse; sa.partial = workspace;
   sa.nch = ((p->S + 255) / 256) * 4;
   sa.nvp = (ns + 12 + 3) & ~3;
-  g_summ = &sa;
-  rc = e->launch(false, p->solver, a, (hipStream_t)stream);
-  g_summ = nullptr;
+  LaunchMode mode;
+  mode.summ = &sa;
+  rc = e->launch(false, p->solver, a, (hipStream_t)stream, mode);
   if (rc) return rc == VIHDS_E_UNSUPPORTED ? rc : fail(rc, "vihds_ode_fwd_summaries: launch refused");
   const long long items = (long long)p->B * p->T * sa.nvp;
   hipLaunchKernelGGL(vihds::summ_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->B, p->T,
@@ -698,28 +698,18 @@ int vihds_ode_adaptive_grid(const vihds_ode_problem* p, const float* theta, cons
   const BbVariant* sized = nullptr;
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
-  if (e->has_weights()) {
-    if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
-    if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
-      if (!bb_builtin(p) && !(sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
-      if (!dev1hot || (p->C > 0 && !cond)) return fail(VIHDS_E_BADARG, "dr_blackbox needs cond and dev1hot");
-    }
-  }
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, false, &sized)) return rc;
   for (int k = 1; k < p->T; ++k)
     if (!(times_host[k] > times_host[k - 1])) return fail(VIHDS_E_BADARG, "output times must increase");
   OdeArgs a;
   int rc = build_args(p, e, a, sized);
   if (rc) return rc;
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.weights = weights;
+  set_inputs(a, theta, cond, dev1hot, nullptr, nullptr, weights);  // (the times stay on the host: ctl)
   AdaptiveCtl ctl = {times_host, rtol, atol, workspace, grid_host, max_grid, index_host, 0};
-  if (sized) {
-    rc = sized->launch(false, p->solver, a, (hipStream_t)stream, &ctl);
-  } else {
-    g_adaptive_ctl = &ctl;
-    rc = e->launch(false, p->solver, a, (hipStream_t)stream);
-    g_adaptive_ctl = nullptr;
-  }
+  LaunchMode mode;
+  mode.grid = &ctl;
+  rc = (sized ? sized->launch : e->launch)(false, p->solver, a, (hipStream_t)stream, mode);
   if (rc == VIHDS_E_UNSUPPORTED) return fail(rc, "the accepted grid does not fit max_grid points");
   if (rc == VIHDS_E_BADARG) return fail(rc, "step size underflow or non-finite error estimate");
   if (rc) return fail(rc, "adaptive step controller failed");
@@ -741,7 +731,7 @@ long long vihds_ode_adaptive_tape_floats(const vihds_ode_problem* p, int max_ste
   const ModelEntry* e = entry(p->model);
   if (!adaptive_device_model(p, e)) return VIHDS_E_UNSUPPORTED;
   const int n = p->B * p->S, nblk = (n + ADP_BLOCK - 1) / ADP_BLOCK;
-  return (long long)AdaptiveLayout(nblk, max_steps, p->T, e->n_states(), (size_t)n).total;
+  return (long long)AdaptiveLayout(nblk, max_steps, p->T, e->n_states, (size_t)n).total;
 }
 static int adaptive_device_call(int mode, const vihds_ode_problem* p, const float* theta, const float* cond,
                                 const float* dev1hot, const float* times, float rtol, float atol, int max_steps,
@@ -758,12 +748,12 @@ static int adaptive_device_call(int mode, const vihds_ode_problem* p, const floa
   int rc = build_args(p, e, a, nullptr);
   if (rc) return rc;
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times;
-  a.traj = traj; a.g_traj = g_traj; a.g_theta = g_theta; a.weights = weights; a.g_weights = g_weights;
+  set_inputs(a, theta, cond, dev1hot, times, nullptr, weights);
+  a.traj = traj; a.g_traj = g_traj; a.g_theta = g_theta; a.g_weights = g_weights;
   AdaptiveDevCtl ctl = {mode, {workspace, rtol, atol, max_steps}, 0};
-  g_adaptive_dev = &ctl;
-  rc = e->launch(mode == 2, p->solver, a, (hipStream_t)stream);
-  g_adaptive_dev = nullptr;
+  LaunchMode lm;
+  lm.dev = &ctl;
+  rc = e->launch(mode == 2, p->solver, a, (hipStream_t)stream, lm);
   if (rc) return fail(rc, "device-resident adaptive solver: not available for this model / solver");
   return check_hip(mode == 1 ? "vihds_ode_adaptive_fwd launch" : "vihds_ode_adaptive_bwd launch");
 }
@@ -804,19 +794,11 @@ int vihds_ode_bwd(const vihds_ode_problem* p, const float* theta, const float* c
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (!obs) return fail(VIHDS_E_BADARG, "null obs");
-  if (e->has_weights()) {
-    if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
-    if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
-      if (!bb_builtin(p) && !(sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
-      if (!dev1hot || (p->C > 0 && !cond)) return fail(VIHDS_E_BADARG, "dr_blackbox needs cond and dev1hot");
-    } else if (p->n_hidden_prec > 256) {
-      return fail(VIHDS_E_UNSUPPORTED, "neural precisions: at most 256 hidden units");
-    }
-  }
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
   OdeArgs a;
   int rc = build_args(p, e, a, sized);
   if (rc) return rc;
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs; a.weights = weights;
+  set_inputs(a, theta, cond, dev1hot, times, obs, weights);
   a.g_weights = g_weights; a.aux = aux;
   // (white-box + hidden-layer precisions without aux: the state / theta adjoints only -- the three weight matrices have
   // no per-thread accumulators, they come from the dump; g_weights then receives nothing)
@@ -824,7 +806,7 @@ int vihds_ode_bwd(const vihds_ode_problem* p, const float* theta, const float* c
   if (e->n_net_weights > 0 && g_weights && !aux)
     return fail(VIHDS_E_BADARG, "a generated model with networks forms its weight gradient from the aux dump: pass aux (vihds_ode_bwd_aux_floats)");
   a.traj_in = traj; a.g_traj = g_traj; a.g_xpred = g_xpred; a.g_logp = g_logp; a.g_theta = g_theta;
-  rc = sized ? sized->launch(true, p->solver, a, (hipStream_t)stream, nullptr) : e->launch(true, p->solver, a, (hipStream_t)stream);
+  rc = (sized ? sized->launch : e->launch)(true, p->solver, a, (hipStream_t)stream, LaunchMode{});
   if (rc) return fail(rc, "unknown solver");
   return check_hip("vihds_ode_bwd launch");
 }
@@ -857,28 +839,20 @@ int vihds_theta_ode_fwd(const vihds_ode_problem* p, int P, const int* kind, cons
   int rc = build_args(p, e, a, nullptr);
   if (rc) return rc;
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
-  const vihds_theta_opts o = theta_opts(opts);
   ThetaStageArgs t;
-  std::memset(&t, 0, sizeof(t));
-  t.P = P; t.kind = kind; t.q_mu = q_mu; t.q_prec = q_prec; t.q_rows = o.q_rows; t.prec_is_log = o.q_prec_is_log;
-  t.p_mu = p_mu; t.p_prec = p_prec; t.clip_lo = clip_lo; t.clip_hi = clip_hi; t.u = u; t.rng = o.rng;
-  t.S_total = p->S; t.s_off = 0;
-  if (o.S_total > 0) {
-    if (o.s_offset < 0 || o.s_offset + p->S > o.S_total) return fail(VIHDS_E_BADARG, "bad sample window");
-    t.S_total = o.S_total; t.s_off = o.s_offset;
-  }
-  t.theta = theta; t.n_rows = p->n_rows; t.log_q = log_q; t.log_p = log_p;
+  if (int rc = theta_stage_args(p, P, kind, q_mu, q_prec, p_mu, p_prec, clip_lo, clip_hi, u, opts, theta, log_q, log_p, t))
+    return rc;
   if (offset && offset->n > 0) {
     if (!offset->W || !offset->bias || !dev1hot || p->D <= 0 || offset->src_row < 0 || offset->src_row + offset->n > P ||
         offset->dst_row < P || offset->dst_row + offset->n > p->n_rows)
       return fail(VIHDS_E_BADARG, "bad offset layer");
     t.off_n = offset->n; t.off_src = offset->src_row; t.off_dst = offset->dst_row; t.off_w = offset->W; t.off_b = offset->bias;
   }
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs; a.weights = weights;
+  set_inputs(a, theta, cond, dev1hot, times, obs, weights);
   a.traj = traj; a.xpred = xpred; a.logp = logp;
-  g_theta_stage = &t;
-  rc = e->launch(false, p->solver, a, (hipStream_t)stream);
-  g_theta_stage = nullptr;
+  LaunchMode mode;
+  mode.theta = &t;
+  rc = e->launch(false, p->solver, a, (hipStream_t)stream, mode);
   if (rc == VIHDS_E_UNSUPPORTED)
     return fail(rc, "vihds_theta_ode_fwd: kernel variant / solver / shape outside the kernels that carry the sampling stage");
   if (rc) return fail(rc, "unknown solver");
@@ -898,20 +872,11 @@ int vihds_ode_bwd_elbo(const vihds_ode_problem* p, const float* theta, const flo
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (!obs) return fail(VIHDS_E_BADARG, "null obs");
   if (solver_is_adaptive(p->solver)) return fail(VIHDS_E_UNSUPPORTED, "vihds_ode_bwd_elbo: fixed-grid solvers");
-  if (e->has_weights()) {
-    if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
-    if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
-      // (side libraries were built against the same headers: their kernels form the weights too)
-      if (!bb_builtin(p) && !(sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
-      if (!dev1hot || (p->C > 0 && !cond)) return fail(VIHDS_E_BADARG, "dr_blackbox needs cond and dev1hot");
-    } else if (p->n_hidden_prec > 256) {
-      return fail(VIHDS_E_UNSUPPORTED, "neural precisions: at most 256 hidden units");
-    }
-  }
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
   OdeArgs a;
   int rc = build_args(p, e, a, sized);
   if (rc) return rc;
-  a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs; a.weights = weights;
+  set_inputs(a, theta, cond, dev1hot, times, obs, weights);
   a.g_weights = g_weights; a.aux = aux;
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && !aux) return fail(VIHDS_E_BADARG, "dr_blackbox backward needs the aux buffer");
   if (e->n_net_weights > 0 && g_weights && !aux)
@@ -919,7 +884,7 @@ int vihds_ode_bwd_elbo(const vihds_ode_problem* p, const float* theta, const flo
   a.traj_in = traj; a.g_theta = g_theta;
   a.iw_logp = logp; a.iw_log_p = log_p; a.iw_log_q = log_q;
   a.logp_grad_broadcast = 1;
-  rc = sized ? sized->launch(true, p->solver, a, (hipStream_t)stream, nullptr) : e->launch(true, p->solver, a, (hipStream_t)stream);
+  rc = (sized ? sized->launch : e->launch)(true, p->solver, a, (hipStream_t)stream, LaunchMode{});
   if (rc) return fail(rc, "unknown solver");
   return check_hip("vihds_ode_bwd_elbo launch");
 }

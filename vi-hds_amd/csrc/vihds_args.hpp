@@ -75,4 +75,15 @@ struct SummArgs {
   int nch, nvp;
 };
 
+// What an entry point asks of a model's launcher besides the plain forward / adjoint launch (all null).  It is the
+// launchers' last argument; one whose kernels do not have a mode that is set returns VIHDS_E_UNSUPPORTED.
+struct AdaptiveCtl;     // vihds_ode_kernels.hpp
+struct AdaptiveDevCtl;  // vihds_rk_adaptive_device.hpp
+struct LaunchMode {
+  const ThetaStageArgs* theta = nullptr;  // vihds_theta_ode_fwd: the sampling stage in front of the forward launch
+  const SummArgs* summ = nullptr;         // vihds_ode_fwd_summaries: the evaluation's second forward pass
+  AdaptiveCtl* grid = nullptr;            // vihds_ode_adaptive_grid: the host-driven step-size controller
+  AdaptiveDevCtl* dev = nullptr;          // vihds_ode_adaptive_fwd / _bwd: the device-resident controller and its adjoint
+};
+
 }  // namespace vihds

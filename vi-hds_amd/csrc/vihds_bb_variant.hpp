@@ -12,7 +12,6 @@
 #include "vihds_args.hpp"
 
 namespace vihds {
-struct AdaptiveCtl;
 struct BbVariant {
   int L, HS, HP, NLAT;
   int n_states;     // 4 + L + 4
@@ -20,8 +19,8 @@ struct BbVariant {
   int dump_fields;  // fields per RHS evaluation in the adjoint's dump
   int n_tail;       // rows behind the dump: Delta (HS + HP), then the output-bias adjoint sums (2 NX + 8)
   int (*n_weights)(int n_const);
-  // ctl != nullptr: run the step-size controller of an adaptive solver instead of the integration
-  int (*launch)(bool backward, int solver, const OdeArgs& a, hipStream_t st, AdaptiveCtl* ctl);
+  // mode.grid set: run the step-size controller of an adaptive solver instead of the integration
+  int (*launch)(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode);
   // Matrix-core kernels on cooperating wavefronts with the weight gradients on chip (vihds_blackbox_split.hpp): built into
   // the side library for at most 3 latent species, 64 / 32 hidden units and 16 latent inputs -- the reference's
   // default n_hidden_decoder = 50 included.  `launch` then takes them for kernel_variant != 1 on a fixed-grid solver.
@@ -30,4 +29,5 @@ struct BbVariant {
   void (*gram_reduce)(const OdeArgs& a, const float* aux, float* g_weights, hipStream_t st);
 };
 }  // namespace vihds
-extern "C" const vihds::BbVariant* vihds_bb_variant_v2(void);  // the one symbol a side library exports (_v2: the record grew)
+// the one symbol a side library exports (_v2: the record grew; _v3: `launch` takes the LaunchMode)
+extern "C" const vihds::BbVariant* vihds_bb_variant_v3(void);

@@ -312,4 +312,8 @@ struct Blackbox {
 template <int L, int HS, int HP, int NZ, int NXG, int NY>
 struct is_blackbox<Blackbox<L, HS, HP, NZ, NXG, NY>> : std::true_type {};
 
+// the sizes built into libvihds_hip.so: the reference's specs/dr_blackbox_icml.yaml:17-31 (n_latent_species 2,
+// n_hidden_decoder 25, n_hidden_decoder_precisions 20, n_z 5, n_x 5, n_y 2)
+using BlackboxIcml = Blackbox<2, 25, 20, 5, 5, 2>;
+
 }  // namespace vihds

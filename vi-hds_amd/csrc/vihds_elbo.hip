@@ -1146,7 +1146,7 @@ void launch_iw_summaries(int B, int S, int T, int N_total, int n_species, const 
                          mu, sd, states, var);                                                                      \
   } while (0)
   // time points per block of the pipelined kernel: as many as leave >= 2048 blocks (8 per CU), between 2 and 8
-  // (tests/probe/summaries_time.py at B=234, S=1000, T=86, N=8: 1 -> 217 us, 2 -> 159, 4 -> 130, 8 -> 129; one block per time
+  // (profiles/LOG.md, section 4.3, at B=234, S=1000, T=86, N=8: 1 -> 217 us, 2 -> 159, 4 -> 130, 8 -> 129; one block per time
   // point: 162)
   const long long cells = (long long)B * T;
   const int tpb = tpb_override > 0 ? tpb_override : (int)(cells / 2048 < 2 ? 2 : (cells / 2048 > 8 ? 8 : cells / 2048));

@@ -36,7 +36,7 @@ __device__ __forceinline__ float wave_sum_e(float v) {
 // the same sum as a DPP scan (row_shr 1, 2, 4, 8, row_bcast 15, 31; total in lane 63, returned uniformly): six dependent
 // VALU steps instead of six ds_bpermute round trips through the LDS crossbar -- the forward kernel is a chain of such sums
 #ifdef VIHDS_TAIL_STAMPS
-// profiling build (tests/probe/enc_stamps.py): every wavefront writes the 100 MHz wall clock at each phase boundary
+// profiling build (readings: profiles/LOG.md, "r03 step tail" rows): every wavefront writes the 100 MHz wall clock at each phase boundary
 static __device__ unsigned long long* vihds_enc_stamp_buf = nullptr;  // [256 blocks][16 waves][8]
 #define VIHDS_ENC_STOP(PH)                                                                          \
   if (vihds_enc_stamp_buf && (threadIdx.x & 63) == 0 && blockIdx.x < 256)                              \
@@ -217,7 +217,7 @@ encoder_fwd_kernel(vihds_encoder_shape s, const float* __restrict__ delta_obs, c
   VIHDS_ENC_STOP(3)
   // Conv1d (cross-correlation, no padding): out[o][t] = bias[o] + sum_c sum_k w[o][c][k] x[c][t+k]
   // The block's big load (the Linear rows: 144 KB) is issued IN BETWEEN the convolution's input channels: issuing 52 loads
-  // per lane back to back keeps a wavefront waiting on the load queue for ~2.5 us (stamps: tests/probe/enc_stamps.py)
+  // per lane back to back keeps a wavefront waiting on the load queue for ~2.5 us (stamps: profiles/LOG.md, round 3)
   // while the convolution needs LDS and VALU only -- one row's 13 loads, one channel's taps, and so on.
   const bool interleave = fast_lin && s.F * d.Lc <= ENC_T && s.C_in <= LIN_U;
   if (interleave) {

@@ -19,7 +19,6 @@
 #endif
 
 namespace vihds {
-struct AdaptiveCtl;
 struct GenModelRecord {
   // layout guard: a library built against other kernel headers or another OdeArgs is refused at registration
   int abi_version;                 // VIHDS_ABI_VERSION
@@ -32,8 +31,8 @@ struct GenModelRecord {
   int neural_prec;  // 1: WithPrec<> around the generated struct
   const char* const* slot_names;
   int (*n_weights)(int n_hidden_prec);  // floats of the whole weight buffer: the networks', then the neural precisions' (vihds_model_n_weights)
-  // ctl != nullptr: run the step-size controller of an adaptive solver instead of the integration (as BbVariant::launch)
-  int (*launch)(bool backward, int solver, const OdeArgs& a, hipStream_t st, AdaptiveCtl* ctl);
+  // mode.grid set: run the step-size controller of an adaptive solver instead of the integration (as BbVariant::launch)
+  int (*launch)(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode);
   // networks of the generated struct itself (0 / 0 without): their weights lead the buffer, their adjoint dump leads aux --
   // net_fields floats per RHS evaluation and trajectory, field-major [net_fields][E][n], per network the inputs, the hidden
   // pre-activation adjoints, the hidden activations and the output adjoints (vihds_ode_bwd_aux_floats adds them)

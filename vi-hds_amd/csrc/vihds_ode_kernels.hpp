@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -431,7 +432,6 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
 // (26 MB at that size), which summ_finish_kernel adds up in a fixed order.  The integration is ode_fwd_kernel's (same
 // ode_step, same operands): the trajectory summed here is bit for bit the one the weights were computed from.
 // grid: (ceil(S / 256), B), 256 threads: every wavefront's 64 samples belong to one data row.
-extern thread_local const SummArgs* g_summ;
 
 // v[0 .. NVP): per-lane values -> u[p] (p < NVP / 4): in the lanes of row r (lanes 16 r .. 16 r + 15) the wavefront's total of
 // value 4 p + {0, 2, 1, 3}[r]
@@ -685,6 +685,15 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
 }
 
 inline int pick_block(int n) { return n >= (1 << 18) ? 256 : 64; }
+// VIHDS_LANE_SPLIT_MAX_N (default 16 384): up to this many trajectories kernel_variant 0 means dr_constant's lane-split
+// kernels, above it the thread-per-trajectory kernels (whose integration vihds_ode_fwd_summaries repeats)
+inline long long lane_split_max_n() {
+  static const long long v = [] {
+    const char* e = std::getenv("VIHDS_LANE_SPLIT_MAX_N");
+    return e ? std::atoll(e) : 16384LL;
+  }();
+  return v;
+}
 
 template <class M, int SOLVER>
 inline void launch_fwd_s(const OdeArgs& a, hipStream_t st) {
@@ -708,8 +717,8 @@ inline void launch_bwd_s(const OdeArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((ode_bwd_kernel<M, SOLVER>), dim3((a.n + blk - 1) / blk), dim3(blk), 0, st, a);
 }
 
-// Request block of vihds_ode_adaptive_grid: when set (by the API, on the calling thread), the model's launcher runs the
-// step-size controller instead of a forward / adjoint launch and leaves the grid length (or an error code) in `result`.
+// Request block of vihds_ode_adaptive_grid (LaunchMode::grid): the model's launcher runs the step-size controller instead
+// of a forward / adjoint launch and leaves the grid length (or an error code) in `result`.
 struct AdaptiveCtl {
   const float* times_host;
   float rtol, atol;
@@ -719,10 +728,6 @@ struct AdaptiveCtl {
   int* index_host;
   int result;
 };
-extern thread_local AdaptiveCtl* g_adaptive_ctl;
-// vihds_theta_ode_fwd: the sampling stage to run in front of the forward launch (NULL: none); a launch function whose kernels
-// have no such stage returns VIHDS_E_UNSUPPORTED when it is set
-extern thread_local const ThetaStageArgs* g_theta_stage;
 template <class M, int ONLY>
 inline int adaptive_grid(int solver, const OdeArgs& a, const float* times_host, float rtol, float atol, float* workspace,
                          float* grid_host, int max_grid, int* index_host, hipStream_t st);
@@ -744,20 +749,20 @@ constexpr bool solver_built_in(int sv) { return ONLY < 0 || sv == ONLY; }
 namespace vihds {
 
 template <class M, int ONLY = kOnlySolver>
-inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st) {
+inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if constexpr (net_fields<M>::value > 0) {
     // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers)
-    if (g_summ || g_adaptive_dev) return VIHDS_E_UNSUPPORTED;
+    if (mode.summ || mode.dev) return VIHDS_E_UNSUPPORTED;
   } else {
-    if (const SummArgs* sm = g_summ) {  // vihds_ode_fwd_summaries: the evaluation's second forward pass
+    if (const SummArgs* sm = mode.summ) {  // vihds_ode_fwd_summaries: the evaluation's second forward pass
       return backward ? VIHDS_E_BADARG : launch_fwd_summ<M, ONLY>(solver, a, *sm, st);
     }
-    if (AdaptiveDevCtl* dc = g_adaptive_dev) {  // vihds_ode_adaptive_fwd / _bwd: the device-resident controller and its adjoint
+    if (AdaptiveDevCtl* dc = mode.dev) {  // vihds_ode_adaptive_fwd / _bwd: the device-resident controller and its adjoint
       dc->result = adaptive_device<M, ONLY>(solver, a, *dc, st);
       return dc->result;
     }
   }
-  if (AdaptiveCtl* ctl = g_adaptive_ctl) {
+  if (AdaptiveCtl* ctl = mode.grid) {
     ctl->result = adaptive_grid<M, ONLY>(solver, a, ctl->times_host, ctl->rtol, ctl->atol, ctl->workspace, ctl->grid_host,
                                    ctl->max_grid, ctl->index_host, st);
     return ctl->result < 0 ? ctl->result : VIHDS_OK;

@@ -465,13 +465,12 @@ __global__ void __launch_bounds__(ADP_BLOCK) ode_adaptive_bwd_kernel(OdeArgs a, 
   }
 }
 
-// request block for the model launchers (see AdaptiveCtl): mode 1 = forward, 2 = adjoint
+// request block for the model launchers (LaunchMode::dev): mode 1 = forward, 2 = adjoint
 struct AdaptiveDevCtl {
   int mode;
   AdaptiveDev dev;
   int result;
 };
-extern thread_local AdaptiveDevCtl* g_adaptive_dev;
 
 template <class M, int SOLVER>
 inline int adaptive_device_s(const OdeArgs& a, const AdaptiveDevCtl& ctl, hipStream_t st) {
