@@ -1957,7 +1957,9 @@ def test_wide_blackbox_default_hidden_size_against_the_restatement(solver, varia
 def test_offset_rows_against_torch():
     """vihds_offset_rows_fwd / _bwd (dr_blackbox's condition_theta, reference models/dr_blackbox.py:86-96: y_i +=
     Linear(D, n_y)(dev_1hot)_i) against torch: the conditioned rows, the routing of their gradient back to the sampled
-    rows and the layer's weight / bias gradients, through ops.OffsetRows + the "linear" row_offset route's kernel."""
+    rows and the layer's weight / bias gradients, through ops.OffsetRows + the "linear" row_offset route's kernel.
+    All three shapes take the backward's register path (B <= 48, S <= 256); the general loop, both sides of that
+    boundary and accumulate = 0 on it are in test_elbo_side_shapes.py::test_offset_rows_both_backward_paths_against_float64."""
     import ctypes
     from vihds import hip, ops
 
