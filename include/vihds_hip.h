@@ -429,6 +429,8 @@ int vihds_iw_summaries(int B, int S, int T, int N_total, int n_species, const fl
 #define VIHDS_OBS_DEFAULT 0 /* x, x*y1, x*(y2+y4), x*(y3+y5)   (needs n_species >= 6) */
 #define VIHDS_OBS_DIRECT 1  /* x, x*y1, x*y2, x*y3             (needs n_species >= 4) */
 #define VIHDS_OBS_INDUCER 2 /* x, x*y1, x*(y2+y3), x*y4        (needs n_species >= 5) */
+#define VIHDS_OBS_CUSTOM 3  /* the model's own map (a registered model; it may read theta): not formed here -- such a model
+                             * passes its stored x_predict to vihds_iw_summaries; VIHDS_E_BADARG */
 /* Tuning knob of both summaries entry points (process-wide, read at launch): how many consecutive time points one block
  * of the pipelined kernel walks (S a multiple of 4 in 512..1024, <= 16 species).  0 = automatic (as many as leave >= 2048
  * blocks, 2 to 8), > 0 = exactly that many, < 0 = the one-block-per-time-point kernel.  Returns the previous value. */

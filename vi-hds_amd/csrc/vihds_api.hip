@@ -348,7 +348,7 @@ int vihds_model_register(const char* library_path) {
     return VIHDS_E_UNSUPPORTED;
   }
   if (r->n_slots + (r->neural_prec ? 0 : 4) > VIHDS_MAX_SLOTS || r->n_states < 1 || !r->launch || !r->slot_names ||
-      !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT) || r->n_net_weights < 0 ||
+      !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT && r->observe_kind != OBS_CUSTOM) || r->n_net_weights < 0 ||
       r->net_fields < 0 || (r->n_net_weights > 0) != (r->net_fields > 0)) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
@@ -1021,6 +1021,9 @@ int vihds_iw_summaries_states(int B, int S, int T, int N_total, int n_species, i
     return fail(VIHDS_E_BADARG, "bad argument");
   if (theta && !prec_rows) return fail(VIHDS_E_BADARG, "theta given without prec_rows");
   if (!theta && N_total < n_species + 4) return fail(VIHDS_E_BADARG, "neural precisions need N_total >= n_species+4");
+  if (observe_kind == VIHDS_OBS_CUSTOM)
+    return fail(VIHDS_E_BADARG, "observe_kind VIHDS_OBS_CUSTOM: the map is the model's own and may read theta, so it is not "
+                                "formed from the states here; such a model passes its stored x_predict (vihds_iw_summaries)");
   const int need = observe_kind == VIHDS_OBS_DEFAULT ? 6 : (observe_kind == VIHDS_OBS_INDUCER ? 5 : 4);
   if (observe_kind < VIHDS_OBS_DEFAULT || observe_kind > VIHDS_OBS_INDUCER || n_species < need)
     return fail(VIHDS_E_BADARG, "observe_kind / n_species: the observation map reads more species than the model has");

@@ -23,7 +23,12 @@
 
 namespace vihds {
 
-enum ObserveKind { OBS_DEFAULT = 0, OBS_DIRECT = 1, OBS_INDUCER = 2 };
+// How the states become the four observed signals.  The first three are fixed maps of the species by position (observe<OBS>
+// of vihds_ode_kernels.hpp); OBS_CUSTOM is a model with a map of its own, which also sees the effective parameters:
+//   observe(y, p, xp)                  xp[4] = the OD, RFP, YFP, CFP signals
+//   observe_vjp(y, p, xpb, yb, pb)     yb += (d xp/d y)^T xpb ; pb += (d xp/d p)^T xpb
+// (models generated from a Python definition, vihds/modelgen.py)
+enum ObserveKind { OBS_DEFAULT = 0, OBS_DIRECT = 1, OBS_INDUCER = 2, OBS_CUSTOM = 3 };
 
 __device__ __forceinline__ float clampf(float x, float lo, float hi) {
   // torch.clamp semantics incl. NaN pass-through
@@ -939,6 +944,11 @@ struct WithPrec {
   __device__ static void init_vjp(const float* yb, float* thb) {
     Core::init_vjp(yb, thb);
     VIHDS_UNROLL for (int j = 0; j < 4; ++j) thb[Core::NSLOT + j] = yb[NS + j];
+  }
+  // a core with an observation map of its own (OBS_CUSTOM): its species lead y and its parameters lead p
+  __device__ static void observe(const float* y, const float* p, float* xp) { Core::observe(y, p, xp); }
+  __device__ static void observe_vjp(const float* y, const float* p, const float* xpb, float* yb, float* pb) {
+    Core::observe_vjp(y, p, xpb, yb, pb);
   }
   __device__ static void hidden(float t, const float* y, float* h) {
     h[0] = ftanh(t);

@@ -28,8 +28,11 @@ namespace vihds {
 constexpr float LOG2PI_F = 1.8378770664093453f;  // math.log(2*math.pi), vihds/training.py:43
 
 
+// The fixed observation maps.  (A model with a map of its own, M::OBS == OBS_CUSTOM, is never handed to these: the forward
+// and the adjoint kernel call its members, and the kernels that only know the fixed maps are not launched for it.)
 template <int OBS>
 __device__ __forceinline__ void observe(const float* y, float* xp) {
+  static_assert(OBS != OBS_CUSTOM, "a custom observation map is the model's own member observe(y, p, xp)");
   xp[0] = y[0];
   xp[1] = y[0] * y[1];
   if (OBS == OBS_DEFAULT) {  // vihds/ode.py:84-93
@@ -45,6 +48,7 @@ __device__ __forceinline__ void observe(const float* y, float* xp) {
 }
 template <int OBS>
 __device__ __forceinline__ void observe_vjp(const float* y, const float* xpb, float* yb) {
+  static_assert(OBS != OBS_CUSTOM, "a custom observation map is the model's own member observe_vjp(y, p, xpb, yb, pb)");
   if (OBS == OBS_DEFAULT) {
     yb[0] += xpb[0] + xpb[1] * y[1] + xpb[2] * (y[2] + y[4]) + xpb[3] * (y[3] + y[5]);
     yb[1] += xpb[1] * y[0];
@@ -400,7 +404,8 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
       }
     }
     float xp[4];
-    observe<M::OBS>(y, xp);
+    if constexpr (M::OBS == OBS_CUSTOM) M::observe(y, p, xp);
+    else observe<M::OBS>(y, xp);
     if (a.xpred) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.xpred[((size_t)k * 4 + j) * n + i] = xp[j];
     }
@@ -627,7 +632,8 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     tHi = tK;
     // gradient injected at time k: log-likelihood term, x_predict and trajectory upstream grads
     float xp[4], xpb[4];
-    observe<M::OBS>(y, xp);
+    if constexpr (M::OBS == OBS_CUSTOM) M::observe(y, p, xp);
+    else observe<M::OBS>(y, xp);
     VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
       const float e = xp[j] - obk[j];
       const float pr = M::NEURAL_PREC ? y[(M::N - 4) + j] : prec[j];
@@ -637,7 +643,9 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
       else precb[j] += prb;
       if (a.g_xpred) xpb[j] += a.g_xpred[((size_t)k * 4 + j) * n + i];
     }
-    observe_vjp<M::OBS>(y, xpb, lam);
+    // (a custom map also has a parameter adjoint: it joins pb ahead of prepare_vjp and reaches g_theta through the epilogue)
+    if constexpr (M::OBS == OBS_CUSTOM) M::observe_vjp(y, p, xpb, lam, pb);
+    else observe_vjp<M::OBS>(y, xpb, lam);
     if (a.g_traj) {
       VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] += a.g_traj[((size_t)k * N + j) * n + i];
     }
@@ -750,8 +758,9 @@ namespace vihds {
 
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
-  if constexpr (net_fields<M>::value > 0) {
-    // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers)
+  if constexpr (net_fields<M>::value > 0 || M::OBS == OBS_CUSTOM) {
+    // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers;
+    // a model with an observation map of its own: the one-pass summaries know the fixed maps only)
     if (mode.summ || mode.dev) return VIHDS_E_UNSUPPORTED;
   } else {
     if (const SummArgs* sm = mode.summ) {  // vihds_ode_fwd_summaries: the evaluation's second forward pass

@@ -7,7 +7,7 @@ A model is one subclass of GeneratedOdeModel (the plugin surface of the referenc
         species = ["OD", "RFP", ...]                 # ODE states, in order
         parameters = ["r", "K", ..., "init_x"]       # theta names the kernel reads, in slot order
         n_conditions = 0                             # treatments read per data row
-        observe_kind = "default"                     # or "direct" (the kinds the kernels implement)
+        observe_kind = "default"                     # or "direct" (the fixed maps of the kernels), or define observe
 
         def __init__(self, config):
             super().__init__(config)
@@ -19,6 +19,8 @@ A model is one subclass of GeneratedOdeModel (the plugin surface of the referenc
             return [th.init_x, ..., 0.0]
         def rhs(self, t, y, p, c):         # reference OdeFunc.forward: one entry per species
             return [...]
+        def observe(self, y, p, c):        # optional; reference observe(x_sample, theta): the OD, RFP, YFP, CFP signals
+            return [y[0], p.gain * y[0] * y[1] + p.bg, ...]
 
 `c` holds the treatments after clamp(exp(cond) - 1, 1e-12, 1e6) (the c[] contract of csrc/vihds_models.hpp).  The three
 functions use + - * / (unary minus, Python numbers) and the operations of this module: exp, log, pow, sigmoid, tanh and
@@ -34,6 +36,15 @@ The adjoint of each operation is torch autograd's formula, with one exception ke
 pow(a, n) is g * a^n * log(a) everywhere, as csrc pow_vjp computes it for the built-in models.  At a = 0 that is NaN
 (0 * -inf) where autograd masks it to 0 (pow_backward_exponent, base 0 and exponent >= 0); clamp the base away from 0
 (as the reference models do: clamp(K, 1e-12, 1) * c) when the exponent is a parameter.
+
+The observation map.  Without `observe` the four signals are one of the kernels' fixed maps of the species by position
+(observe_kind: "default" [y0, y0 y1, y0 (y2 + y4), y0 (y3 + y5)], "direct" [y0, y0 y1, y0 y2, y0 y3]).  A model that defines
+observe(y, p, c) -> list of 4 has observe_kind "custom": the map is traced into the same DAG (the same operations, no t, no
+network calls), sees the species, the effective parameters of prepare and the treatments, and is emitted with its
+reverse-mode adjoint as two more members of the struct, called once per time point by the forward and the adjoint kernel.
+A parameter may be read by observe only; a treatment it reads is copied by prepare like one rhs reads.  On instances
+`observe` stays OdeModel.observe(x_sample, theta) (the definition is kept as the class's map, as `parameters` is kept as
+parameter_names); torch_observe evaluates it with torch ops.
 
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
@@ -64,6 +75,7 @@ from vihds.ode import OdeModel
 
 MAX_STATES = 32  # ODE states of a generated model (all of them live in registers of one thread)
 OBSERVE_KINDS = {"default": ("OBS_DEFAULT", 6), "direct": ("OBS_DIRECT", 4)}  # kernel enum, species observe() reads
+OBSERVE_CUSTOM = "custom"  # observe_kind of a class that defines observe(y, p, c): the struct's own map, OBS_CUSTOM
 OPERATIONS = ("exp", "log", "pow", "sigmoid", "tanh", "clamp")
 # networks of a generated model (the hidden layer is walked one unit at a time, the inputs and outputs live in registers)
 MAX_NETWORKS, MAX_NET_INPUTS, MAX_NET_HIDDEN, MAX_NET_OUTPUTS = 2, 16, 32, 8
@@ -556,7 +568,7 @@ class _Networks(object):
 
 
 class Trace(object):
-    """The three functions of a model class traced into one Graph."""
+    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe) traced into one Graph."""
 
     def __init__(self, cls):
         inst = cls.__new__(cls)  # (the functions are methods; nothing of nn.Module is touched by them)
@@ -567,8 +579,8 @@ class Trace(object):
 
         def call(k, name, net, inputs):
             if self._phase != "rhs":
-                raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only"
-                                           % (name, self._phase))
+                raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only (not in "
+                                           "prepare, initial_state or observe)" % (name, self._phase))
             if name in self._called:
                 raise ModelDefinitionError("network '%s' is called twice: a network may be called at most once per rhs "
                                            "evaluation (its adjoint dump has one slot per evaluation)" % name)
@@ -600,9 +612,19 @@ class Trace(object):
                 raise ModelDefinitionError("%s: network '%s' is declared but %s" % (
                     cls.__name__, name, "no derivative depends on its outputs" if name in self._called
                     else "never called in rhs"))
-        used = {n.val for n in _topo(self.dy) if n.op == "p"}
-        self.c_in_rhs = [q for q in range(C) if NPU + q in used]
-        # remap the treatments rhs reads to consecutive parameter indices behind the named ones
+        # observe (optional) sees the species, the effective parameters and the treatments, like rhs without t
+        self.obs = None
+        definition = getattr(cls, "_observe_def", None)
+        if definition is not None:
+            self._phase = "observe"
+            xp = definition(inst, [g.leaf("y", j) for j in range(N)], p, _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
+            if not isinstance(xp, (list, tuple)) or len(xp) != 4:
+                raise ModelDefinitionError("%s.observe must return a list of 4 entries (the OD, RFP, YFP and CFP signals)"
+                                           % cls.__name__)
+            self.obs = [g._arg(x) for x in xp]
+        used = {n.val for n in _topo(self.dy + (self.obs or [])) if n.op == "p"}
+        self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs or by observe)
+        # remap the treatments rhs / observe read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
         self.c_slot = {NPU + q: NPU + k for k, q in enumerate(self.c_in_rhs)}
 
@@ -769,7 +791,7 @@ def generate_source(cls, neural=False):
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
-    obs_enum = OBSERVE_KINDS[cls.observe_kind][0]
+    obs_enum = "OBS_CUSTOM" if tr.obs is not None else OBSERVE_KINDS[cls.observe_kind][0]
     sname = "GenModel_" + _ident(cls.model_key)
 
     # prepare: named parameters, then the treatments rhs reads
@@ -802,6 +824,16 @@ def generate_source(cls, neural=False):
     rhs_vjp = [("yb[%d]" % j, "+=", adj1[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj1]
     rhs_vjp += [("pb[%d]" % k, "+=", adj1[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj1]
 
+    # observe / observe_vjp (a model with a map of its own): both run once per time point inside the time loop.  The adjoint
+    # adds into yb and into pb of the named effective parameters (a treatment has no adjoint)
+    obs_decl = []
+    if tr.obs is not None:
+        xpb = [g.leaf("seed", j) for j in range(4)]
+        adj2 = vjp(g, tr.obs, xpb)
+        obs = [("xp[%d]" % j, "=", e) for j, e in enumerate(tr.obs)]
+        obs_vjp = [("yb[%d]" % j, "+=", adj2[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj2]
+        obs_vjp += [("pb[%d]" % k, "+=", adj2[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj2]
+
     def body(assign, fast, seed, p_map=None):
         names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed}
         return "\n".join(_Emitter(fast, names, p_map).emit(assign))
@@ -833,6 +865,15 @@ def generate_source(cls, neural=False):
         vjp_sig = ["  __device__ static void rhs_vjp(float t, const float* y, const float* p, const float*, const float* v, float* yb,",
                    "                                 float* pb) {"]
         net_decl = []
+    if tr.obs is not None:
+        obs_decl = [
+            "  __device__ static void observe(const float* y, const float* p, float* xp) {",
+            body(obs, True, "xpb", tr.c_slot),
+            "  }",
+            "  __device__ static void observe_vjp(const float* y, const float* p, const float* xpb, float* yb, float* pb) {",
+            body(obs_vjp, True, "xpb", tr.c_slot),
+            "  }",
+        ]
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -871,6 +912,7 @@ def generate_source(cls, neural=False):
     ] + vjp_sig + [
         body(rhs_vjp, True, "v", tr.c_slot),
         "  }",
+    ] + obs_decl + [
         "};",
         "}  // namespace vihds",
         "#define VIHDS_GEN_CORE %s" % sname,
@@ -985,6 +1027,7 @@ class GeneratedOdeModel(OdeModel):
     parameter_names = None
     n_conditions = 0
     observe_kind = "default"
+    _observe_def = None  # the class's own observation map observe(self, y, p, c), when it defines one (module docstring)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
 
     def __init_subclass__(cls, **kw):
@@ -995,6 +1038,24 @@ class GeneratedOdeModel(OdeModel):
         if isinstance(declared, (list, tuple)):
             cls.parameter_names = list(declared)
             del cls.parameters
+        # ... and its observation map as `observe(self, y, p, c)`, which would hide OdeModel.observe(x_sample, theta), the
+        # entry point the decoder calls on instances: keep the definition as the class's map, the method as it is
+        definition = cls.__dict__.get("observe")
+        if definition is not None:
+            if not callable(definition):
+                raise ModelDefinitionError("%s.observe must be a function observe(self, y, p, c)" % cls.__name__)
+            cls._observe_def = definition
+            del cls.observe
+        if getattr(cls, "_observe_def", None) is not None:
+            for k in cls.__mro__:
+                kind = k.__dict__.get("observe_kind", "default")
+                if kind != "default" and not (kind == OBSERVE_CUSTOM and k.__dict__.get("_observe_kind_set")):
+                    raise ModelDefinitionError("%s defines observe and observe_kind = %r: a model has either a map of its "
+                                               "own or one of the fixed kinds (leave observe_kind at 'default')"
+                                               % (cls.__name__, kind))
+                if k is GeneratedOdeModel:
+                    break
+            cls.observe_kind, cls._observe_kind_set = OBSERVE_CUSTOM, True
         if cls.__dict__.get("model_key") is None and getattr(cls, "_trace", None) is not None:
             cls._trace = Trace(cls)  # (a subclass that only changes __init__)
             return
@@ -1121,6 +1182,43 @@ class GeneratedOdeModel(OdeModel):
 
         return rhs, x0
 
+    @classmethod
+    def torch_observe(cls, y, theta, cond):
+        """The model's own observation map with torch ops in y's dtype (the float64 reference of the generated observe /
+        observe_vjp, as torch_problem is for rhs): y [B,S,N,T] species (states behind them, e.g. neural precisions, are
+        ignored), theta {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as the data holds it
+        -> x_predict [B,S,4,T]."""
+        if cls._observe_def is None:
+            raise ModelDefinitionError("%s defines no observe(self, y, p, c): its map is the fixed kind '%s'"
+                                       % (cls.__name__, cls.observe_kind))
+        return _observe_torch(cls, cls.__new__(cls), y[:, :, :len(cls.species), :], theta, cond)
+
+    def _observe_map(self, x_sample):
+        """OdeModel.observe on a tensor that is not the last solution: the model's own map (torch_observe) with theta and
+        the treatments of the last solve."""
+        if type(self)._observe_def is None:
+            return super(GeneratedOdeModel, self)._observe_map(x_sample)
+        if self._last_inputs is None:
+            raise RuntimeError("%s.observe: the map reads theta and the treatments of the last solve, and nothing has been "
+                               "solved yet" % type(self).__name__)
+        packed, row_of, cond = self._last_inputs
+        theta = {n: packed[row_of[n]].to(x_sample.device) for n in type(self).parameter_names}
+        return type(self).torch_observe(x_sample, theta, cond.to(x_sample.device))
+
+
+def _observe_torch(cls, inst, y, th, cond):
+    """The class's map with torch ops: y [B,S,N,T], th {parameter name: [B,S]}, cond [B,C] -> [B,S,4,T]."""
+    ref = y[:, :, 0, :]
+    S = ref.shape[1]
+    tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
+    cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+    thn = _Named([(n, th[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
+    over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
+    p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
+    xp = cls._observe_def(inst, list(torch.unbind(y, dim=2)), p, _Conditions([over_time(v) for v in cs]))
+    full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
+    return torch.stack([full(v) for v in xp], dim=2)
+
 
 def _validate(cls):
     name = cls.__name__
@@ -1132,9 +1230,11 @@ def _validate(cls):
         raise ModelDefinitionError("%s.parameters must list the theta names the kernel reads" % name)
     if len(set(cls.parameter_names)) != len(cls.parameter_names):
         raise ModelDefinitionError("%s.parameters has duplicates" % name)
-    if cls.observe_kind not in OBSERVE_KINDS:
-        raise ModelDefinitionError("%s.observe_kind must be one of %s" % (name, sorted(OBSERVE_KINDS)))
-    need = OBSERVE_KINDS[cls.observe_kind][1]
+    custom = getattr(cls, "_observe_def", None) is not None  # (a map of its own reads whatever species it names)
+    if not custom and cls.observe_kind not in OBSERVE_KINDS:
+        raise ModelDefinitionError("%s.observe_kind must be one of %s (or define observe(self, y, p, c))"
+                                   % (name, sorted(OBSERVE_KINDS)))
+    need = 1 if custom else OBSERVE_KINDS[cls.observe_kind][1]
     if len(cls.species) < need:
         raise ModelDefinitionError("%s: observe_kind '%s' reads %d species, the model has %d"
                                    % (name, cls.observe_kind, need, len(cls.species)))

@@ -101,6 +101,7 @@ class OdeModel(nn.Module):
         self._rng_state = None
         self._fused_unsupported = {}
         self._last = None
+        self._last_inputs = None  # (packed theta, row_of, treatments) of the last solve: what a custom observation map reads
 
     # ---- device conditioning (reference ode.py:43-58) ----------------------------------------------
     def device_conditioner(self, param, param_name, dev_1hot, use_bias=False, activation="relu"):
@@ -239,6 +240,7 @@ class OdeModel(nn.Module):
 
         slots = self.kernel_slots()
         packed, row_of = theta.pack(slots)
+        self._last_inputs = (packed, row_of, conditions)
         spec = self._spec(config, row_of, packed.shape[0])
         dev = packed.device
         times = times.to(dev)
@@ -251,8 +253,10 @@ class OdeModel(nn.Module):
         # evaluation passes (no graph to differentiate) leave x_predict to whoever asks for it: Training.cost's summaries
         # form it inside their kernel, plugin code reading DecoderResult gets it from the map below
         # (... and so do training steps whose backward is ops.GeneralTail: nobody reads x_predict there)
+        # (a map of the model's own -- observe_kind "custom", vihds/modelgen.py -- exists in its kernels only and may read
+        # theta: such a model always stores x_predict, and the summaries take it from that buffer)
         lazy = ((not torch.is_grad_enabled() or getattr(self, "_train_without_x_predict", False))
-                and bool(default_get_value(config.params, "lazy_x_predict", True)))
+                and bool(default_get_value(config.params, "lazy_x_predict", True)) and self.observe_kind != "custom")
         traj, xpred, logp = ops.OdeSolveObserve.apply(spec, packed, conditions.to(dev), times, obs.to(dev),
                                                       dev_1hot.to(dev) if dev_1hot is not None else None,
                                                       self.neural_weights(), row_offset, row_offset_map, not lazy)
@@ -434,7 +438,8 @@ class OdeModel(nn.Module):
 
     def observe(self, x_sample, _theta):
         """reference ode.py:84-93.  When x_sample is (a view of) the solution just simulated, the fused
-        kernel's x_predict is returned; otherwise the observation map is evaluated with torch ops."""
+        kernel's x_predict is returned; otherwise the observation map is evaluated with torch ops (a generated model's own
+        map: GeneratedOdeModel.torch_observe with theta and the treatments of the last solve)."""
         last = self._last
         if last is not None and x_sample.data_ptr() == last.sol.data_ptr() and x_sample.shape[3] == last.sol.shape[3]:
             return last.x_predict

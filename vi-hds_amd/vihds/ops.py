@@ -1716,7 +1716,8 @@ def iwae_loss(logp, log_p, log_q, n_iwae_total=None, group=None, defer=False):
     return IwaeLossSharded.apply(logp, log_p, log_q, S, group)
 
 
-OBSERVE_KINDS = {"default": 0, "direct": 1, "inducer": 2}  # VIHDS_OBS_* of include/vihds_hip.h
+# VIHDS_OBS_* of include/vihds_hip.h ("custom": a generated model's own map; iw_summaries takes its stored x_predict)
+OBSERVE_KINDS = {"default": 0, "direct": 1, "inducer": 2, "custom": 3}
 
 
 def ode_logp_only(spec, theta, cond, times, obs, dev1hot, weights):
