@@ -20,6 +20,8 @@ template <>
 struct GenSel<true> {
   using type = WithPrec<VIHDS_GEN_CORE>;
 };
+static_assert(!(VIHDS_GEN_NEURAL != 0 && own_prec<VIHDS_GEN_CORE>::value),
+              "a model with a precision map of its own does not take NeuralPrecisions");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
@@ -63,9 +65,9 @@ static int launch_gen(bool backward, int solver, const OdeArgs& a, hipStream_t s
 
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
   using namespace vihds;
-  static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, GenM::N, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
+  static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, traj_rows<GenM>::value, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
                                    slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
-                                   net_fields<VIHDS_GEN_CORE>::value};
+                                   net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0};
   return &r;
 }
 #endif

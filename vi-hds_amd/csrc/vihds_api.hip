@@ -110,7 +110,12 @@ struct ModelEntry {
   // a registered model whose generated struct has networks of its own (GenModelRecord): weights in front of the precision
   // network's, dump fields in front of its fields
   int n_net_weights = 0, net_fields = 0;
+  // a registered model with a precision map of its own (GenModelRecord::own_prec): four precision rows behind the species in
+  // the trajectory like a neural-precision model, but no precision slots and no weights of its own
+  bool own_prec = false;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
+  bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
+  int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
   const char* slot_name(int s) const { return slot_names ? slot_names[s] : slot_name_of(s); }
 };
 // the entry of a built-in model: its sizes and names from the model struct M (vihds_models.hpp), its launcher from its unit
@@ -171,7 +176,7 @@ template <int... K>
 static ModelEntry gen_entry_of(int k, const GenModelRecord* r, std::integer_sequence<int, K...>) {
   static const launch_fn table[] = {GenSlot<K>::launch...};
   return {table[k], r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, r->n_net_weights,
-          r->net_fields};
+          r->net_fields, r->own_prec != 0};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -247,7 +252,7 @@ static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& 
   if (p->C < e->n_cond) return fail(VIHDS_E_BADARG, "the model reads more treatments per row than C provides");
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && p->n_const < p->C + p->D)
     return fail(VIHDS_E_BADARG, "dr_blackbox: n_const must cover the C treatments and the D-wide device one-hot");
-  const int ns = v ? v->n_slots : e->n_slots + (e->neural_prec ? 0 : 4);
+  const int ns = v ? v->n_slots : e->n_slots + e->n_prec_slots();
   std::memset(&a, 0, sizeof(a));
   a.B = p->B; a.S = p->S; a.T = p->T; a.C = p->C; a.n = p->B * p->S;
   a.solver = p->solver; a.kernel_variant = p->kernel_variant; a.logp_grad_broadcast = p->logp_grad_broadcast; a.D = p->D; a.n_const = p->n_const; a.init_latent = p->init_latent; a.init_prec = p->init_prec;
@@ -347,7 +352,8 @@ int vihds_model_register(const char* library_path) {
     dlclose(h);
     return VIHDS_E_UNSUPPORTED;
   }
-  if (r->n_slots + (r->neural_prec ? 0 : 4) > VIHDS_MAX_SLOTS || r->n_states < 1 || !r->launch || !r->slot_names ||
+  if (r->n_slots + ((r->neural_prec || r->own_prec) ? 0 : 4) > VIHDS_MAX_SLOTS || r->n_states < (r->own_prec ? 5 : 1) ||
+      (r->neural_prec && r->own_prec) || !r->launch || !r->slot_names ||
       !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT && r->observe_kind != OBS_CUSTOM) || r->n_net_weights < 0 ||
       r->net_fields < 0 || (r->n_net_weights > 0) != (r->net_fields > 0)) {
     dlclose(h);
@@ -371,18 +377,18 @@ int vihds_model_n_states(int model) {
 }
 int vihds_model_n_species(int model) {
   const ModelEntry* e = entry(model);
-  return e ? e->n_states - (e->neural_prec ? 4 : 0) : VIHDS_E_UNSUPPORTED;
+  return e ? e->n_states - (e->prec_rows() ? 4 : 0) : VIHDS_E_UNSUPPORTED;
 }
 int vihds_model_n_slots(int model) {
   const ModelEntry* e = entry(model);
-  return e ? e->n_slots + (e->neural_prec ? 0 : 4) : VIHDS_E_UNSUPPORTED;
+  return e ? e->n_slots + e->n_prec_slots() : VIHDS_E_UNSUPPORTED;
 }
 const char* vihds_model_slot_name(int model, int slot) {
   const ModelEntry* e = entry(model);
   if (!e || slot < 0) return nullptr;
   const int ns = e->n_slots;
   if (slot < ns) return e->slot_name(slot);
-  if (!e->neural_prec && slot < ns + 4) return kPrecNames[slot - ns];
+  if (slot < ns + e->n_prec_slots()) return kPrecNames[slot - ns];
   return nullptr;
 }
 int vihds_model_n_weights(const vihds_ode_problem* p) {
@@ -503,7 +509,8 @@ long long vihds_ode_bwd_aux_floats(const vihds_ode_problem* p) {
   if (vihds_ode_bwd_reduces_weights(p)) return relay_lanes_aux_floats(p->B * p->S, lane_model_species(p->model));  // one partial row per block
   // white-box + neural precisions: [8 + NIN][E][n], NIN = 1 + core states (optional: see vihds_ode_bwd)
   const long long stages = ode_stages(p->solver);
-  // (a registered model with networks of its own: their fields first -- vihds_gen_model.hpp)
+  // (a registered model with networks of its own: their fields first -- vihds_gen_model.hpp; one with a precision map of its
+  // own has no precision network: the networks' fields alone)
   const long long prec_fields = e->neural_prec ? 8 + e->n_states - 4 + 1 + (p->n_hidden_prec > 0 ? 2 * p->n_hidden_prec : 0) : 0;
   return (e->net_fields + prec_fields) * (p->T - 1) * stages * p->B * p->S;
 }
@@ -622,7 +629,7 @@ __global__ void __launch_bounds__(256) summ_finish_kernel(int B, int T, int nch,
 }  // namespace vihds
 static int summ_species(const vihds_ode_problem* p, const ModelEntry* e) {
   const int n_states = vihds_problem_n_states(p);
-  return n_states < 0 ? n_states : (e->neural_prec ? n_states - 4 : n_states);
+  return n_states < 0 ? n_states : (e->prec_rows() ? n_states - 4 : n_states);
 }
 int vihds_ode_fwd_summaries_supported(const vihds_ode_problem* p) {
   if (!p) return 0;

@@ -24,7 +24,8 @@ struct GenModelRecord {
   int abi_version;                 // VIHDS_ABI_VERSION
   int odeargs_size;                // sizeof(OdeArgs)
   unsigned long long header_hash;  // VIHDS_HDR_HASH
-  int n_states;     // N (incl. the 4 precision states of a neural-precision model)
+  int n_states;     // rows per time point of the trajectory: N (incl. the 4 precision states of a neural-precision model), or
+                    // species + 4 for a model with a precision map of its own (own_prec: four algebraic rows behind the species)
   int n_slots;      // kernel theta slots (a neural-precision model's init_prec_* included, constant precisions not)
   int n_cond;       // treatments read per data row
   int observe_kind; // ObserveKind
@@ -38,6 +39,9 @@ struct GenModelRecord {
   // pre-activation adjoints, the hidden activations and the output adjoints (vihds_ode_bwd_aux_floats adds them)
   int n_net_weights;
   int net_fields;
+  // 1: the generated struct has a precision map of its own (precision / precision_vjp, vihds_models.hpp own_prec<>): no
+  // prec_* / init_prec_* slot rows and no weights of its own; never together with neural_prec
+  int own_prec;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

@@ -899,6 +899,24 @@ struct net_fields<M, std::void_t<decltype(M::NET_FIELDS)>> {
   static constexpr int value = M::NET_FIELDS;
 };
 
+// A core generated with a precision map of its own (vihds/modelgen.py) declares OWN_PREC = true and two members that run once
+// per time point, like a custom observation map:
+//   precision(y, xp, p, pr)                        pr[4] = the precisions of the OD, RFP, YFP, CFP signals
+//   precision_vjp(y, xp, p, prb, yb, xpb, pb)      yb += (d pr/d y)^T prb ; xpb += (d pr/d xp)^T prb ; pb += (d pr/d p)^T prb
+// Such a model has no prec_* / init_prec_* slot rows: its noise parameters are ordinary slots.  The precisions are algebraic,
+// not ODE states: M::N stays the species count (ode_step, the step-size controller and every register array of the
+// integration see the species only) and the kernels store the four values as rows N .. N + 3 of each time point of the
+// trajectory (traj_rows<M>), the layout a *_precisions model has.  False for every other model.
+template <class M, class = void>
+struct own_prec : std::false_type {};
+template <class M>
+struct own_prec<M, std::void_t<decltype(M::OWN_PREC)>> : std::bool_constant<M::OWN_PREC> {};
+// rows per time point of the trajectory buffer (traj, traj_in, g_traj)
+template <class M>
+struct traj_rows {
+  static constexpr int value = M::N + (own_prec<M>::value ? 4 : 0);
+};
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};

@@ -307,8 +307,10 @@ __device__ __forceinline__ void ode_step_vjp(float t0, float t1, float h0, const
 template <class M>
 __device__ __forceinline__ void load_theta(const OdeArgs& a, int i, int b, float* th, float* prec, float* c) {
   VIHDS_UNROLL for (int q = 0; q < M::NSLOT; ++q) th[q] = a.theta[(size_t)a.slot_row[q] * a.n + i];
-  if (!M::NEURAL_PREC) {  // constant precisions: four more theta rows (reference precisions.py:31-35)
-    VIHDS_UNROLL for (int j = 0; j < 4; ++j) prec[j] = a.theta[(size_t)a.slot_row[M::NSLOT + j] * a.n + i];
+  if constexpr (!own_prec<M>::value) {  // (a precision map of the model's own has no precision slot rows: prec stays unset)
+    if (!M::NEURAL_PREC) {  // constant precisions: four more theta rows (reference precisions.py:31-35)
+      VIHDS_UNROLL for (int j = 0; j < 4; ++j) prec[j] = a.theta[(size_t)a.slot_row[M::NSLOT + j] * a.n + i];
+    }
   }
   VIHDS_UNROLL for (int q = 0; q < M::NC; ++q) c[q] = clampf(expf(a.cond[b * a.C + q]) - 1.f, 1e-12f, 1e6f);
 }
@@ -339,6 +341,8 @@ __device__ __forceinline__ const float* stage_weights(const OdeArgs& a, float* l
 template <class M, int SOLVER, bool LDS_IN>
 __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   constexpr int N = M::N;
+  constexpr int NT = traj_rows<M>::value;  // rows per time point of traj: N, + 4 precision rows of a model with its own map
+  constexpr bool OWN_PREC = own_prec<M>::value;
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations
   const float* wts = stage_weights<M>(a, wlds);
@@ -369,7 +373,8 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
 
   float lc[4], lp[4];
   VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
-    lc[j] = M::NEURAL_PREC ? 0.f : LOG2PI_F - logf(prec[j]);
+    if constexpr (OWN_PREC) lc[j] = 0.f;  // (unused: the own branch of the time loop forms the term from its values)
+    else lc[j] = M::NEURAL_PREC ? 0.f : LOG2PI_F - logf(prec[j]);
     lp[j] = 0.f;
   }
   const float* ob = a.obs + (size_t)b * 4 * a.T;
@@ -381,7 +386,7 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   // A trajectory larger than the chip's caches (the evaluation shape: 644 MB at B=234, S=1000) is written with streaming
   // (non-temporal) stores: its lines are not kept dirty in L2 / Infinity Cache, so the summaries launch that follows does not
   // share HBM with their write-back.  Training shapes keep ordinary stores (the adjoint re-reads them from cache).
-  const bool nt_traj = VIHDS_NT_TRAJ && (size_t)a.n * N * a.T * sizeof(float) > ((size_t)256 << 20);
+  const bool nt_traj = VIHDS_NT_TRAJ && (size_t)a.n * NT * a.T * sizeof(float) > ((size_t)256 << 20);
   // times / observations are fetched one step ahead so their latency is off the dependent chain
   float tA = time_at(0), tB = time_at(1);
   float obc[4], obn[4];
@@ -398,9 +403,9 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     tB = tC;
     if (a.traj) {
       if (nt_traj) {  // (streaming stores at evaluation-sized launches: see nt_traj)
-        VIHDS_UNROLL for (int j = 0; j < N; ++j) __builtin_nontemporal_store(y[j], &a.traj[((size_t)k * N + j) * n + i]);
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) __builtin_nontemporal_store(y[j], &a.traj[((size_t)k * NT + j) * n + i]);
       } else {
-        VIHDS_UNROLL for (int j = 0; j < N; ++j) a.traj[((size_t)k * N + j) * n + i] = y[j];
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) a.traj[((size_t)k * NT + j) * n + i] = y[j];
       }
     }
     float xp[4];
@@ -409,7 +414,28 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     if (a.xpred) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.xpred[((size_t)k * 4 + j) * n + i] = xp[j];
     }
-    if (a.logp) {
+    if constexpr (OWN_PREC) {
+      // a precision map of the model's own: evaluated on the species and the predicted signals of this time point, stored
+      // as the four rows behind the species (where a *_precisions model keeps its precision states); the log-likelihood
+      // term is the neural branch's.  (A branch of its own: every other model's code stays what it was.)
+      float pr4[4];
+      M::precision(y, xp, p, pr4);
+      if (a.traj) {
+        if (nt_traj) {
+          VIHDS_UNROLL for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(pr4[j], &a.traj[((size_t)k * NT + N + j) * n + i]);
+        } else {
+          VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.traj[((size_t)k * NT + N + j) * n + i] = pr4[j];
+        }
+      }
+      if (a.logp) {
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+          const float e = xp[j] - obc[j];
+          const float pr = pr4[j];
+          lp[j] += -0.5f * (LOG2PI_F - logf(pr) + pr * e * e);
+          obc[j] = obn[j];
+        }
+      }
+    } else if (a.logp) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
         const float e = xp[j] - obc[j];
         if (M::NEURAL_PREC) {  // precisions are ODE states (reference precisions.py:89-94)
@@ -581,6 +607,8 @@ inline int launch_fwd_summ(int solver, const OdeArgs& a, const SummArgs& sa, hip
 template <class M, int SOLVER, bool DUMP = false>
 __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   constexpr int N = M::N;
+  constexpr int NT = traj_rows<M>::value;  // rows per time point of traj_in / g_traj (the precision rows of traj_in are never read)
+  constexpr bool OWN_PREC = own_prec<M>::value;
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   const float* wts = stage_weights<M>(a, wlds);
   const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -615,7 +643,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
 
   // software pipeline: the stored state, observations and times of step k-1 are requested while step k computes
   float yn[N], obn[4];
-  VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(a.T - 1) * N + j) * n + i];
+  VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(a.T - 1) * NT + j) * n + i];
   VIHDS_UNROLL for (int j = 0; j < 4; ++j) obn[j] = ob[j * a.T + a.T - 1];
   float tHi = a.times[a.T - 1], tLo = tHi;
   for (int k = a.T - 1; k >= 0; --k) {
@@ -624,7 +652,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     VIHDS_UNROLL for (int j = 0; j < 4; ++j) obk[j] = obn[j];
     const float tK = tLo;
     if (k > 0) {
-      VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(k - 1) * N + j) * n + i];
+      VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(k - 1) * NT + j) * n + i];
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) obn[j] = ob[j * a.T + k - 1];
       tLo = a.times[k - 1];
     }
@@ -634,20 +662,39 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     float xp[4], xpb[4];
     if constexpr (M::OBS == OBS_CUSTOM) M::observe(y, p, xp);
     else observe<M::OBS>(y, xp);
-    VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
-      const float e = xp[j] - obk[j];
-      const float pr = M::NEURAL_PREC ? y[(M::N - 4) + j] : prec[j];
-      xpb[j] = -glp[j] * pr * e;
-      const float prb = glp[j] * (0.5f / pr - 0.5f * e * e);
-      if (M::NEURAL_PREC) lam[(M::N - 4) + j] += prb;
-      else precb[j] += prb;
-      if (a.g_xpred) xpb[j] += a.g_xpred[((size_t)k * 4 + j) * n + i];
+    if constexpr (OWN_PREC) {
+      // a precision map of the model's own (a branch of its own: every other model's code stays what it was).  The forward
+      // values are recomputed, never read from traj_in; prb is the log-likelihood's part plus what arrives for the four
+      // precision rows of the trajectory.  The precision adjoint goes into lam, xpb and pb BEFORE the observation map's
+      // adjoint runs: a precision that depends on the predicted signals chains through observe_vjp; its parameter part joins
+      // pb ahead of prepare_vjp like the map's
+      float pr4[4], prb4[4];
+      M::precision(y, xp, p, pr4);
+      VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+        const float e = xp[j] - obk[j];
+        const float pr = pr4[j];
+        xpb[j] = -glp[j] * pr * e;
+        prb4[j] = glp[j] * (0.5f / pr - 0.5f * e * e);
+        if (a.g_traj) prb4[j] += a.g_traj[((size_t)k * NT + N + j) * n + i];
+        if (a.g_xpred) xpb[j] += a.g_xpred[((size_t)k * 4 + j) * n + i];
+      }
+      M::precision_vjp(y, xp, p, prb4, lam, xpb, pb);
+    } else {
+      VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+        const float e = xp[j] - obk[j];
+        const float pr = M::NEURAL_PREC ? y[(M::N - 4) + j] : prec[j];
+        xpb[j] = -glp[j] * pr * e;
+        const float prb = glp[j] * (0.5f / pr - 0.5f * e * e);
+        if (M::NEURAL_PREC) lam[(M::N - 4) + j] += prb;
+        else precb[j] += prb;
+        if (a.g_xpred) xpb[j] += a.g_xpred[((size_t)k * 4 + j) * n + i];
+      }
     }
     // (a custom map also has a parameter adjoint: it joins pb ahead of prepare_vjp and reaches g_theta through the epilogue)
     if constexpr (M::OBS == OBS_CUSTOM) M::observe_vjp(y, p, xpb, lam, pb);
     else observe_vjp<M::OBS>(y, xpb, lam);
     if (a.g_traj) {
-      VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] += a.g_traj[((size_t)k * N + j) * n + i];
+      VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] += a.g_traj[((size_t)k * NT + j) * n + i];
     }
   }
   float thb[M::NSLOT];
@@ -661,8 +708,10 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   M::init_vjp(lam, thb);
   if (live) {
     VIHDS_UNROLL for (int q = 0; q < M::NSLOT; ++q) a.g_theta[(size_t)a.slot_row[q] * n + i] = thb[q];
-    if (!M::NEURAL_PREC) {
-      VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.g_theta[(size_t)a.slot_row[M::NSLOT + j] * n + i] = precb[j];
+    if constexpr (!OWN_PREC) {  // (a precision map of the model's own has no precision slot rows: nothing to store)
+      if (!M::NEURAL_PREC) {
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.g_theta[(size_t)a.slot_row[M::NSLOT + j] * n + i] = precb[j];
+      }
     }
   }
   if constexpr (!is_blackbox<M>::value && M::NEURAL_PREC) {
@@ -758,9 +807,10 @@ namespace vihds {
 
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
-  if constexpr (net_fields<M>::value > 0 || M::OBS == OBS_CUSTOM) {
+  if constexpr (net_fields<M>::value > 0 || M::OBS == OBS_CUSTOM || own_prec<M>::value) {
     // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers;
-    // a model with an observation map of its own: the one-pass summaries know the fixed maps only)
+    // a model with an observation map of its own: the one-pass summaries know the fixed maps only; a model with a precision
+    // map of its own: both families know the constant precisions and the precision states only)
     if (mode.summ || mode.dev) return VIHDS_E_UNSUPPORTED;
   } else {
     if (const SummArgs* sm = mode.summ) {  // vihds_ode_fwd_summaries: the evaluation's second forward pass

@@ -32,6 +32,8 @@ MODELS = {
 # registered generated models with networks of their own (modelgen.register_kernel): key -> [(n_inputs, n_hidden,
 # n_outputs)] in the weight buffer's order
 GENERATED_NETWORKS = {}
+# keys of registered models with a precision map of their own: four precision rows behind the species, no precision network
+GENERATED_OWN_PRECISION = set()
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8}

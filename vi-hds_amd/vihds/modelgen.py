@@ -21,6 +21,8 @@ A model is one subclass of GeneratedOdeModel (the plugin surface of the referenc
             return [...]
         def observe(self, y, p, c):        # optional; reference observe(x_sample, theta): the OD, RFP, YFP, CFP signals
             return [y[0], p.gain * y[0] * y[1] + p.bg, ...]
+        def precision(self, y, x, p, c):   # optional; the precisions of the four signals (then no self.precisions above)
+            return [1.0 / (p.s0_od * p.s0_od + pow(p.s1_od * x[0], 2.0)), ...]
 
 `c` holds the treatments after clamp(exp(cond) - 1, 1e-12, 1e6) (the c[] contract of csrc/vihds_models.hpp).  The three
 functions use + - * / (unary minus, Python numbers) and the operations of this module: exp, log, pow, sigmoid, tanh and
@@ -45,6 +47,21 @@ reverse-mode adjoint as two more members of the struct, called once per time poi
 A parameter may be read by observe only; a treatment it reads is copied by prepare like one rhs reads.  On instances
 `observe` stays OdeModel.observe(x_sample, theta) (the definition is kept as the class's map, as `parameters` is kept as
 parameter_names); torch_observe evaluates it with torch ops.
+
+The observation noise.  Without `precision` the precisions are what the instance's `precisions` says: four constant theta
+entries (ConstantPrecisions: the slots prec_x .. prec_cfp behind the model's own) or the reference's precision ODE
+(NeuralPrecisions).  A model that defines precision(y, x, p, c) -> list of 4 owns them: the method is traced into the same DAG
+(the operations and limits of observe: no t, no network calls) and sees the species, the four predicted signals x of that time
+point (from the model's observe, or from the fixed map of its observe_kind), the effective parameters and the treatments.  It
+is emitted with its reverse-mode adjoint as the members precision / precision_vjp, called once per time point; the forward
+kernel stores the four values as four rows behind the species in the trajectory (the layout of a NeuralPrecisions model, so
+expand_precisions and the evaluation summaries read them unchanged).  Such a model has no prec_* or init_prec_* slots -- its
+noise parameters are ordinary entries of `parameters`, which may then be as many as VIHDS_MAX_SLOTS (not VIHDS_MAX_SLOTS - 4)
+-- and its `precisions` attribute is a ModelPrecisions the base class creates; assigning another kind raises, and it does not
+combine with NeuralPrecisions.  POSITIVITY IS THE AUTHOR'S RESPONSIBILITY: the log-likelihood takes logf of each value, so a
+non-positive precision gives NaN exactly as a non-positive constant precision does; no clamp is inserted (write
+1 / (s0^2 + (s1 x)^2), exp(.), or clamp(., 1e-6, 1e6) where the expression could reach 0).  torch_precision evaluates the
+definition with torch ops.
 
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
@@ -122,7 +139,7 @@ def _class_networks(cls):
 # ---------------------------------------------------------------------------------------------------------------------
 # expression DAG
 # ---------------------------------------------------------------------------------------------------------------------
-_LEAVES = ("const", "th", "c", "y", "p", "t", "seed")
+_LEAVES = ("const", "th", "c", "y", "p", "t", "seed", "x")  # (x: the predicted signals precision() reads)
 _COMMUTATIVE = ("add", "mul")
 
 
@@ -568,7 +585,8 @@ class _Networks(object):
 
 
 class Trace(object):
-    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe) traced into one Graph."""
+    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe and precision) traced into one
+    Graph."""
 
     def __init__(self, cls):
         inst = cls.__new__(cls)  # (the functions are methods; nothing of nn.Module is touched by them)
@@ -580,7 +598,7 @@ class Trace(object):
         def call(k, name, net, inputs):
             if self._phase != "rhs":
                 raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only (not in "
-                                           "prepare, initial_state or observe)" % (name, self._phase))
+                                           "prepare, initial_state, observe or precision)" % (name, self._phase))
             if name in self._called:
                 raise ModelDefinitionError("network '%s' is called twice: a network may be called at most once per rhs "
                                            "evaluation (its adjoint dump has one slot per evaluation)" % name)
@@ -622,9 +640,20 @@ class Trace(object):
                 raise ModelDefinitionError("%s.observe must return a list of 4 entries (the OD, RFP, YFP and CFP signals)"
                                            % cls.__name__)
             self.obs = [g._arg(x) for x in xp]
-        used = {n.val for n in _topo(self.dy + (self.obs or [])) if n.op == "p"}
-        self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs or by observe)
-        # remap the treatments rhs / observe read to consecutive parameter indices behind the named ones
+        # precision (optional) sees the species, the four predicted signals, the effective parameters and the treatments
+        self.prec = None
+        definition = getattr(cls, "_precision_def", None)
+        if definition is not None:
+            self._phase = "precision"
+            pr = definition(inst, [g.leaf("y", j) for j in range(N)], [g.leaf("x", j) for j in range(4)], p,
+                            _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
+            if not isinstance(pr, (list, tuple)) or len(pr) != 4:
+                raise ModelDefinitionError("%s.precision must return a list of 4 entries (the precisions of the OD, RFP, YFP "
+                                           "and CFP signals)" % cls.__name__)
+            self.prec = [g._arg(x) for x in pr]
+        used = {n.val for n in _topo(self.dy + (self.obs or []) + (self.prec or [])) if n.op == "p"}
+        self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe or by precision)
+        # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
         self.c_slot = {NPU + q: NPU + k for k, q in enumerate(self.c_in_rhs)}
 
@@ -788,6 +817,9 @@ def generate_source(cls, neural=False):
     recomputed inside them) and the switches csrc/generated/ode_generated_model.hip reads.  Deterministic: the same
     definition gives byte-identical text; its hash (with the kernel headers') names the library."""
     tr = cls._trace
+    if neural and tr.prec is not None:
+        raise ModelDefinitionError("%s defines precision(self, y, x, p, c): a model with a precision map of its own does not "
+                                   "take NeuralPrecisions" % cls.__name__)
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -834,8 +866,20 @@ def generate_source(cls, neural=False):
         obs_vjp = [("yb[%d]" % j, "+=", adj2[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj2]
         obs_vjp += [("pb[%d]" % k, "+=", adj2[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj2]
 
+    # precision / precision_vjp (a model with a precision map of its own): once per time point inside the time loop, like
+    # the map.  The adjoint adds into yb, into xpb (the predicted signals' adjoint, which observe_vjp then pulls back) and
+    # into pb of the named effective parameters
+    prec_decl = []
+    if tr.prec is not None:
+        prb = [g.leaf("seed", j) for j in range(4)]
+        adj3 = vjp(g, tr.prec, prb)
+        prec = [("pr[%d]" % j, "=", e) for j, e in enumerate(tr.prec)]
+        prec_vjp = [("yb[%d]" % j, "+=", adj3[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj3]
+        prec_vjp += [("xpb[%d]" % j, "+=", adj3[g.leaf("x", j).id]) for j in range(4) if g.leaf("x", j).id in adj3]
+        prec_vjp += [("pb[%d]" % k, "+=", adj3[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj3]
+
     def body(assign, fast, seed, p_map=None):
-        names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed}
+        names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp"}
         return "\n".join(_Emitter(fast, names, p_map).emit(assign))
 
     names = ", ".join('"%s"' % n for n in P)
@@ -872,6 +916,17 @@ def generate_source(cls, neural=False):
             "  }",
             "  __device__ static void observe_vjp(const float* y, const float* p, const float* xpb, float* yb, float* pb) {",
             body(obs_vjp, True, "xpb", tr.c_slot),
+            "  }",
+        ]
+    if tr.prec is not None:
+        prec_decl = [
+            "  static constexpr bool OWN_PREC = true;  // the precisions are this struct's map: no prec_* / init_prec_* slots",
+            "  __device__ static void precision(const float* y, const float* xp, const float* p, float* pr) {",
+            body(prec, True, "prb", tr.c_slot),
+            "  }",
+            "  __device__ static void precision_vjp(const float* y, const float* xp, const float* p, const float* prb, float* yb,",
+            "                                       float* xpb, float* pb) {",
+            body(prec_vjp, True, "prb", tr.c_slot),
             "  }",
         ]
     out = [
@@ -912,7 +967,7 @@ def generate_source(cls, neural=False):
     ] + vjp_sig + [
         body(rhs_vjp, True, "v", tr.c_slot),
         "  }",
-    ] + obs_decl + [
+    ] + obs_decl + prec_decl + [
         "};",
         "}  // namespace vihds",
         "#define VIHDS_GEN_CORE %s" % sname,
@@ -1012,6 +1067,8 @@ def register_kernel(cls, neural=False):
     hip.MODELS[key] = mid
     # what ops needs to contract the adjoint's dump: the networks' sizes, in the weight buffer's order
     hip.GENERATED_NETWORKS[key] = [net.sizes for net in _class_networks(cls).values()]
+    if cls._trace.prec is not None:  # (four precision rows behind the species that are no NeuralPrecisions states)
+        hip.GENERATED_OWN_PRECISION.add(key)
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -1028,6 +1085,7 @@ class GeneratedOdeModel(OdeModel):
     n_conditions = 0
     observe_kind = "default"
     _observe_def = None  # the class's own observation map observe(self, y, p, c), when it defines one (module docstring)
+    _precision_def = None  # the class's own precision map precision(self, y, x, p, c), when it defines one (module docstring)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
 
     def __init_subclass__(cls, **kw):
@@ -1056,6 +1114,11 @@ class GeneratedOdeModel(OdeModel):
                 if k is GeneratedOdeModel:
                     break
             cls.observe_kind, cls._observe_kind_set = OBSERVE_CUSTOM, True
+        definition = cls.__dict__.get("precision")
+        if definition is not None:
+            if not callable(definition):
+                raise ModelDefinitionError("%s.precision must be a function precision(self, y, x, p, c)" % cls.__name__)
+            cls._precision_def = definition
         if cls.__dict__.get("model_key") is None and getattr(cls, "_trace", None) is not None:
             cls._trace = Trace(cls)  # (a subclass that only changes __init__)
             return
@@ -1069,6 +1132,9 @@ class GeneratedOdeModel(OdeModel):
         super(GeneratedOdeModel, self).__init__(config)
         self.species = list(type(self).species)
         self.n_species = len(self.species)
+        if type(self)._precision_def is not None:  # the model's own precision map: the rows the kernel stores behind the species
+            from vihds.precisions import ModelPrecisions
+            self.precisions = ModelPrecisions()
         # the networks' weights (created under the seed the caller set for the whole model, like every module here): the
         # weight matrices as the reference's NeuralStates initialises them, the biases nn.Linear's default
         nets = _class_networks(type(self))
@@ -1083,6 +1149,21 @@ class GeneratedOdeModel(OdeModel):
                 self.nets[name] = m
             self._flat_all = None
             object.__setattr__(self, "net", _Networks(type(self), self._torch_call(self.network_weights)))
+
+    def __setattr__(self, name, value):
+        if name == "precisions" and value is not None and type(self)._precision_def is not None:
+            from vihds.precisions import ModelPrecisions
+            if not isinstance(value, ModelPrecisions):
+                raise ModelDefinitionError(
+                    "%s defines precision(self, y, x, p, c): its precisions are that map (a ModelPrecisions the base class "
+                    "creates), not %s -- a subclass __init__ must not assign self.precisions" % (
+                        type(self).__name__, type(value).__name__))
+        super(GeneratedOdeModel, self).__setattr__(name, value)
+
+    @property
+    def precision_kind(self):
+        """'custom' for a model with a precision map of its own (module docstring), else 'fixed'."""
+        return "custom" if type(self)._precision_def is not None else "fixed"
 
     # the three functions of a model
     def prepare(self, th, c):
@@ -1099,7 +1180,7 @@ class GeneratedOdeModel(OdeModel):
 
     # kernels
     def _neural(self):
-        return bool(getattr(self.precisions, "dynamic", False))
+        return type(self)._precision_def is None and bool(getattr(self.precisions, "dynamic", False))
 
     def kernel_slots(self):
         register_kernel(type(self), self._neural())
@@ -1193,6 +1274,25 @@ class GeneratedOdeModel(OdeModel):
                                        % (cls.__name__, cls.observe_kind))
         return _observe_torch(cls, cls.__new__(cls), y[:, :, :len(cls.species), :], theta, cond)
 
+    @classmethod
+    def torch_precision(cls, y, theta, cond):
+        """The model's own precision map with torch ops in y's dtype (the float64 reference of the generated precision /
+        precision_vjp, as torch_observe is for the map): y [B,S,N,T] species (rows stored behind them are ignored), theta
+        {parameter name: [B,S]} and cond [B,C] as the data holds it.  prepare and the observation map -- the model's own
+        observe, or the fixed map of its observe_kind -- are applied first -> precisions [B,S,4,T]."""
+        if cls._precision_def is None:
+            raise ModelDefinitionError("%s defines no precision(self, y, x, p, c): its precisions are its `precisions` "
+                                       "attribute's" % cls.__name__)
+        inst = cls.__new__(cls)
+        y = y[:, :, :len(cls.species), :]
+        if cls._observe_def is not None:
+            x = _observe_torch(cls, inst, y, theta, cond)
+        else:
+            fixed = OdeModel.__new__(OdeModel)  # (the fixed maps of OdeModel._observe_map read observe_kind only)
+            fixed.__dict__["observe_kind"] = cls.observe_kind
+            x = OdeModel._observe_map(fixed, y)
+        return _precision_torch(cls, inst, y, x, theta, cond)
+
     def _observe_map(self, x_sample):
         """OdeModel.observe on a tensor that is not the last solution: the model's own map (torch_observe) with theta and
         the treatments of the last solve."""
@@ -1220,6 +1320,21 @@ def _observe_torch(cls, inst, y, th, cond):
     return torch.stack([full(v) for v in xp], dim=2)
 
 
+def _precision_torch(cls, inst, y, x, th, cond):
+    """The class's precision map with torch ops: y [B,S,N,T], x [B,S,4,T], th {parameter name: [B,S]}, cond [B,C] -> [B,S,4,T]."""
+    ref = y[:, :, 0, :]
+    S = ref.shape[1]
+    tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
+    cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+    thn = _Named([(n, th[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
+    over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
+    p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
+    pr = cls._precision_def(inst, list(torch.unbind(y, dim=2)), list(torch.unbind(x, dim=2)), p,
+                            _Conditions([over_time(v) for v in cs]))
+    full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
+    return torch.stack([full(v) for v in pr], dim=2)
+
+
 def _validate(cls):
     name = cls.__name__
     if not isinstance(cls.model_key, str) or not cls.model_key:
@@ -1241,10 +1356,13 @@ def _validate(cls):
     if len(cls.species) > MAX_STATES:
         raise ModelDefinitionError("%s: %d species; generated models hold at most %d states"
                                    % (name, len(cls.species), MAX_STATES))
-    # four more slots follow the model's own: the constant precisions, or the neural precisions' initial values
-    if len(cls.parameter_names) + 4 > hip.VIHDS_MAX_SLOTS:
-        raise ModelDefinitionError("%s: %d parameters; the kernels read at most %d slots (VIHDS_MAX_SLOTS, 4 of them for "
-                                   "the precisions)" % (name, len(cls.parameter_names), hip.VIHDS_MAX_SLOTS - 4))
+    # four more slots follow the model's own: the constant precisions, or the neural precisions' initial values -- unless the
+    # model has a precision map of its own (its noise parameters are among its own slots)
+    n_prec_slots = 0 if getattr(cls, "_precision_def", None) is not None else 4
+    if len(cls.parameter_names) + n_prec_slots > hip.VIHDS_MAX_SLOTS:
+        raise ModelDefinitionError("%s: %d parameters; the kernels read at most %d slots (VIHDS_MAX_SLOTS%s)" % (
+            name, len(cls.parameter_names), hip.VIHDS_MAX_SLOTS - n_prec_slots,
+            ", 4 of them for the precisions" if n_prec_slots else ": a model with a precision map of its own has all of them"))
     if not isinstance(cls.n_conditions, int) or cls.n_conditions < 0:
         raise ModelDefinitionError("%s.n_conditions must be an integer >= 0" % name)
     nets = getattr(cls, "networks", None)

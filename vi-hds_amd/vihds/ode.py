@@ -79,6 +79,7 @@ class OdeModel(nn.Module):
 
     model_key = None
     observe_kind = "default"
+    precision_kind = "fixed"  # "custom": a generated model's own precision map (vihds/modelgen.py)
 
     def __init__(self, config):
         super(OdeModel, self).__init__()
@@ -254,9 +255,11 @@ class OdeModel(nn.Module):
         # form it inside their kernel, plugin code reading DecoderResult gets it from the map below
         # (... and so do training steps whose backward is ops.GeneralTail: nobody reads x_predict there)
         # (a map of the model's own -- observe_kind "custom", vihds/modelgen.py -- exists in its kernels only and may read
-        # theta: such a model always stores x_predict, and the summaries take it from that buffer)
+        # theta: such a model always stores x_predict, and the summaries take it from that buffer; so does a model with a
+        # precision map of its own -- its precision rows go to vihds_iw_summaries, which takes x_predict as a buffer)
         lazy = ((not torch.is_grad_enabled() or getattr(self, "_train_without_x_predict", False))
-                and bool(default_get_value(config.params, "lazy_x_predict", True)) and self.observe_kind != "custom")
+                and bool(default_get_value(config.params, "lazy_x_predict", True)) and self.observe_kind != "custom"
+                and self.precision_kind != "custom")
         traj, xpred, logp = ops.OdeSolveObserve.apply(spec, packed, conditions.to(dev), times, obs.to(dev),
                                                       dev_1hot.to(dev) if dev_1hot is not None else None,
                                                       self.neural_weights(), row_offset, row_offset_map, not lazy)

@@ -129,6 +129,8 @@ class OdeProblemSpec:
         # a generated model's own networks [(n_inputs, n_hidden, n_outputs)]: their weights lead the weight buffer, their
         # dump fields lead the adjoint's aux buffer (decoder_weight_grads)
         self.networks = list(hip.GENERATED_NETWORKS.get(model, ()))
+        # a generated model's own precision map: n_states - n_species = 4 rows the kernel stores, not a precision network
+        self.own_precision = model in hip.GENERATED_OWN_PRECISION
         self.covers_all_rows = len({row_of[s] for s in self.slots}) == n_rows
         self.unwritten_rows = sorted(set(range(n_rows)) - {row_of[s] for s in self.slots})  # rows the adjoint leaves alone
         self.cache = {}  # device-side constants derived from this spec
@@ -691,7 +693,7 @@ def decoder_weight_grads(spec, prob, aux, g_w):
     is the same bits run to run.  The precision network's section (neural_precision_weight_grads) follows."""
     if not spec.networks:
         return neural_precision_weight_grads(spec, prob, aux, g_w)
-    neural = spec.n_species < spec.n_states
+    neural = spec.n_species < spec.n_states and not spec.own_precision
     F_all = sum(I + 2 * H + O for I, H, O in spec.networks)
     if neural:
         F_all += 8 + (spec.n_species + 1) + 2 * max(int(spec.proto.n_hidden_prec), 0)

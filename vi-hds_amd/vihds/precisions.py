@@ -29,6 +29,27 @@ class ConstantPrecisions(nn.Module):
         pass
 
 
+class ModelPrecisions(nn.Module):
+    """Precisions a generated model defines itself (GeneratedOdeModel.precision, vihds/modelgen.py): the ODE kernel evaluates
+    the map at every time point and stores the four values as the last four rows of the states, where a NeuralPrecisions
+    model keeps its precision states.  No parameters of its own: the noise parameters are entries of theta."""
+
+    n_outputs = 4
+
+    def __init__(self):
+        super(ModelPrecisions, self).__init__()
+        self.dynamic = True  # (the precisions are rows of the solution, not theta entries)
+
+    def weight_tensors(self):
+        return []
+
+    def expand(self, theta, _n_times, x_states):
+        return x_states[:, :, : -self.n_outputs, :], x_states[:, :, -self.n_outputs:, :]
+
+    def summaries(self, _writer, _epoch):
+        pass
+
+
 class NeuralPrecisions(nn.Module):
     """d prec/dt = sigmoid(prod(.)) - sigmoid(degr(.)) * prec with the wiring of reference precisions.py:41-74.
     The weights live here (so optimisers and summaries see them); the arithmetic runs inside the ODE kernels."""
