@@ -1,12 +1,15 @@
 """Which model launcher accepts which launch mode: every mode-carrying ODE entry point of the C ABI (the plain forward, the
 sampling stage in front of it, the evaluation's second pass, the host-driven and the device-resident adaptive controllers)
-called for every built-in model, one registered generated model and one sized dr_blackbox side library, at kernel_variant
+and the two backward entry points (vihds_ode_bwd at rk4, vihds_ode_bwd_elbo at both solvers, on the trajectory the plain
+forward just wrote) called for every built-in model, one registered generated model and one sized dr_blackbox side library, at kernel_variant
 0 / 1 and rk4 / dopri5, against the table recorded in tests/golden/launch_mode_table.json.
 
 The launchers decide on model, variant, solver and mode, never on size, so the smallest legal shape (B 2, S 3, T 5) takes
 every branch.  Parameters sit at their prior locations (q = p, u = 0 through the library's own sampling stage), every call
 gets real device buffers of the sizes the library's own queries ask for, and outputs start as NaN: "finite" means written
-and finite.  A launcher that accepts a mode it used to decline therefore shows up as a table mismatch, not as a fault.
+and finite.  (g_weights is the one output the kernels ADD to: it starts as zero like its callers', "finite" covers it, and
+"g_weights_written" records whether anything arrived in it -- dr_blackbox leaves it alone, its gradients come from aux.)
+A launcher that accepts a mode it used to decline therefore shows up as a table mismatch, not as a fault.
 
 Record the table (on a GPU, against the library the table is to pin):  python tests/test_launch_modes.py --out <file>"""
 import ctypes
@@ -159,6 +162,28 @@ def _call(L, fn, outputs):
     return {"rc": 0, "finite": _finite(*outputs())}
 
 
+def _backward(L, x, pp, name, times, traj, logp, with_aux=True):
+    """One backward entry point on the forward's trajectory: aux and g_weights of the sizes the library's queries return."""
+    from vihds import hip
+
+    n_aux, n_w = int(L.vihds_ode_bwd_aux_floats(pp)), int(L.vihds_model_n_weights(pp))
+    aux = torch.zeros(n_aux, device=DEV) if with_aux and n_aux > 0 else None
+    g_w = torch.zeros(n_w, device=DEV) if n_w > 0 else None
+    g_theta = _nan(*x["theta"].shape)
+    head = (pp, hip.ptr(x["theta"]), hip.ptr(x["cond"]), hip.ptr(x["dev1hot"]), hip.ptr(times), hip.ptr(x["obs"]),
+            hip.ptr(x["weights"]), hip.ptr(traj))
+    if name == "vihds_ode_bwd":
+        grads = (torch.full_like(traj, 0.01), torch.full((T, 4, B, S), 0.01, device=DEV), torch.ones(4, B, S, device=DEV))
+    else:  # (the log-likelihood gradient is formed in the kernel from logp, log_p, log_q)
+        grads = (logp, torch.zeros(B, S, device=DEV), torch.zeros(B, S, device=DEV))
+    row = _call(L, lambda: getattr(L, name)(*head, *(hip.ptr(g) for g in grads), hip.ptr(g_theta), hip.ptr(g_w), hip.ptr(aux),
+                                            hip.current_stream()),
+                lambda: (g_theta,) + ((g_w,) if g_w is not None else ()))
+    if row["rc"] == 0 and g_w is not None:
+        row["g_weights_written"] = bool((g_w != 0).any())
+    return row
+
+
 def _run(case, variant, solver):
     from vihds import hip
 
@@ -178,6 +203,11 @@ def _run(case, variant, solver):
     out["vihds_ode_fwd"] = _call(L, lambda: L.vihds_ode_fwd(
         pp, hip.ptr(theta), hip.ptr(cond), hip.ptr(dev1hot), hip.ptr(times), hip.ptr(obs), hip.ptr(w), hip.ptr(traj),
         hip.ptr(xpred), hip.ptr(logp), st), lambda: (traj, xpred, logp))
+
+    for name in (("vihds_ode_bwd",) if solver == "rk4" else ()) + ("vihds_ode_bwd_elbo",):
+        out[name] = _backward(L, x, pp, name, times, traj, logp)
+        if spec.model == "dr_blackbox":  # (refused before any launch)
+            out[name + " without aux"] = _backward(L, x, pp, name, times, traj, logp, with_aux=False)
 
     traj, xpred, logp = _nan(T, N, B, S), _nan(T, 4, B, S), _nan(4, B, S)
     th2, log_q, log_p = theta.clone(), _nan(B, S), _nan(B, S)

@@ -41,8 +41,8 @@ VIHDS_GEN_DECL(0) VIHDS_GEN_DECL(1) VIHDS_GEN_DECL(2) VIHDS_GEN_DECL(3) VIHDS_GE
 VIHDS_GEN_DECL(6) VIHDS_GEN_DECL(7) VIHDS_GEN_DECL(8)
 static_assert(VIHDS_SOLVER_COUNT == 9, "one object per solver: extend the table and the Makefile");
 namespace vihds {
-// (the wrapper in vihds_api.hip declines the sampling stage, the one-pass summaries and the device-resident adaptive solver
-// for registered models before it calls in: of the launch modes only the host-driven controller arrives here)
+// (the entry points of vihds_api.hip decline the sampling stage, the one-pass summaries and the device-resident adaptive
+// solver for registered models before any launcher is called: of the launch modes only the host-driven controller arrives here)
 template <class M>
 static int n_weights_of(int H) {
   if constexpr (M::NEURAL_PREC) return VIHDS_GEN_CORE::NW + M::n_weights(H);

@@ -1,5 +1,6 @@
 // dr_blackbox kernels for the configuration of the reference's specs/dr_blackbox_icml.yaml (BlackboxIcml, vihds_blackbox.hpp).
 #include "vihds_ode_kernels.hpp"
+#include "vihds_bb_variant.hpp"
 #include "vihds_blackbox_split.hpp"
 
 // Compiled TWICE (csrc/Makefile): VIHDS_BB_PART 1 = the forward launch of the cooperating-wavefront kernels alone, built
@@ -33,25 +34,12 @@ int launch_dr_blackbox(bool backward, int solver, const OdeArgs& a, hipStream_t 
   }
   return launch_bb_split_dir<BbMfma, true>(solver, a, st);
 }
-int bb_n_weights(int n_const) { return BB::n_weights(n_const); }
-// kernel_variant 0 (anything but 1) with a fixed-grid solver: the matrix-core adjoint with the Gram tiles on chip
-static bool bb_gram_mode(int solver, int kernel_variant) {
-  return kernel_variant != 1 && !solver_is_adaptive(solver);
-}
-long long bb_aux_floats(int n, int T, int solver, int kernel_variant) {
-  return (long long)bb_mfma_head_floats(n, T, solver, bb_gram_mode(solver, kernel_variant)) + (long long)BB::NTAIL * n;
-}
-long long bb_tail_offset_floats(int n, int T, int solver, int kernel_variant) {
-  return (long long)bb_mfma_head_floats(n, T, solver, bb_gram_mode(solver, kernel_variant));
-}
-int bb_gram_on_chip(int solver, int kernel_variant) { return bb_gram_mode(solver, kernel_variant) ? 1 : 0; }
-void bb_gram_reduce(const OdeArgs& a, const float* aux, float* g_weights, hipStream_t st) {
-  launch_bb_gram_reduce<BbMfma>(a, aux, g_weights, st);
-}
-int bb_check(int L, int HS, int HP, int n_const, int C, int D) {
-  return L == 2 && HS == 25 && HP == 20 && n_const == BB::NLAT + C + D;
-}
-int bb_dump_fields() { return BB::NF; }
+// The ICML sizes as the record every size set has (vihds_bb_variant.hpp): vihds_api.hip resolves a dr_blackbox problem to
+// this one or to a side library's, and reads sizes, launcher and aux layout from whichever it got.
+static long long bb_builtin_gram_floats(int n) { return (long long)BbMfma::gram_floats(n); }
+static const BbVariant kBuiltinVariant = {2, 25, 20, BB::NLAT, BB::N, BB::NSLOT, BB::NF, BB::NTAIL, BB::n_weights,
+                                          launch_dr_blackbox, 1, bb_builtin_gram_floats, launch_bb_gram_reduce<BbMfma>};
+const BbVariant* bb_builtin_variant() { return &kBuiltinVariant; }
 }  // namespace vihds
 #endif  // VIHDS_BB_PART
 #ifdef VIHDS_BB_STAMPS

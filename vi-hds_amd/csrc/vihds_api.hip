@@ -11,7 +11,6 @@
 #include <mutex>
 #include <string>
 #include <tuple>
-#include <utility>
 
 #include <limits.h>
 #include <stdlib.h>
@@ -45,13 +44,7 @@ VIHDS_DECL(relay_constant_prec)
 VIHDS_DECL(degrader_constant_prec)
 VIHDS_DECL(dr_blackbox)
 #undef VIHDS_DECL
-int bb_n_weights(int n_const);
-long long bb_aux_floats(int n, int T, int solver, int kernel_variant);
-long long bb_tail_offset_floats(int n, int T, int solver, int kernel_variant);
-int bb_gram_on_chip(int solver, int kernel_variant);
-void bb_gram_reduce(const OdeArgs& a, const float* aux, float* g_weights, hipStream_t st);
-int bb_check(int L, int HS, int HP, int n_const, int C, int D);
-int bb_dump_fields();
+const BbVariant* bb_builtin_variant();  // ode_dr_blackbox.hip: the built-in dr_blackbox sizes
 
 int launch_dr_constant_train_v1(int, const OdeArgs&, hipStream_t, const ThetaStageArgs*);
 int launch_dr_constant_train_v2(int, const OdeArgs&, hipStream_t, const ThetaStageArgs*);
@@ -107,12 +100,16 @@ struct ModelEntry {
   const char* (*slot_name_of)(int);  // a built-in model's names ...
   const char* const* slot_names;     // ... a registered model's (GenModelRecord)
   bool neural_prec;
+  // species of the model's lane kernels (vihds_relay_lanes.hpp: relay / degrader / prpr / auto_constant, with constant or
+  // neural precisions), 0 for a model without them
+  int lane_species = 0;
   // a registered model whose generated struct has networks of its own (GenModelRecord): weights in front of the precision
   // network's, dump fields in front of its fields
   int n_net_weights = 0, net_fields = 0;
   // a registered model with a precision map of its own (GenModelRecord::own_prec): four precision rows behind the species in
   // the trajectory like a neural-precision model, but no precision slots and no weights of its own
   bool own_prec = false;
+  int (*n_weights)(int n_hidden_prec) = nullptr;  // a registered model's whole weight buffer (GenModelRecord::n_weights)
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
   bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
   int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
@@ -120,26 +117,26 @@ struct ModelEntry {
 };
 // the entry of a built-in model: its sizes and names from the model struct M (vihds_models.hpp), its launcher from its unit
 template <class M>
-static ModelEntry entry_of(launch_fn launch) {
-  return {launch, M::NSLOT, M::N, M::NC, M::slot_name, nullptr, M::NEURAL_PREC};
+static ModelEntry entry_of(launch_fn launch, int lane_species = 0) {
+  return {launch, M::NSLOT, M::N, M::NC, M::slot_name, nullptr, M::NEURAL_PREC, lane_species};
 }
 static const ModelEntry kModels[VIHDS_MODEL_COUNT] = {
-    entry_of<DrConstant<1>>(launch_dr_constant_v1),                      // VIHDS_MODEL_DR_CONSTANT
-    entry_of<DrConstant<2>>(launch_dr_constant_v2),                      // VIHDS_MODEL_DR_CONSTANT_V2
-    entry_of<AutoConstant>(launch_auto_constant),                        // VIHDS_MODEL_AUTO_CONSTANT
-    entry_of<PrprConstant>(launch_prpr_constant),                        // VIHDS_MODEL_PRPR_CONSTANT
-    entry_of<RelayConstant>(launch_relay_constant),                      // VIHDS_MODEL_RELAY_CONSTANT
-    entry_of<DegraderConstant>(launch_degrader_constant),                // VIHDS_MODEL_DEGRADER_CONSTANT
-    entry_of<WithPrec<DrConstant<1>>>(launch_dr_constant_prec_v1),       // VIHDS_MODEL_DR_CONSTANT_PRECISIONS
-    entry_of<WithPrec<DrConstant<2>>>(launch_dr_constant_prec_v2),       // VIHDS_MODEL_DR_CONSTANT_PRECISIONS_V2
-    entry_of<WithPrec<AutoConstant>>(launch_auto_constant_prec),         // VIHDS_MODEL_AUTO_CONSTANT_PRECISIONS
-    entry_of<WithPrec<PrprConstant>>(launch_prpr_constant_prec),         // VIHDS_MODEL_PRPR_CONSTANT_PRECISIONS
-    entry_of<WithPrec<RelayConstant>>(launch_relay_constant_prec),       // VIHDS_MODEL_RELAY_CONSTANT_PRECISIONS
-    entry_of<WithPrec<DegraderConstant>>(launch_degrader_constant_prec), // VIHDS_MODEL_DEGRADER_CONSTANT_PRECISIONS
-    entry_of<BlackboxIcml>(launch_dr_blackbox),                          // VIHDS_MODEL_DR_BLACKBOX
-    entry_of<InducerConstant>(launch_inducer_constant),                  // VIHDS_MODEL_INDUCER_CONSTANT
-    entry_of<WithPrec<InducerConstant>>(launch_inducer_constant_prec),   // VIHDS_MODEL_INDUCER_CONSTANT_PRECISIONS
-    entry_of<DebugConstant>(launch_debug_constant),                      // VIHDS_MODEL_DEBUG_CONSTANT
+    entry_of<DrConstant<1>>(launch_dr_constant_v1),                                        // VIHDS_MODEL_DR_CONSTANT
+    entry_of<DrConstant<2>>(launch_dr_constant_v2),                                        // VIHDS_MODEL_DR_CONSTANT_V2
+    entry_of<AutoConstant>(launch_auto_constant, RlAuto::NSP),                             // VIHDS_MODEL_AUTO_CONSTANT
+    entry_of<PrprConstant>(launch_prpr_constant, RlPrpr::NSP),                             // VIHDS_MODEL_PRPR_CONSTANT
+    entry_of<RelayConstant>(launch_relay_constant, RlRelay::NSP),                          // VIHDS_MODEL_RELAY_CONSTANT
+    entry_of<DegraderConstant>(launch_degrader_constant, RlDegrader::NSP),                 // VIHDS_MODEL_DEGRADER_CONSTANT
+    entry_of<WithPrec<DrConstant<1>>>(launch_dr_constant_prec_v1),                         // VIHDS_MODEL_DR_CONSTANT_PRECISIONS
+    entry_of<WithPrec<DrConstant<2>>>(launch_dr_constant_prec_v2),                         // VIHDS_MODEL_DR_CONSTANT_PRECISIONS_V2
+    entry_of<WithPrec<AutoConstant>>(launch_auto_constant_prec, RlAuto::NSP),              // VIHDS_MODEL_AUTO_CONSTANT_PRECISIONS
+    entry_of<WithPrec<PrprConstant>>(launch_prpr_constant_prec, RlPrpr::NSP),              // VIHDS_MODEL_PRPR_CONSTANT_PRECISIONS
+    entry_of<WithPrec<RelayConstant>>(launch_relay_constant_prec, RlRelay::NSP),           // VIHDS_MODEL_RELAY_CONSTANT_PRECISIONS
+    entry_of<WithPrec<DegraderConstant>>(launch_degrader_constant_prec, RlDegrader::NSP),  // VIHDS_MODEL_DEGRADER_CONSTANT_PRECISIONS
+    entry_of<BlackboxIcml>(launch_dr_blackbox),                                            // VIHDS_MODEL_DR_BLACKBOX
+    entry_of<InducerConstant>(launch_inducer_constant),                                    // VIHDS_MODEL_INDUCER_CONSTANT
+    entry_of<WithPrec<InducerConstant>>(launch_inducer_constant_prec),                     // VIHDS_MODEL_INDUCER_CONSTANT_PRECISIONS
+    entry_of<DebugConstant>(launch_debug_constant),                                        // VIHDS_MODEL_DEBUG_CONSTANT
 };
 
 static thread_local char g_err[256] = "";
@@ -159,24 +156,15 @@ static int check_hip(const char* what) {
 static const char* kPrecNames[4] = {"prec_x", "prec_rfp", "prec_yfp", "prec_cfp"};
 
 // ---- registered models (vihds_gen_model.hpp): ids VIHDS_GEN_MODEL_BASE + k -------------------------------------------
-// ModelEntry::launch is a plain function pointer, so every registration slot k has its own wrapper over g_gen[k]: it declines
-// the sampling stage, the one-pass summaries and the device-resident adaptive solver (none of them exists for a registered
-// model) and passes the rest of the mode -- the host-driven adaptive controller -- on.
-static const GenModelRecord* g_gen[VIHDS_GEN_MODEL_MAX];
+// An entry's launcher is the record's own.  Of the launch modes it takes the plain ones and the host-driven adaptive
+// controller; the sampling stage, the one-pass summaries and the device-resident adaptive solver do not exist for a
+// registered model, and their entry points decline one before any launcher is called (vihds_theta_ode_fwd,
+// vihds_ode_fwd_summaries, adaptive_device_model).
 static ModelEntry g_gen_entries[VIHDS_GEN_MODEL_MAX];
 static std::atomic<int> g_gen_count{0};
-template <int K>
-struct GenSlot {
-  static int launch(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
-    if (mode.theta || mode.summ || mode.dev) return VIHDS_E_UNSUPPORTED;
-    return g_gen[K]->launch(backward, solver, a, st, mode);
-  }
-};
-template <int... K>
-static ModelEntry gen_entry_of(int k, const GenModelRecord* r, std::integer_sequence<int, K...>) {
-  static const launch_fn table[] = {GenSlot<K>::launch...};
-  return {table[k], r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, r->n_net_weights,
-          r->net_fields, r->own_prec != 0};
+static ModelEntry gen_entry_of(const GenModelRecord* r) {
+  return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
+          r->net_fields, r->own_prec != 0, r->n_weights};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -189,16 +177,17 @@ static const ModelEntry* entry(int model) {
 }
 
 // ---- dr_blackbox size sets (vihds_bb_variant.hpp) --------------------------------------------------------------------
-// The ICML sizes are built in (bb_check); any other set is looked for as libvihds_bb_<L>_<HS>_<HP>_<NLAT>.so in the
-// directory this library was loaded from, once per process.
+// Every size set is one BbVariant record: the ICML sizes' is built in (bb_builtin_variant), any other set's is looked for
+// as libvihds_bb_<L>_<HS>_<HP>_<NLAT>.so in the directory this library was loaded from, once per process.
 static bool bb_sizes_ok(const vihds_ode_problem* p) {
   return p->n_latent_states >= 0 && p->n_hidden_states > 0 && p->n_hidden_prec > 0 && p->n_const >= p->C + p->D &&
          p->C >= 0 && p->D >= 0;
 }
-static bool bb_builtin(const vihds_ode_problem* p) {
-  return bb_check(p->n_latent_states, p->n_hidden_states, p->n_hidden_prec, p->n_const, p->C, p->D) != 0;
-}
-static const BbVariant* bb_sized(const vihds_ode_problem* p) {
+static const BbVariant* bb_variant(const vihds_ode_problem* p) {
+  const BbVariant* builtin = bb_builtin_variant();  // (matched without the lock below: the training step's launches ask)
+  if (p->n_latent_states == builtin->L && p->n_hidden_states == builtin->HS && p->n_hidden_prec == builtin->HP &&
+      p->n_const == builtin->NLAT + p->C + p->D)
+    return builtin;
   static std::mutex mu;
   static std::map<std::tuple<int, int, int, int>, const BbVariant*> loaded;
   if (!bb_sizes_ok(p)) {
@@ -238,14 +227,24 @@ static const BbVariant* bb_sized(const vihds_ode_problem* p) {
   loaded[key] = v;
   return v;
 }
-// a side library's matrix-core kernels with the weight gradients on chip apply (same rule as its launch function)
-static bool bb_sized_gram(const BbVariant* v, const vihds_ode_problem* p) {
-  return v->mfma && p->kernel_variant != 1 && p->solver >= VIHDS_SOLVER_MODEULER && p->solver <= VIHDS_SOLVER_RK4;
+// the matrix-core kernels with the weight gradients on chip apply (the rule of the records' launch functions): kernel_variant
+// 0 (anything but 1) with a fixed-grid solver
+static bool bb_gram(const BbVariant* v, const vihds_ode_problem* p) {
+  return v->mfma && p->kernel_variant != 1 && p->solver <= VIHDS_SOLVER_RK4;
 }
-static long long bb_sized_dump_floats(const BbVariant* v, const vihds_ode_problem* p) {
+// the adjoint's aux buffer: the head -- the wavefronts' Gram partial sums, or the dump of every RHS evaluation -- and behind it
+// the tail (Delta, bias sums)
+static long long bb_dump_floats(const BbVariant* v, const vihds_ode_problem* p) {
   return (long long)(p->T - 1) * ode_stages(p->solver) * v->dump_fields * p->B * p->S;
 }
+static long long bb_head_floats(const BbVariant* v, const vihds_ode_problem* p) {
+  return bb_gram(v, p) ? v->gram_floats(p->B * p->S) : bb_dump_floats(v, p);
+}
+static long long bb_aux_floats(const BbVariant* v, const vihds_ode_problem* p) {
+  return bb_head_floats(v, p) + (long long)v->n_tail * p->B * p->S;
+}
 
+// (v: the size set's record of a dr_blackbox problem, null for any other model)
 static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& a, const BbVariant* v = nullptr) {
   if (p->B <= 0 || p->S <= 0 || p->T < 2) return fail(VIHDS_E_BADARG, "B, S must be > 0 and T >= 2");
   if ((long long)p->B * p->S > 0x7fffffffLL) return fail(VIHDS_E_BADARG, "B*S exceeds int range");
@@ -267,22 +266,24 @@ static void set_inputs(OdeArgs& a, const float* theta, const float* cond, const 
                        const float* obs, const float* weights) {
   a.theta = theta; a.cond = cond; a.dev1hot = dev1hot; a.times = times; a.obs = obs; a.weights = weights;
 }
-// A model with neural blocks gets its weights; dr_blackbox is built in or has its side library (then *sized) and gets cond and
-// dev1hot; the precision network of any other model has at most 256 hidden units where the entry point's kernels hold that
+// A model with neural blocks gets its weights; dr_blackbox has the record of its size set (*bb) and gets cond and dev1hot;
+// the precision network of any other model has at most 256 hidden units where the entry point's kernels hold that
 // limit (limit_hidden).
 static int check_weights(const vihds_ode_problem* p, const ModelEntry* e, const float* weights, const float* cond,
-                         const float* dev1hot, bool limit_hidden, const BbVariant** sized) {
+                         const float* dev1hot, bool limit_hidden, const BbVariant** bb) {
   if (!e->has_weights()) return VIHDS_OK;
   if (!weights) return fail(VIHDS_E_BADARG, "model has neural blocks: weights must not be NULL");
   if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
     // (side libraries were built against the same headers: their kernels take every argument the built-in ones do)
-    if (!bb_builtin(p) && !(*sized = bb_sized(p))) return VIHDS_E_UNSUPPORTED;
+    if (!(*bb = bb_variant(p))) return VIHDS_E_UNSUPPORTED;
     if (!dev1hot || (p->C > 0 && !cond)) return fail(VIHDS_E_BADARG, "dr_blackbox needs cond and dev1hot");
   } else if (limit_hidden && p->n_hidden_prec > 256) {
     return fail(VIHDS_E_UNSUPPORTED, "neural precisions: at most 256 hidden units");
   }
   return VIHDS_OK;
 }
+// the launcher of a checked problem: the size set's for dr_blackbox (check_weights), the model's own otherwise
+static launch_fn launcher_of(const ModelEntry* e, const BbVariant* bb) { return bb ? bb->launch : e->launch; }
 static vihds_theta_opts theta_opts(const vihds_theta_opts* o) {
   vihds_theta_opts d = {nullptr, 0, nullptr, 0, 0, nullptr, nullptr};
   return o ? *o : d;
@@ -364,8 +365,7 @@ int vihds_model_register(const char* library_path) {
     dlclose(h);
     return fail(VIHDS_E_UNSUPPORTED, "vihds_model_register: too many registered models in this process");
   }
-  g_gen[k] = r;
-  g_gen_entries[k] = gen_entry_of(k, r, std::make_integer_sequence<int, VIHDS_GEN_MODEL_MAX>{});
+  g_gen_entries[k] = gen_entry_of(r);
   g_gen_count.store(k + 1, std::memory_order_release);  // (entry() sees the slot only once it is filled)
   by_path[resolved] = VIHDS_GEN_MODEL_BASE + k;
   return VIHDS_GEN_MODEL_BASE + k;
@@ -396,10 +396,9 @@ int vihds_model_n_weights(const vihds_ode_problem* p) {
   const ModelEntry* e = entry(p->model);
   if (!e) return VIHDS_E_UNSUPPORTED;
   if (!e->has_weights()) return 0;
-  if (is_registered(p->model)) return g_gen[p->model - VIHDS_GEN_MODEL_BASE]->n_weights(p->n_hidden_prec);
+  if (e->n_weights) return e->n_weights(p->n_hidden_prec);
   if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
-    if (bb_builtin(p)) return bb_n_weights(p->n_const);
-    const BbVariant* v = bb_sized(p);
+    const BbVariant* v = bb_variant(p);
     return v ? v->n_weights(p->n_const) : VIHDS_E_UNSUPPORTED;
   }
   const int n_in = e->n_states - 4 + 1;
@@ -471,17 +470,6 @@ int vihds_theta_ode_logp_grad(const vihds_ode_problem* p, int P, const int* kind
   return check_hip("vihds_theta_ode_logp_grad launch");
 }
 
-// *_precisions models whose adjoint can run one lane per state (vihds_relay_lanes.hpp) and then leaves the precision
-// network's weight gradients as one partial row per block: the number of species, 0 for any other model
-static int lane_model_species(int model) {
-  switch (model) {
-    case VIHDS_MODEL_RELAY_CONSTANT_PRECISIONS: return RlRelay::NSP;
-    case VIHDS_MODEL_DEGRADER_CONSTANT_PRECISIONS: return RlDegrader::NSP;
-    case VIHDS_MODEL_PRPR_CONSTANT_PRECISIONS: return RlPrpr::NSP;
-    case VIHDS_MODEL_AUTO_CONSTANT_PRECISIONS: return RlAuto::NSP;
-  }
-  return 0;
-}
 // (ABI 14 keeps the entry point: the time-fastest [B][S][N][T] layout belonged to kernel_variant 5 -- the time-parallel
 // kernels for relay / degrader / prpr / auto_constant, built in round 4, never faster than the lane kernels and removed in
 // round 6 -- so every kernel family now writes [T][N][B][S])
@@ -489,24 +477,24 @@ int vihds_ode_traj_layout(const vihds_ode_problem* p) {
   (void)p;
   return 0;
 }
+// a *_precisions model whose adjoint runs one lane per state (vihds_relay_lanes.hpp): it leaves the precision network's
+// weight gradients as one partial row per block and adds them up itself
 int vihds_ode_bwd_reduces_weights(const vihds_ode_problem* p) {
-  if (!p) return 0;
-  return lane_model_species(p->model) > 0 &&
+  const ModelEntry* e = p ? entry(p->model) : nullptr;
+  return e && e->lane_species > 0 && e->neural_prec &&
          relay_lanes_applicable(p->B * p->S, p->solver, p->kernel_variant, p->n_hidden_prec) ? 1 : 0;
 }
 
 long long vihds_ode_bwd_aux_floats(const vihds_ode_problem* p) {
   if (!p) return VIHDS_E_BADARG;
   if (p->model == VIHDS_MODEL_DR_BLACKBOX) {
-    if (bb_builtin(p)) return bb_aux_floats(p->B * p->S, p->T, p->solver, p->kernel_variant);
-    const BbVariant* v = bb_sized(p);
-    if (v && bb_sized_gram(v, p)) return v->gram_floats(p->B * p->S) + (long long)v->n_tail * p->B * p->S;
-    return v ? bb_sized_dump_floats(v, p) + (long long)v->n_tail * p->B * p->S : VIHDS_E_UNSUPPORTED;
+    const BbVariant* v = bb_variant(p);
+    return v ? bb_aux_floats(v, p) : VIHDS_E_UNSUPPORTED;
   }
   const ModelEntry* e = entry(p->model);
   if (!e) return VIHDS_E_UNSUPPORTED;
   if (!e->has_weights()) return 0;
-  if (vihds_ode_bwd_reduces_weights(p)) return relay_lanes_aux_floats(p->B * p->S, lane_model_species(p->model));  // one partial row per block
+  if (vihds_ode_bwd_reduces_weights(p)) return relay_lanes_aux_floats(p->B * p->S, e->lane_species);  // one partial row per block
   // white-box + neural precisions: [8 + NIN][E][n], NIN = 1 + core states (optional: see vihds_ode_bwd)
   const long long stages = ode_stages(p->solver);
   // (a registered model with networks of its own: their fields first -- vihds_gen_model.hpp; one with a precision map of its
@@ -514,56 +502,42 @@ long long vihds_ode_bwd_aux_floats(const vihds_ode_problem* p) {
   const long long prec_fields = e->neural_prec ? 8 + e->n_states - 4 + 1 + (p->n_hidden_prec > 0 ? 2 * p->n_hidden_prec : 0) : 0;
   return (e->net_fields + prec_fields) * (p->T - 1) * stages * p->B * p->S;
 }
-int vihds_blackbox_dump_fields(void) { return bb_dump_fields(); }
+int vihds_blackbox_dump_fields(void) { return bb_builtin_variant()->dump_fields; }
 int vihds_problem_dump_fields(const vihds_ode_problem* p) {
   if (!p || p->model != VIHDS_MODEL_DR_BLACKBOX) return VIHDS_E_BADARG;
-  if (bb_builtin(p)) return bb_dump_fields();
-  const BbVariant* v = bb_sized(p);
+  const BbVariant* v = bb_variant(p);
   return v ? v->dump_fields : VIHDS_E_UNSUPPORTED;
 }
 int vihds_problem_n_states(const vihds_ode_problem* p) {
   if (!p) return VIHDS_E_BADARG;
-  if (p->model == VIHDS_MODEL_DR_BLACKBOX && !bb_builtin(p)) {
-    const BbVariant* v = bb_sized(p);
-    return v ? v->n_states : VIHDS_E_UNSUPPORTED;
-  }
-  return vihds_model_n_states(p->model);
+  if (p->model != VIHDS_MODEL_DR_BLACKBOX) return vihds_model_n_states(p->model);
+  const BbVariant* v = bb_variant(p);
+  return v ? v->n_states : VIHDS_E_UNSUPPORTED;
 }
 int vihds_problem_n_slots(const vihds_ode_problem* p) {
   if (!p) return VIHDS_E_BADARG;
-  if (p->model == VIHDS_MODEL_DR_BLACKBOX && !bb_builtin(p)) {
-    const BbVariant* v = bb_sized(p);
-    return v ? v->n_slots : VIHDS_E_UNSUPPORTED;
-  }
-  return vihds_model_n_slots(p->model);
+  if (p->model != VIHDS_MODEL_DR_BLACKBOX) return vihds_model_n_slots(p->model);
+  const BbVariant* v = bb_variant(p);
+  return v ? v->n_slots : VIHDS_E_UNSUPPORTED;
 }
 int vihds_blackbox_gram_on_chip(const vihds_ode_problem* p) {
   if (!p || p->model != VIHDS_MODEL_DR_BLACKBOX) return 0;
-  if (!bb_builtin(p)) {
-    const BbVariant* v = bb_sized(p);
-    return v && bb_sized_gram(v, p) ? 1 : 0;
-  }
-  return bb_gram_on_chip(p->solver, p->kernel_variant);
+  const BbVariant* v = bb_variant(p);
+  return v && bb_gram(v, p) ? 1 : 0;
 }
 long long vihds_blackbox_tail_offset_floats(const vihds_ode_problem* p) {
   if (!p || p->model != VIHDS_MODEL_DR_BLACKBOX) return VIHDS_E_BADARG;
-  if (!bb_builtin(p)) {
-    const BbVariant* v = bb_sized(p);
-    if (v && bb_sized_gram(v, p)) return v->gram_floats(p->B * p->S);
-    return v ? bb_sized_dump_floats(v, p) : VIHDS_E_UNSUPPORTED;
-  }
-  return bb_tail_offset_floats(p->B * p->S, p->T, p->solver, p->kernel_variant);
+  const BbVariant* v = bb_variant(p);
+  return v ? bb_head_floats(v, p) : VIHDS_E_UNSUPPORTED;
 }
 int vihds_blackbox_gram_reduce(const vihds_ode_problem* p, const float* aux, float* g_weights, void* stream) {
   if (!p || !aux || !g_weights) return fail(VIHDS_E_BADARG, "null argument");
-  if (p->model != VIHDS_MODEL_DR_BLACKBOX || !vihds_blackbox_gram_on_chip(p))
+  const BbVariant* v = p->model == VIHDS_MODEL_DR_BLACKBOX ? bb_variant(p) : nullptr;
+  if (!v || !bb_gram(v, p))
     return fail(VIHDS_E_BADARG, "vihds_blackbox_gram_reduce: not an on-chip Gram problem (see vihds_blackbox_gram_on_chip)");
-  const ModelEntry* e = entry(p->model);
-  const BbVariant* v = bb_builtin(p) ? nullptr : bb_sized(p);
   OdeArgs a;
-  if (int rc = build_args(p, e, a, v)) return rc;
-  if (v) v->gram_reduce(a, aux, g_weights, (hipStream_t)stream);
-  else bb_gram_reduce(a, aux, g_weights, (hipStream_t)stream);
+  if (int rc = build_args(p, entry(p->model), a, v)) return rc;
+  v->gram_reduce(a, aux, g_weights, (hipStream_t)stream);
   return check_hip("vihds_blackbox_gram_reduce launch");
 }
 
@@ -571,18 +545,18 @@ int vihds_ode_fwd(const vihds_ode_problem* p, const float* theta, const float* c
                   const float* times, const float* obs, const float* weights, float* traj, float* xpred, float* logp,
                   void* stream) {
   if (!p || !theta || !times) return fail(VIHDS_E_BADARG, "null problem/theta/times");
-  const BbVariant* sized = nullptr;
+  const BbVariant* bb = nullptr;
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (logp && !obs) return fail(VIHDS_E_BADARG, "logp requested without obs");
-  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &bb)) return rc;
   OdeArgs a;
-  int rc = build_args(p, e, a, sized);
+  int rc = build_args(p, e, a, bb);
   if (rc) return rc;
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
   set_inputs(a, theta, cond, dev1hot, times, obs, weights);
   a.traj = traj; a.xpred = xpred; a.logp = logp;
-  rc = (sized ? sized->launch : e->launch)(false, p->solver, a, (hipStream_t)stream, LaunchMode{});
+  rc = launcher_of(e, bb)(false, p->solver, a, (hipStream_t)stream, LaunchMode{});
   if (rc) return fail(rc, "unknown solver");
   return check_hip("vihds_ode_fwd launch");
 }
@@ -660,8 +634,8 @@ int vihds_ode_fwd_summaries(const vihds_ode_problem* p, const float* theta, cons
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (p->model == VIHDS_MODEL_DR_BLACKBOX || solver_is_adaptive(p->solver))
     return VIHDS_E_UNSUPPORTED;  // (dr_blackbox and the adaptive pairs keep vihds_ode_fwd + vihds_iw_summaries_states)
-  const BbVariant* sized = nullptr;  // (stays null: dr_blackbox left above)
-  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
+  const BbVariant* bb = nullptr;  // (stays null: dr_blackbox left above)
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &bb)) return rc;
   OdeArgs a;
   int rc = build_args(p, e, a, nullptr);
   if (rc) return rc;
@@ -676,6 +650,7 @@ int vihds_ode_fwd_summaries(const vihds_ode_problem* p, const float* theta, cons
   sa.nvp = (ns + 12 + 3) & ~3;
   LaunchMode mode;
   mode.summ = &sa;
+  if (is_registered(p->model)) return VIHDS_E_UNSUPPORTED;  // (a generated library has no kernels of this pass)
   rc = e->launch(false, p->solver, a, (hipStream_t)stream, mode);
   if (rc) return rc == VIHDS_E_UNSUPPORTED ? rc : fail(rc, "vihds_ode_fwd_summaries: launch refused");
   const long long items = (long long)p->B * p->T * sa.nvp;
@@ -702,21 +677,21 @@ int vihds_ode_adaptive_grid(const vihds_ode_problem* p, const float* theta, cons
     return fail(VIHDS_E_BADARG, "null argument");
   if (!solver_is_adaptive(p->solver)) return fail(VIHDS_E_BADARG, "vihds_ode_adaptive_grid needs an adaptive solver id");
   if (!(rtol > 0.f) || !(atol > 0.f)) return fail(VIHDS_E_BADARG, "rtol and atol must be positive");
-  const BbVariant* sized = nullptr;
+  const BbVariant* bb = nullptr;
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
-  if (int rc = check_weights(p, e, weights, cond, dev1hot, false, &sized)) return rc;
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, false, &bb)) return rc;
   for (int k = 1; k < p->T; ++k)
     if (!(times_host[k] > times_host[k - 1])) return fail(VIHDS_E_BADARG, "output times must increase");
   OdeArgs a;
-  int rc = build_args(p, e, a, sized);
+  int rc = build_args(p, e, a, bb);
   if (rc) return rc;
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
   set_inputs(a, theta, cond, dev1hot, nullptr, nullptr, weights);  // (the times stay on the host: ctl)
   AdaptiveCtl ctl = {times_host, rtol, atol, workspace, grid_host, max_grid, index_host, 0};
   LaunchMode mode;
   mode.grid = &ctl;
-  rc = (sized ? sized->launch : e->launch)(false, p->solver, a, (hipStream_t)stream, mode);
+  rc = launcher_of(e, bb)(false, p->solver, a, (hipStream_t)stream, mode);
   if (rc == VIHDS_E_UNSUPPORTED) return fail(rc, "the accepted grid does not fit max_grid points");
   if (rc == VIHDS_E_BADARG) return fail(rc, "step size underflow or non-finite error estimate");
   if (rc) return fail(rc, "adaptive step controller failed");
@@ -792,18 +767,24 @@ int vihds_ode_adaptive_bwd(const vihds_ode_problem* p, const float* theta, const
                               g_traj, g_theta, stream);
 }
 
-int vihds_ode_bwd(const vihds_ode_problem* p, const float* theta, const float* cond, const float* dev1hot,
-                  const float* times, const float* obs, const float* weights, const float* traj, const float* g_traj,
-                  const float* g_xpred, const float* g_logp, float* g_theta, float* g_weights, float* aux,
-                  void* stream) {
-  if (!p || !theta || !times || !traj || !g_theta) return fail(VIHDS_E_BADARG, "null problem/theta/times/traj/g_theta");
-  const BbVariant* sized = nullptr;
+// The adjoint's log-likelihood gradient: the caller's (vihds_ode_bwd: g_traj, g_xpred, g_logp), or formed in the kernel from
+// the importance weights (vihds_ode_bwd_elbo: iw_logp set, with log_p and log_q)
+struct BwdGrads {
+  const float *g_traj, *g_xpred, *g_logp, *iw_logp, *iw_log_p, *iw_log_q;
+};
+// the two backward entry points behind their null checks
+static int ode_bwd(const char* launch_name, const vihds_ode_problem* p, const float* theta, const float* cond, const float* dev1hot,
+                   const float* times, const float* obs, const float* weights, const float* traj, const BwdGrads& g,
+                   float* g_theta, float* g_weights, float* aux, void* stream) {
+  const bool elbo = g.iw_logp != nullptr;
+  const BbVariant* bb = nullptr;
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
   if (!obs) return fail(VIHDS_E_BADARG, "null obs");
-  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
+  if (elbo && solver_is_adaptive(p->solver)) return fail(VIHDS_E_UNSUPPORTED, "vihds_ode_bwd_elbo: fixed-grid solvers");
+  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &bb)) return rc;
   OdeArgs a;
-  int rc = build_args(p, e, a, sized);
+  int rc = build_args(p, e, a, bb);
   if (rc) return rc;
   set_inputs(a, theta, cond, dev1hot, times, obs, weights);
   a.g_weights = g_weights; a.aux = aux;
@@ -812,10 +793,20 @@ int vihds_ode_bwd(const vihds_ode_problem* p, const float* theta, const float* c
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && !aux) return fail(VIHDS_E_BADARG, "dr_blackbox backward needs the aux buffer");
   if (e->n_net_weights > 0 && g_weights && !aux)
     return fail(VIHDS_E_BADARG, "a generated model with networks forms its weight gradient from the aux dump: pass aux (vihds_ode_bwd_aux_floats)");
-  a.traj_in = traj; a.g_traj = g_traj; a.g_xpred = g_xpred; a.g_logp = g_logp; a.g_theta = g_theta;
-  rc = (sized ? sized->launch : e->launch)(true, p->solver, a, (hipStream_t)stream, LaunchMode{});
+  a.traj_in = traj; a.g_traj = g.g_traj; a.g_xpred = g.g_xpred; a.g_logp = g.g_logp; a.g_theta = g_theta;
+  a.iw_logp = g.iw_logp; a.iw_log_p = g.iw_log_p; a.iw_log_q = g.iw_log_q;
+  if (elbo) a.logp_grad_broadcast = 1;
+  rc = launcher_of(e, bb)(true, p->solver, a, (hipStream_t)stream, LaunchMode{});
   if (rc) return fail(rc, "unknown solver");
-  return check_hip("vihds_ode_bwd launch");
+  return check_hip(launch_name);
+}
+int vihds_ode_bwd(const vihds_ode_problem* p, const float* theta, const float* cond, const float* dev1hot,
+                  const float* times, const float* obs, const float* weights, const float* traj, const float* g_traj,
+                  const float* g_xpred, const float* g_logp, float* g_theta, float* g_weights, float* aux,
+                  void* stream) {
+  if (!p || !theta || !times || !traj || !g_theta) return fail(VIHDS_E_BADARG, "null problem/theta/times/traj/g_theta");
+  return ode_bwd("vihds_ode_bwd launch", p, theta, cond, dev1hot, times, obs, weights, traj,
+                 {g_traj, g_xpred, g_logp, nullptr, nullptr, nullptr}, g_theta, g_weights, aux, stream);
 }
 
 int vihds_rng_advance(unsigned int* rng, void* stream) {
@@ -833,10 +824,8 @@ int vihds_theta_ode_fwd(const vihds_ode_problem* p, int P, const int* kind, cons
     return fail(VIHDS_E_BADARG, "null argument");
   const ModelEntry* e = entry(p->model);
   if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
-  const bool lane_family = p->model == VIHDS_MODEL_AUTO_CONSTANT || p->model == VIHDS_MODEL_PRPR_CONSTANT ||
-                           p->model == VIHDS_MODEL_RELAY_CONSTANT || p->model == VIHDS_MODEL_DEGRADER_CONSTANT ||
-                           lane_model_species(p->model) > 0;
-  if (!lane_family && !(p->model == VIHDS_MODEL_DR_BLACKBOX && bb_builtin(p)))
+  // (the lane kernels and the built-in dr_blackbox sizes carry it: a side library does not)
+  if (e->lane_species == 0 && !(p->model == VIHDS_MODEL_DR_BLACKBOX && bb_variant(p) == bb_builtin_variant()))
     return fail(VIHDS_E_UNSUPPORTED, "vihds_theta_ode_fwd: no sampling stage in this model's forward kernels");
   if (logp && !obs) return fail(VIHDS_E_BADARG, "logp requested without obs");
   if (P <= 0 || P > p->n_rows) return fail(VIHDS_E_BADARG, "P out of range");
@@ -874,26 +863,8 @@ int vihds_ode_bwd_elbo(const vihds_ode_problem* p, const float* theta, const flo
                        const float* log_p, const float* log_q, float* g_theta, float* g_weights, float* aux,
                        void* stream) {
   if (!p || !theta || !times || !traj || !g_theta || !logp) return fail(VIHDS_E_BADARG, "null problem/theta/times/traj/g_theta/logp");
-  const BbVariant* sized = nullptr;
-  const ModelEntry* e = entry(p->model);
-  if (!e) return fail(VIHDS_E_UNSUPPORTED, "model not supported by this build");
-  if (!obs) return fail(VIHDS_E_BADARG, "null obs");
-  if (solver_is_adaptive(p->solver)) return fail(VIHDS_E_UNSUPPORTED, "vihds_ode_bwd_elbo: fixed-grid solvers");
-  if (int rc = check_weights(p, e, weights, cond, dev1hot, true, &sized)) return rc;
-  OdeArgs a;
-  int rc = build_args(p, e, a, sized);
-  if (rc) return rc;
-  set_inputs(a, theta, cond, dev1hot, times, obs, weights);
-  a.g_weights = g_weights; a.aux = aux;
-  if (p->model == VIHDS_MODEL_DR_BLACKBOX && !aux) return fail(VIHDS_E_BADARG, "dr_blackbox backward needs the aux buffer");
-  if (e->n_net_weights > 0 && g_weights && !aux)
-    return fail(VIHDS_E_BADARG, "a generated model with networks forms its weight gradient from the aux dump: pass aux (vihds_ode_bwd_aux_floats)");
-  a.traj_in = traj; a.g_theta = g_theta;
-  a.iw_logp = logp; a.iw_log_p = log_p; a.iw_log_q = log_q;
-  a.logp_grad_broadcast = 1;
-  rc = (sized ? sized->launch : e->launch)(true, p->solver, a, (hipStream_t)stream, LaunchMode{});
-  if (rc) return fail(rc, "unknown solver");
-  return check_hip("vihds_ode_bwd_elbo launch");
+  return ode_bwd("vihds_ode_bwd_elbo launch", p, theta, cond, dev1hot, times, obs, weights, traj,
+                 {nullptr, nullptr, nullptr, logp, log_p, log_q}, g_theta, g_weights, aux, stream);
 }
 
 int vihds_theta_fwd(int P, int B, int S, const int* kind, const float* q_mu, const float* q_prec, const float* p_mu,

@@ -5,7 +5,8 @@
 //   libvihds_bb_<L>_<HS>_<HP>_<NLAT>.so      (make -C vi-hds_amd/csrc blackbox L=.. HS=.. HP=.. NLAT=..)
 // next to it, holding the thread-per-trajectory kernels (vihds_blackbox.hpp) of every solver and -- for up to three latent
 // species and 64 / 32 hidden units -- the matrix-core kernels (vihds_blackbox_split.hpp), loaded on first use
-// (vihds_api.hip: bb_lookup).  NLAT = n_z + n_x + n_y (the kernels only see the total: z, x, y are consecutive slots).
+// (vihds_api.hip: bb_variant, which resolves the ICML sizes to the same kind of record -- ode_dr_blackbox.hip:
+// bb_builtin_variant).  NLAT = n_z + n_x + n_y (the kernels only see the total: z, x, y are consecutive slots).
 #pragma once
 #include <hip/hip_runtime.h>
 

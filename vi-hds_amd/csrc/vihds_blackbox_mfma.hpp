@@ -244,13 +244,6 @@ struct BbMfma : BbMfmaT<Blackbox<2, 25, 20, 5, 5, 2>, 2, 25, 20, 12> {};
 // vihds_gram_blocks: `kernel_variant 4`.  The cooperating-wavefront kernels of vihds_blackbox_split.hpp superseded them at every
 // size; removed in round 6.)
 
-// floats of aux ahead of the tail (Delta, bias sums): the per-evaluation dump, or the wavefronts' Gram partial sums
-__host__ __device__ inline size_t bb_mfma_head_floats(int n, int T, int solver, bool gram) {
-  using BB = BbMfma::BB;
-  if (gram) return BbMfma::gram_floats(n);
-  return (size_t)(T - 1) * BB::stages(solver) * BB::NF * n;
-}
-
 // sums the wavefronts' partial tiles in a fixed order (deterministic) and scatters them into the flat weight gradient.
 // One block = 64 elements of a tile x 16 interleaved slices of the wavefronts (as one thread per element walking all
 // 450 wavefronts -- 113 dependent rounds of loads -- this took 39 us).
