@@ -22,6 +22,8 @@ struct GenSel<true> {
 };
 static_assert(!(VIHDS_GEN_NEURAL != 0 && own_prec<VIHDS_GEN_CORE>::value),
               "a model with a precision map of its own does not take NeuralPrecisions");
+static_assert(!(VIHDS_GEN_NEURAL != 0 && own_lik<VIHDS_GEN_CORE>::value),
+              "a model with an observation log density of its own does not take NeuralPrecisions");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds

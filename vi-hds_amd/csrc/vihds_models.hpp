@@ -917,6 +917,19 @@ struct traj_rows {
   static constexpr int value = M::N + (own_prec<M>::value ? 4 : 0);
 };
 
+// A core generated with an observation log density of its own (vihds/modelgen.py) declares OWN_LIK = true and two members that
+// run once per time point, in place of the Gaussian term -0.5 (log 2 pi - log pr + pr e^2):
+//   loglik(xp, ob, pr, p, ll)                        ll[4] = the log densities of the four signals at this time point
+//   loglik_vjp(xp, ob, pr, p, llb, xpb, prb, pb)     xpb += (d ll/d xp)^T llb ; prb += (d ll/d pr)^T llb ; pb += (d ll/d p)^T llb
+// xp are the predicted signals (the model's own map or the fixed one), ob the observations (data: no adjoint), pr the
+// precisions: the constant slots, or the values of the model's own precision map.  The adjoint kernel runs loglik_vjp first,
+// then precision_vjp (own_prec), then the observation map's adjoint.  False for every hand-written model and for WithPrec<>
+// (which declares no OWN_LIK and does not forward its core's).
+template <class M, class = void>
+struct own_lik : std::false_type {};
+template <class M>
+struct own_lik<M, std::void_t<decltype(M::OWN_LIK)>> : std::bool_constant<M::OWN_LIK> {};
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};

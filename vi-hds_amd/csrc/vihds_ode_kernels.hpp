@@ -343,6 +343,7 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   constexpr int N = M::N;
   constexpr int NT = traj_rows<M>::value;  // rows per time point of traj: N, + 4 precision rows of a model with its own map
   constexpr bool OWN_PREC = own_prec<M>::value;
+  constexpr bool OWN_LIK = own_lik<M>::value;  // the log density is the model's own member (vihds_models.hpp)
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations
   const float* wts = stage_weights<M>(a, wlds);
@@ -373,7 +374,8 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
 
   float lc[4], lp[4];
   VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
-    if constexpr (OWN_PREC) lc[j] = 0.f;  // (unused: the own branch of the time loop forms the term from its values)
+    if constexpr (OWN_LIK) lc[j] = 0.f;  // (unused: the model's own log density takes the precisions as they are)
+    else if constexpr (OWN_PREC) lc[j] = 0.f;  // (unused: the own branch of the time loop forms the term from its values)
     else lc[j] = M::NEURAL_PREC ? 0.f : LOG2PI_F - logf(prec[j]);
     lp[j] = 0.f;
   }
@@ -414,7 +416,31 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     if (a.xpred) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.xpred[((size_t)k * 4 + j) * n + i] = xp[j];
     }
-    if constexpr (OWN_PREC) {
+    if constexpr (OWN_LIK) {
+      // an observation log density of the model's own (a branch of its own: every other model's code stays what it was).  Its
+      // precisions are the constant slots, or the values of the model's own map, which are stored as in the branch below
+      float prl[4];
+      if constexpr (OWN_PREC) {
+        M::precision(y, xp, p, prl);
+        if (a.traj) {
+          if (nt_traj) {
+            VIHDS_UNROLL for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(prl[j], &a.traj[((size_t)k * NT + N + j) * n + i]);
+          } else {
+            VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.traj[((size_t)k * NT + N + j) * n + i] = prl[j];
+          }
+        }
+      } else {
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) prl[j] = prec[j];
+      }
+      if (a.logp) {
+        float ll[4];
+        M::loglik(xp, obc, prl, p, ll);
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+          lp[j] += ll[j];
+          obc[j] = obn[j];
+        }
+      }
+    } else if constexpr (OWN_PREC) {
       // a precision map of the model's own: evaluated on the species and the predicted signals of this time point, stored
       // as the four rows behind the species (where a *_precisions model keeps its precision states); the log-likelihood
       // term is the neural branch's.  (A branch of its own: every other model's code stays what it was.)
@@ -609,6 +635,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   constexpr int N = M::N;
   constexpr int NT = traj_rows<M>::value;  // rows per time point of traj_in / g_traj (the precision rows of traj_in are never read)
   constexpr bool OWN_PREC = own_prec<M>::value;
+  constexpr bool OWN_LIK = own_lik<M>::value;  // the log density's adjoint is the model's own member (vihds_models.hpp)
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   const float* wts = stage_weights<M>(a, wlds);
   const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -662,7 +689,37 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     float xp[4], xpb[4];
     if constexpr (M::OBS == OBS_CUSTOM) M::observe(y, p, xp);
     else observe<M::OBS>(y, xp);
-    if constexpr (OWN_PREC) {
+    if constexpr (OWN_LIK) {
+      // an observation log density of the model's own (a branch of its own: every other model's code stays what it was).
+      // Three adjoints in this order: the log density's (seeded with glp; it adds into xpb, prb4 and pb), then the precision
+      // map's where the model has one (prb4 plus what arrives for the precision rows of the trajectory; into lam, xpb and
+      // pb) -- constant precisions take prb4 into precb --, then the observation map's below, which pulls xpb back.  The
+      // parameter parts join pb ahead of prepare_vjp.  Forward values are recomputed; nothing is buffered
+      float prl[4], llb[4], prb4[4];
+      if constexpr (OWN_PREC) {
+        M::precision(y, xp, p, prl);
+      } else {
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) prl[j] = prec[j];
+      }
+      VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+        llb[j] = glp[j];
+        xpb[j] = 0.f;
+        prb4[j] = 0.f;
+      }
+      // (no log-likelihood gradient arrives -- the host-driven adaptive route integrates on placeholder observations and forms
+      // the log-likelihood itself: the adjoint is skipped, uniformly over the launch, not multiplied by zero: a density that is
+      // singular at the placeholder would give 0 * inf)
+      if (a.g_logp || a.iw_logp) M::loglik_vjp(xp, obk, prl, p, llb, xpb, prb4, pb);
+      VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+        if constexpr (OWN_PREC) {
+          if (a.g_traj) prb4[j] += a.g_traj[((size_t)k * NT + N + j) * n + i];
+        } else {
+          precb[j] += prb4[j];
+        }
+        if (a.g_xpred) xpb[j] += a.g_xpred[((size_t)k * 4 + j) * n + i];
+      }
+      if constexpr (OWN_PREC) M::precision_vjp(y, xp, p, prb4, lam, xpb, pb);
+    } else if constexpr (OWN_PREC) {
       // a precision map of the model's own (a branch of its own: every other model's code stays what it was).  The forward
       // values are recomputed, never read from traj_in; prb is the log-likelihood's part plus what arrives for the four
       // precision rows of the trajectory.  The precision adjoint goes into lam, xpb and pb BEFORE the observation map's
@@ -807,10 +864,11 @@ namespace vihds {
 
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
-  if constexpr (net_fields<M>::value > 0 || M::OBS == OBS_CUSTOM || own_prec<M>::value) {
+  if constexpr (net_fields<M>::value > 0 || M::OBS == OBS_CUSTOM || own_prec<M>::value || own_lik<M>::value) {
     // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers;
     // a model with an observation map of its own: the one-pass summaries know the fixed maps only; a model with a precision
-    // map of its own: both families know the constant precisions and the precision states only)
+    // map of its own: both families know the constant precisions and the precision states only; a model with a log density
+    // of its own: both families form the Gaussian term)
     if (mode.summ || mode.dev) return VIHDS_E_UNSUPPORTED;
   } else {
     if (const SummArgs* sm = mode.summ) {  // vihds_ode_fwd_summaries: the evaluation's second forward pass

@@ -23,6 +23,8 @@ A model is one subclass of GeneratedOdeModel (the plugin surface of the referenc
             return [y[0], p.gain * y[0] * y[1] + p.bg, ...]
         def precision(self, y, x, p, c):   # optional; the precisions of the four signals (then no self.precisions above)
             return [1.0 / (p.s0_od * p.s0_od + pow(p.s1_od * x[0], 2.0)), ...]
+        def log_likelihood(self, x, obs, pr, p, c):   # optional; the four log densities of one time point
+            return [C + 0.5 * log(pr[j]) - 0.5 * (NU + 1.0) * log(1.0 + pr[j] * (x[j] - obs[j]) * (x[j] - obs[j]) / NU) ...]
 
 `c` holds the treatments after clamp(exp(cond) - 1, 1e-12, 1e6) (the c[] contract of csrc/vihds_models.hpp).  The three
 functions use + - * / (unary minus, Python numbers) and the operations of this module: exp, log, pow, sigmoid, tanh and
@@ -63,6 +65,24 @@ non-positive precision gives NaN exactly as a non-positive constant precision do
 1 / (s0^2 + (s1 x)^2), exp(.), or clamp(., 1e-6, 1e6) where the expression could reach 0).  torch_precision evaluates the
 definition with torch ops.
 
+The observation likelihood.  Without `log_likelihood` the density that joins prediction, observation and precision is the
+kernels' Gaussian, -0.5 (log 2 pi - log pr + pr (x - obs)^2) per signal and time point.  A model that defines
+log_likelihood(x, obs, pr, p, c) -> list of 4 owns it (likelihood_kind "custom", otherwise "gaussian"): the method is traced
+into the same DAG (the operations and limits of observe: no t, no network calls, no species) with two more leaf kinds -- the
+four observations of the time point, which are data and get no adjoint, and the four precisions (the constant slots, or the
+values of the model's own precision) -- and returns the four per-signal log densities of that time point; the kernel sums
+them over time into logp[j].  It is emitted with its reverse-mode adjoint as the members loglik / loglik_vjp (time-loop
+helpers; the adjoint adds into the predicted signals', the precisions' and the parameters' adjoints).  The adjoint kernel runs
+the three adjoints in the order likelihood, precision, observation map.  A parameter may be read by log_likelihood only (a
+mixing weight, a width); a treatment it reads is copied by prepare.  Normalising constants are Python numbers (math.lgamma).
+It composes with constant precisions, an own precision, an own observe and networks in rhs, not with NeuralPrecisions; a
+subclass returns to the Gaussian with `log_likelihood = None`.
+torch_log_likelihood evaluates the definition with torch ops; the host paths that restate the Gaussian (the host-driven
+adaptive route, training.log_prob_observations) take it for such a model.  WHAT STAYS GAUSSIAN: everything downstream of
+logp is untouched, and the evaluation summaries (iw_variance, iw_predict_std) keep reading the precision rows as inverse
+variances.  For a Student-t with nu degrees of freedom and scale 1 / sqrt(pr) the variance is nu / (nu - 2) / pr (nu > 2), so
+those two summaries understate the spread by that factor unless the model's precision already carries it.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -80,6 +100,7 @@ scalars through the constant address space, and the weight gradient comes from a
 contracted by vihds_gram_blocks -- fixed summation order, no atomics (ops.decoder_weight_grads).
 """
 import hashlib
+import inspect
 import math
 import os
 import sys
@@ -140,6 +161,10 @@ def _class_networks(cls):
 # expression DAG
 # ---------------------------------------------------------------------------------------------------------------------
 _LEAVES = ("const", "th", "c", "y", "p", "t", "seed", "x")  # (x: the predicted signals precision() reads)
+# ... and the two leaf kinds only log_likelihood() reads: the observations of the time point (forward only: data have no
+# adjoint) and the precisions (the constant slots or the values of the model's own precision map)
+_LEAVES += ("ob", "pr")
+_NO_ADJOINT = ("ob",)
 _COMMUTATIVE = ("add", "mul")
 
 
@@ -403,7 +428,7 @@ def vjp(g, outputs, seeds):
     net_adj = {}  # "net" node id -> {output index: adjoint}
 
     def acc(node, contrib):
-        if node.op == "const":
+        if node.op == "const" or node.op in _NO_ADJOINT:
             return
         adj[node.id] = g.make("add", (adj[node.id], contrib)) if node.id in adj else contrib
 
@@ -585,8 +610,8 @@ class _Networks(object):
 
 
 class Trace(object):
-    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe and precision) traced into one
-    Graph."""
+    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe, precision and log_likelihood)
+    traced into one Graph."""
 
     def __init__(self, cls):
         inst = cls.__new__(cls)  # (the functions are methods; nothing of nn.Module is touched by them)
@@ -598,7 +623,7 @@ class Trace(object):
         def call(k, name, net, inputs):
             if self._phase != "rhs":
                 raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only (not in "
-                                           "prepare, initial_state, observe or precision)" % (name, self._phase))
+                                           "prepare, initial_state, observe or precision, nor in log_likelihood)" % (name, self._phase))
             if name in self._called:
                 raise ModelDefinitionError("network '%s' is called twice: a network may be called at most once per rhs "
                                            "evaluation (its adjoint dump has one slot per evaluation)" % name)
@@ -651,8 +676,20 @@ class Trace(object):
                 raise ModelDefinitionError("%s.precision must return a list of 4 entries (the precisions of the OD, RFP, YFP "
                                            "and CFP signals)" % cls.__name__)
             self.prec = [g._arg(x) for x in pr]
-        used = {n.val for n in _topo(self.dy + (self.obs or []) + (self.prec or [])) if n.op == "p"}
-        self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe or by precision)
+        # log_likelihood (optional) sees the four predicted signals, the four observations and the four precisions of the time
+        # point, the effective parameters and the treatments: no species, no t
+        self.lik = None
+        definition = getattr(cls, "_likelihood_def", None)
+        if definition is not None:
+            self._phase = "log_likelihood"
+            ll = definition(inst, [g.leaf("x", j) for j in range(4)], [g.leaf("ob", j) for j in range(4)],
+                            [g.leaf("pr", j) for j in range(4)], p, _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
+            if not isinstance(ll, (list, tuple)) or len(ll) != 4:
+                raise ModelDefinitionError("%s.log_likelihood must return a list of 4 entries (the log densities of the OD, "
+                                           "RFP, YFP and CFP signals at one time point)" % cls.__name__)
+            self.lik = [g._arg(x) for x in ll]
+        used = {n.val for n in _topo(self.dy + (self.obs or []) + (self.prec or []) + (self.lik or [])) if n.op == "p"}
+        self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
         self.c_slot = {NPU + q: NPU + k for k, q in enumerate(self.c_in_rhs)}
@@ -820,6 +857,9 @@ def generate_source(cls, neural=False):
     if neural and tr.prec is not None:
         raise ModelDefinitionError("%s defines precision(self, y, x, p, c): a model with a precision map of its own does not "
                                    "take NeuralPrecisions" % cls.__name__)
+    if neural and tr.lik is not None:
+        raise ModelDefinitionError("%s defines log_likelihood(self, x, obs, pr, p, c): a model with a likelihood of its own "
+                                   "does not take NeuralPrecisions" % cls.__name__)
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -878,8 +918,20 @@ def generate_source(cls, neural=False):
         prec_vjp += [("xpb[%d]" % j, "+=", adj3[g.leaf("x", j).id]) for j in range(4) if g.leaf("x", j).id in adj3]
         prec_vjp += [("pb[%d]" % k, "+=", adj3[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj3]
 
+    # loglik / loglik_vjp (a model with a likelihood of its own): once per time point inside the time loop.  The adjoint adds
+    # into xpb (the predicted signals), prb (the precisions) and pb of the named effective parameters; the observations are
+    # data and get none
+    lik_decl = []
+    if tr.lik is not None:
+        llb = [g.leaf("seed", j) for j in range(4)]
+        adj4 = vjp(g, tr.lik, llb)
+        lik = [("ll[%d]" % j, "=", e) for j, e in enumerate(tr.lik)]
+        lik_vjp = [("xpb[%d]" % j, "+=", adj4[g.leaf("x", j).id]) for j in range(4) if g.leaf("x", j).id in adj4]
+        lik_vjp += [("prb[%d]" % j, "+=", adj4[g.leaf("pr", j).id]) for j in range(4) if g.leaf("pr", j).id in adj4]
+        lik_vjp += [("pb[%d]" % k, "+=", adj4[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj4]
+
     def body(assign, fast, seed, p_map=None):
-        names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp"}
+        names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp", "ob": "ob", "pr": "pr"}
         return "\n".join(_Emitter(fast, names, p_map).emit(assign))
 
     names = ", ".join('"%s"' % n for n in P)
@@ -929,6 +981,17 @@ def generate_source(cls, neural=False):
             body(prec_vjp, True, "prb", tr.c_slot),
             "  }",
         ]
+    if tr.lik is not None:
+        lik_decl = [
+            "  static constexpr bool OWN_LIK = true;  // the observation log density is this struct's: loglik / loglik_vjp",
+            "  __device__ static void loglik(const float* xp, const float* ob, const float* pr, const float* p, float* ll) {",
+            body(lik, True, "llb", tr.c_slot),
+            "  }",
+            "  __device__ static void loglik_vjp(const float* xp, const float* ob, const float* pr, const float* p, const float* llb,",
+            "                                    float* xpb, float* prb, float* pb) {",
+            body(lik_vjp, True, "llb", tr.c_slot),
+            "  }",
+        ]
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -967,7 +1030,7 @@ def generate_source(cls, neural=False):
     ] + vjp_sig + [
         body(rhs_vjp, True, "v", tr.c_slot),
         "  }",
-    ] + obs_decl + prec_decl + [
+    ] + obs_decl + prec_decl + lik_decl + [
         "};",
         "}  // namespace vihds",
         "#define VIHDS_GEN_CORE %s" % sname,
@@ -1086,6 +1149,8 @@ class GeneratedOdeModel(OdeModel):
     observe_kind = "default"
     _observe_def = None  # the class's own observation map observe(self, y, p, c), when it defines one (module docstring)
     _precision_def = None  # the class's own precision map precision(self, y, x, p, c), when it defines one (module docstring)
+    # the class's own observation log density log_likelihood(self, x, obs, pr, p, c), when it defines one (module docstring)
+    _likelihood_def = None
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
 
     def __init_subclass__(cls, **kw):
@@ -1119,6 +1184,22 @@ class GeneratedOdeModel(OdeModel):
             if not callable(definition):
                 raise ModelDefinitionError("%s.precision must be a function precision(self, y, x, p, c)" % cls.__name__)
             cls._precision_def = definition
+        if "log_likelihood" in cls.__dict__:
+            definition = cls.__dict__["log_likelihood"]
+            if definition is None:  # (a subclass returns to the kernels' Gaussian)
+                cls._likelihood_def = None
+            else:
+                # the five arguments the tracer passes, self in front; arguments with defaults and keyword-only helpers are the
+                # author's own
+                required = [q for q in inspect.signature(definition).parameters.values()
+                            if q.default is q.empty and q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD)] \
+                    if callable(definition) else None
+                if required is None or len(required) != 6:
+                    raise ModelDefinitionError("%s.log_likelihood must be a function log_likelihood(self, x, obs, pr, p, c): it "
+                                               "sees the predicted signals, the observations and the precisions of one time "
+                                               "point, the effective parameters and the treatments -- no t and no species (or "
+                                               "None in a subclass, for the Gaussian)" % cls.__name__)
+                cls._likelihood_def = definition
         if cls.__dict__.get("model_key") is None and getattr(cls, "_trace", None) is not None:
             cls._trace = Trace(cls)  # (a subclass that only changes __init__)
             return
@@ -1164,6 +1245,11 @@ class GeneratedOdeModel(OdeModel):
     def precision_kind(self):
         """'custom' for a model with a precision map of its own (module docstring), else 'fixed'."""
         return "custom" if type(self)._precision_def is not None else "fixed"
+
+    @property
+    def likelihood_kind(self):
+        """'custom' for a model with an observation log density of its own (module docstring), else 'gaussian'."""
+        return "custom" if type(self)._likelihood_def is not None else "gaussian"
 
     # the three functions of a model
     def prepare(self, th, c):
@@ -1292,6 +1378,42 @@ class GeneratedOdeModel(OdeModel):
             fixed.__dict__["observe_kind"] = cls.observe_kind
             x = OdeModel._observe_map(fixed, y)
         return _precision_torch(cls, inst, y, x, theta, cond)
+
+    @classmethod
+    def torch_log_likelihood(cls, x, obs, prec, theta, cond):
+        """The model's own observation log density with torch ops in x's dtype (the float64 reference of the generated loglik
+        / loglik_vjp): x [B,S,4,T] predicted signals, obs [B,4,T] observations, prec [B,S,4,T] precisions (anything that
+        broadcasts to it), theta {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as the data
+        holds it -> the per-signal log densities of every time point [B,S,4,T] (the kernels sum them over time)."""
+        if cls._likelihood_def is None:
+            raise ModelDefinitionError("%s defines no log_likelihood(self, x, obs, pr, p, c): its observation log density is "
+                                       "the Gaussian's" % cls.__name__)
+        ref = x[:, :, 0, :]
+        S = ref.shape[1]
+        inst = cls.__new__(cls)
+        tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
+        cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+        thn = _Named([(n, theta[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
+        over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
+        p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
+        ob = obs.to(ref.dtype)[:, None].expand(x.shape)
+        pr = prec.to(ref.dtype).expand(x.shape)
+        ll = cls._likelihood_def(inst, list(torch.unbind(x, dim=2)), list(torch.unbind(ob, dim=2)), list(torch.unbind(pr, dim=2)),
+                                 p, _Conditions([over_time(v) for v in cs]))
+        full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
+        return torch.stack([full(v) for v in ll], dim=2)
+
+    def _log_likelihood_map(self, x_predict, observations, precisions):
+        """The model's own log density on tensors of the host paths (the host-driven adaptive route, the plugin fallback of
+        Training.cost), with theta and the treatments of the last solve, as _observe_map: x_predict [B,S,4,T], observations
+        [B,4,T], precisions broadcastable to x_predict -> [B,S,4,T]."""
+        if self._last_inputs is None:
+            raise RuntimeError("%s.log_likelihood reads theta and the treatments of the last solve, and nothing has been "
+                               "solved yet" % type(self).__name__)
+        packed, row_of, cond = self._last_inputs
+        dev = x_predict.device
+        theta = {n: packed[row_of[n]].to(dev) for n in type(self).parameter_names}
+        return type(self).torch_log_likelihood(x_predict, observations.to(dev), precisions, theta, cond.to(dev))
 
     def _observe_map(self, x_sample):
         """OdeModel.observe on a tensor that is not the last solution: the model's own map (torch_observe) with theta and

@@ -80,6 +80,7 @@ class OdeModel(nn.Module):
     model_key = None
     observe_kind = "default"
     precision_kind = "fixed"  # "custom": a generated model's own precision map (vihds/modelgen.py)
+    likelihood_kind = "gaussian"  # "custom": a generated model's own observation log density (vihds/modelgen.py)
 
     def __init__(self, config):
         super(OdeModel, self).__init__()
@@ -320,8 +321,14 @@ class OdeModel(nn.Module):
             else:  # constant precisions: four theta rows broadcast over time (reference precisions.py:31-35)
                 rows = [row_of[n] for n in spec.slots[-4:]]
                 prec = packed[rows][None]
-            err = xpred - observations.to(dev).permute(2, 1, 0)[:, :, :, None]
-            logp = (-0.5 * (math.log(2 * math.pi) - torch.log(prec) + prec * err * err)).sum(0)  # training.py:24-44
+            if self.likelihood_kind == "custom":
+                # the model's own log density (vihds/modelgen.py) on the gathered rows, with theta and the treatments of this
+                # solve: [T,4,B,S] -> [B,S,4,T] and back, summed over time
+                ll = self._log_likelihood_map(xpred.permute(2, 3, 1, 0), observations, prec.permute(2, 3, 1, 0))
+                logp = ll.sum(3).permute(2, 0, 1)
+            else:
+                err = xpred - observations.to(dev).permute(2, 1, 0)[:, :, :, None]
+                logp = (-0.5 * (math.log(2 * math.pi) - torch.log(prec) + prec * err * err)).sum(0)  # training.py:24-44
         else:
             logp = torch.zeros((4,) + tuple(packed.shape[1:]), device=dev)
         self._last = DecodedSolution(traj, xpred, logp)

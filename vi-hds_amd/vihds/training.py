@@ -28,6 +28,10 @@ def log_prob_observations(model, x_predict, x_obs, precisions, use_laplace=False
     """reference training.py:24-33 -> [B,S,4]."""
     if use_laplace:
         raise NotImplementedError("Laplace likelihood is dead code in the reference (training.py:36-38)")
+    ode_model = getattr(getattr(model, "decoder", None), "ode_model", None)
+    if getattr(ode_model, "likelihood_kind", "gaussian") == "custom":
+        # a generated model's own log density (vihds/modelgen.py), with theta and the treatments of its last solve
+        return torch.sum(ode_model._log_likelihood_map(x_predict, x_obs, precisions), 3)
     return torch.sum(log_prob_gaussian(torch.unsqueeze(x_obs, 1), x_predict, precisions), 3)
 
 
