@@ -60,6 +60,28 @@ __device__ __forceinline__ float ftanh(float x) { return tanhf(x); }
 __device__ __forceinline__ float ftanh(float x) { return 1.f - 2.f * frcp(1.f + fexp(2.f * x)); }
 #endif
 
+// Piecewise terms of generated models (vihds/modelgen.py: where, minimum, maximum, abs, sqrt).  All of them are selects
+// (v_cndmask_b32 on a v_cmp mask: full rate, no branch), so a right-hand side that uses them stays straight-line code.
+__device__ __forceinline__ float fsel(bool c, float a, float b) { return c ? a : b; }
+// torch.minimum / torch.maximum: a NaN in either argument is the result (v_min_f32 / v_max_f32 and fminf / fmaxf return
+// the other argument instead, which would hide a trajectory that has gone NaN from the non-finite-loss exit)
+__device__ __forceinline__ float fmin_nan(float a, float b) { return (a < b || a != a) ? a : b; }
+__device__ __forceinline__ float fmax_nan(float a, float b) { return (a > b || a != a) ? a : b; }
+// their backward, as the weight of the FIRST argument (the second's is the same call with the arguments swapped): 1 where
+// it is selected, 1/2 at a tie, 0 where the other one is -- torch's where(a == b, g / 2, g).masked_fill(a > b, 0)
+__device__ __forceinline__ float min_pass(float a, float b) { return a > b ? 0.f : (a == b ? 0.5f : 1.f); }
+__device__ __forceinline__ float max_pass(float a, float b) { return a < b ? 0.f : (a == b ? 0.5f : 1.f); }
+// torch.sign: 0 at 0 (and at NaN)
+__device__ __forceinline__ float fsign(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+// sqrt on the time-loop path: v_sqrt_f32 (1 ulp, one quarter-rate instruction) instead of the correctly rounded sqrtf,
+// which scales denormal inputs and adds a two-fma correction step around the same instruction.  Inputs below 2^-126 give
+// 0 (absolute error < 1.1e-19); negative inputs give NaN, -0 gives -0, +inf gives +inf, as sqrtf does.
+#ifdef VIHDS_PRECISE_MATH
+__device__ __forceinline__ float fsqrt(float x) { return sqrtf(x); }
+#else
+__device__ __forceinline__ float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
+#endif
+
 // d/da a^n and d/dn a^n, matching autograd of torch.pow(tensor, tensor)
 __device__ __forceinline__ void pow_vjp(float a, float n, float an, float g, float& ab, float& nb) {
   ab += g * n * powf(a, n - 1.f);

@@ -26,9 +26,10 @@ A model is one subclass of GeneratedOdeModel (the plugin surface of the referenc
         def log_likelihood(self, x, obs, pr, p, c):   # optional; the four log densities of one time point
             return [C + 0.5 * log(pr[j]) - 0.5 * (NU + 1.0) * log(1.0 + pr[j] * (x[j] - obs[j]) * (x[j] - obs[j]) / NU) ...]
 
-`c` holds the treatments after clamp(exp(cond) - 1, 1e-12, 1e6) (the c[] contract of csrc/vihds_models.hpp).  The three
-functions use + - * / (unary minus, Python numbers) and the operations of this module: exp, log, pow, sigmoid, tanh and
-clamp (constant bounds).  Each of them dispatches on its arguments:
+`c` holds the treatments after clamp(exp(cond) - 1, 1e-12, 1e6) (the c[] contract of csrc/vihds_models.hpp).  The
+functions use + - * / (unary minus, Python numbers) and the operations of this module: exp, log, pow, sigmoid, tanh, clamp
+(constant bounds), and the piecewise ones: where(cond, a, b), minimum(a, b), maximum(a, b), abs(x) (Python's abs() too),
+sqrt(x), erf(x), erfc(x).  Each of them dispatches on its arguments:
   - symbols (when the class is defined): an expression DAG, from which the model struct of vihds_models.hpp and its
     reverse-mode adjoint are generated as HIP C++ (generate_source);
   - torch tensors: torch ops, eagerly -- the same definition is then a float64 PyTorch right-hand side (torch_problem).
@@ -40,6 +41,26 @@ The adjoint of each operation is torch autograd's formula, with one exception ke
 pow(a, n) is g * a^n * log(a) everywhere, as csrc pow_vjp computes it for the built-in models.  At a = 0 that is NaN
 (0 * -inf) where autograd masks it to 0 (pow_backward_exponent, base 0 and exponent >= 0); clamp the base away from 0
 (as the reference models do: clamp(K, 1e-12, 1) * c) when the exponent is a parameter.
+
+Piecewise terms.  A comparison a < b, a <= b, a > b, a >= b between model quantities and / or Python numbers gives a
+CONDITION; conditions combine with & | ~ (not with and / or / not, which are Python control flow and raise, as `if` does) and
+select in where(cond, a, b).  A condition is not a number -- arithmetic on one raises; write where(cond, 1.0, 0.0) for an
+indicator -- and == / != stay refused.  A Python bool as cond selects when the model is traced.  Conditions may read any leaf
+(t in rhs: where(t < p.tau, 0.0, p.dose) is an input switched on at tau; the observations in log_likelihood: a censored
+density).  minimum / maximum take two quantities or numbers; a symbolic bound for clamp is minimum(maximum(x, lo), hi).  The
+forward semantics are torch's, NaN included: a NaN operand makes every comparison false, minimum / maximum return the NaN (so
+a trajectory that has gone NaN stays NaN and the non-finite-loss exit sees it), sqrt of a negative value is NaN.  All of them
+are emitted as selects, never as branches.  The adjoints are torch autograd's: where passes the gradient to the branch taken
+BY A SELECT (the other branch gets exactly 0, whatever it holds); minimum / maximum pass it to the selected argument, half to
+each at a tie; abs: g sign(x), sign(0) = 0; sqrt: g / (2 sqrt(x)), infinite at 0; erf: g 2 / sqrt(pi) exp(-x^2), erfc its
+negative.  They are allowed in prepare, rhs (network inputs included), observe, precision and log_likelihood; initial_state
+stays affine in theta (a where, minimum, maximum, abs, sqrt of a parameter or treatment there is refused).  Two traps:
+  - the double-where idiom.  where(x > 0, log(x), 0) has the right value, but its adjoint forms 0 / x in the branch not
+    taken: 0 * inf = NaN at x = 0 (and log's value there may be -inf or NaN, which the select hides only in the forward
+    pass).  Make the argument safe with an inner where: where(x > 0, log(where(x > 0, x, 1.0)), 0) -- as with torch.where.
+  - a switch time or a threshold gets no gradient through the condition itself: conditions carry no adjoint, so in
+    where(t < p.tau, 0.0, p.dose) the gradient reaches dose, never tau (the true derivative with respect to a switch time is
+    a jump term no fixed-grid scheme resolves); a parameter that is only ever compared is not learned from the data.
 
 The observation map.  Without `observe` the four signals are one of the kernels' fixed maps of the species by position
 (observe_kind: "default" [y0, y0 y1, y0 (y2 + y4), y0 (y3 + y5)], "direct" [y0, y0 y1, y0 y2, y0 y3]).  A model that defines
@@ -114,7 +135,7 @@ from vihds.ode import OdeModel
 MAX_STATES = 32  # ODE states of a generated model (all of them live in registers of one thread)
 OBSERVE_KINDS = {"default": ("OBS_DEFAULT", 6), "direct": ("OBS_DIRECT", 4)}  # kernel enum, species observe() reads
 OBSERVE_CUSTOM = "custom"  # observe_kind of a class that defines observe(y, p, c): the struct's own map, OBS_CUSTOM
-OPERATIONS = ("exp", "log", "pow", "sigmoid", "tanh", "clamp")
+OPERATIONS = ("exp", "log", "pow", "sigmoid", "tanh", "clamp", "where", "minimum", "maximum", "abs", "sqrt", "erf", "erfc")
 # networks of a generated model (the hidden layer is walked one unit at a time, the inputs and outputs live in registers)
 MAX_NETWORKS, MAX_NET_INPUTS, MAX_NET_HIDDEN, MAX_NET_OUTPUTS = 2, 16, 32, 8
 NET_ACTIVATIONS = ("relu", "tanh")
@@ -166,13 +187,33 @@ _LEAVES = ("const", "th", "c", "y", "p", "t", "seed", "x")  # (x: the predicted 
 _LEAVES += ("ob", "pr")
 _NO_ADJOINT = ("ob",)
 _COMMUTATIVE = ("add", "mul")
+# conditions: a < b and a <= b (a > b and a >= b are the same two with the arguments swapped), their combinations and the
+# constant ones that folding leaves.  A condition is no number: it selects in where(), has no adjoint and no arithmetic
+_COMPARISONS = ("lt", "le")
+_CONDITIONS = _COMPARISONS + ("and", "or", "not", "cconst")
+# nodes only vjp() builds: the backward weights of clamp, minimum / maximum and abs -- piecewise constant, no adjoint
+_PASS_NODES = ("cpass", "minpass", "maxpass", "sign")
+_TWO_OVER_SQRT_PI = 2.0 / math.sqrt(math.pi)
 
 
 def _control_flow(*_args, **_kw):
     raise ModelDefinitionError(
         "a generated model's functions are traced once, symbolically: Python control flow on a model quantity (if, "
-        "and/or, comparisons, bool(), float(), abs(), math.*) is not possible -- write it with the operations %s "
-        "(clamp for bounds)" % ", ".join(OPERATIONS))
+        "and/or/not, bool(), float(), math.*) is not possible -- a comparison a < b gives a condition: combine conditions "
+        "with & | ~ and select with where(cond, a, b); the operations are %s (clamp, minimum, maximum for bounds)"
+        % ", ".join(OPERATIONS))
+
+
+def _no_equality(*_args, **_kw):
+    raise ModelDefinitionError(
+        "== and != on a model quantity are not available to generated models: equality of floating-point values is not a "
+        "condition to build a model on (conditions are a < b, a <= b, a > b, a >= b, combined with & | ~)")
+
+
+def _condition_arithmetic(*_args, **_kw):
+    raise ModelDefinitionError(
+        "arithmetic on a condition: a condition (a < b, c1 & c2, ...) is not a number -- it combines with & | ~ and selects "
+        "with where(cond, a, b); write where(cond, 1.0, 0.0) for an indicator")
 
 
 class Sym(object):
@@ -219,8 +260,36 @@ class Sym(object):
     def __rpow__(self, o):
         return self.g.make("pow", (o, self))
 
-    __bool__ = __float__ = __int__ = __index__ = __abs__ = _control_flow
-    __lt__ = __le__ = __gt__ = __ge__ = __eq__ = __ne__ = _control_flow
+    def __abs__(self):
+        return self.g.make("abs", (self,))
+
+    def __lt__(self, o):
+        return self.g.compare("lt", self, o)
+
+    def __le__(self, o):
+        return self.g.compare("le", self, o)
+
+    def __gt__(self, o):
+        return self.g.compare("lt", o, self)
+
+    def __ge__(self, o):
+        return self.g.compare("le", o, self)
+
+    def __and__(self, o):
+        return self.g.logic("and", (self, o))
+
+    __rand__ = __and__
+
+    def __or__(self, o):
+        return self.g.logic("or", (self, o))
+
+    __ror__ = __or__
+
+    def __invert__(self):
+        return self.g.logic("not", (self,))
+
+    __bool__ = __float__ = __int__ = __index__ = _control_flow
+    __eq__ = __ne__ = _no_equality
     __hash__ = object.__hash__
 
     @classmethod
@@ -230,6 +299,20 @@ class Sym(object):
 
     def __repr__(self):
         return "Sym(%s#%d)" % (self.op, self.id)
+
+
+class Cond(Sym):
+    """A condition node: a comparison of two quantities or a combination of conditions.  It selects in where(cond, a, b); it
+    is no number (arithmetic and comparisons on it raise), and bool() of it -- if, and, or, not -- is Python control flow."""
+
+    __slots__ = ()
+
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = _condition_arithmetic
+    __neg__ = __pos__ = __pow__ = __rpow__ = __abs__ = _condition_arithmetic
+    __lt__ = __le__ = __gt__ = __ge__ = _condition_arithmetic
+
+    def __repr__(self):
+        return "Cond(%s#%d)" % (self.op, self.id)
 
 
 def _fold(op, a, b=None, val=None):
@@ -248,12 +331,24 @@ def _fold(op, a, b=None, val=None):
         if op == "tanh": return float(np.tanh(a))
         if op == "clamp": return float(min(max(a, val[0]), val[1])) if a == a else float(a)
         if op == "cpass": return 1.0 if val[0] <= a <= val[1] else 0.0
+        if op == "lt": return bool(a < np.float64(b))  # (a NaN operand makes every comparison false)
+        if op == "le": return bool(a <= np.float64(b))
+        if op == "minimum": return float(np.minimum(a, np.float64(b)))  # (np.minimum / np.maximum propagate NaN, as torch's)
+        if op == "maximum": return float(np.maximum(a, np.float64(b)))
+        if op == "minpass": return 0.0 if a > b else (0.5 if a == b else 1.0)
+        if op == "maxpass": return 0.0 if a < b else (0.5 if a == b else 1.0)
+        if op == "abs": return float(np.abs(a))
+        if op == "sign": return 1.0 if a > 0.0 else (-1.0 if a < 0.0 else 0.0)
+        if op == "sqrt": return float(np.sqrt(a))
+        if op == "erf": return math.erf(a)
+        if op == "erfc": return math.erfc(a)
     raise AssertionError(op)
 
 
 class Graph(object):
     """Hash-consed expression DAG: building a node that exists returns that node (common-subexpression elimination);
-    operations on constants are folded; x+0, x*1, x*0, x/1, -(-x), pow(x, 1) simplify."""
+    operations on constants are folded; x+0, x*1, x*0, x/1, -(-x), pow(x, 1), where(c, a, a), minimum(a, a) simplify.
+    Conditions (compare, logic) are nodes of their own class, Cond; where() selects between two values by one."""
 
     def __init__(self, networks=()):
         self.nodes = []
@@ -264,7 +359,7 @@ class Graph(object):
         key = (op, tuple(a.id for a in args), val)
         n = self._table.get(key)
         if n is None:
-            n = Sym(self, op, tuple(args), val, len(self.nodes))
+            n = (Cond if op in _CONDITIONS else Sym)(self, op, tuple(args), val, len(self.nodes))
             self.nodes.append(n)
             self._table[key] = n
         return n
@@ -277,6 +372,8 @@ class Graph(object):
         return self._intern(kind, (), index)
 
     def _arg(self, a):
+        if isinstance(a, Cond):
+            _condition_arithmetic()
         if isinstance(a, Sym):
             if a.g is not self:
                 raise ModelDefinitionError("a model quantity from another trace was used")
@@ -290,6 +387,50 @@ class Graph(object):
         """Network k applied to `inputs`: the call node and one node per output (never folded or simplified)."""
         call = self._intern("net", tuple(self._arg(a) for a in inputs), k)
         return [self._intern("netout", (call,), j) for j in range(self.networks[k].sizes[2])]
+
+    def compare(self, op, a, b):
+        """The condition a < b ("lt") or a <= b ("le"); constant operands fold to a constant condition."""
+        a, b = self._arg(a), self._arg(b)
+        if a.op == "const" and b.op == "const":
+            return self._intern("cconst", (), _fold(op, a.val, b.val))
+        return self._intern(op, (a, b), None)
+
+    def _condition(self, c, what):
+        if isinstance(c, Cond):
+            if c.g is not self:
+                raise ModelDefinitionError("a model quantity from another trace was used")
+            return c
+        if isinstance(c, (bool, np.bool_)):
+            return self._intern("cconst", (), bool(c))
+        raise ModelDefinitionError("%s takes conditions (a < b, a <= b, a > b, a >= b and their combinations with & | ~) or a "
+                                   "Python bool, not %s" % (what, "a model quantity" if isinstance(c, Sym) else type(c).__name__))
+
+    def logic(self, op, args):
+        """c1 & c2 ("and"), c1 | c2 ("or"), ~c ("not"); constant conditions fold, c & c, c | c and ~~c simplify."""
+        args = tuple(self._condition(c, {"and": "&", "or": "|", "not": "~"}[op]) for c in args)
+        if op == "not":
+            if args[0].op == "cconst": return self._intern("cconst", (), not args[0].val)
+            if args[0].op == "not": return args[0].args[0]
+            return self._intern(op, args, None)
+        absorbing = op == "or"  # (the constant that decides the result: True for |, False for &)
+        for k in (0, 1):
+            if args[k].op == "cconst":
+                return args[k] if args[k].val == absorbing else args[1 - k]
+        if args[0] is args[1]:
+            return args[0]
+        if args[0].id > args[1].id:
+            args = (args[1], args[0])
+        return self._intern(op, args, None)
+
+    def where(self, c, a, b):
+        """a where the condition holds, else b (a select: the value not taken may be anything, NaN and inf included)."""
+        c = self._condition(c, "where(cond, a, b): cond")
+        a, b = self._arg(a), self._arg(b)
+        if c.op == "cconst":
+            return a if c.val else b
+        if a is b:
+            return a
+        return self._intern("where", (c, a, b), None)
 
     def make(self, op, args, val=None):
         args = tuple(self._arg(a) for a in args)
@@ -316,6 +457,8 @@ class Graph(object):
             if args[0].op == "neg": return args[0].args[0]
         elif op == "pow":
             if one(args[1]): return args[0]
+        elif op in ("minimum", "maximum"):
+            if args[0] is args[1]: return args[0]
         if op in _COMMUTATIVE and args[0].id > args[1].id:
             args = (args[1], args[0])
         return self._intern(op, args, val)
@@ -384,10 +527,79 @@ def clamp(x, lo, hi):
     return min(max(x, lo), hi)
 
 
+def _like(v, other):
+    """A Python number as a tensor beside `other` (torch.minimum / maximum / where want tensors)."""
+    return v if isinstance(v, torch.Tensor) else torch.as_tensor(float(v), dtype=other.dtype, device=other.device)
+
+
+def where(cond, a, b):
+    """a where cond holds, else b.  cond is a condition (a comparison of model quantities / numbers, combined with & | ~) or
+    a Python bool, which selects when the model is traced."""
+    g = _sym_of((cond, a, b))
+    if g: return g.where(cond, a, b)
+    if isinstance(cond, (bool, np.bool_)):
+        return a if cond else b
+    if not (isinstance(cond, torch.Tensor) and cond.dtype == torch.bool):
+        raise ModelDefinitionError("where(cond, a, b): cond must be a condition (a < b, ... combined with & | ~) or a Python "
+                                   "bool, not %s" % type(cond).__name__)
+    ta, tb = isinstance(a, torch.Tensor), isinstance(b, torch.Tensor)
+    if ta or tb:
+        return torch.where(cond, _like(a, b if tb else a), _like(b, a if ta else b))
+    # two Python numbers: nothing says which float type the caller computes in.  Numbers that float32 holds exactly (0.0 and
+    # 1.0 of a switch) stay float32, which every tensor they meet promotes; any other pair is kept in float64
+    a, b = _number(a, "where's value"), _number(b, "where's value")
+    exact = all(float(np.float32(v)) == v or v != v for v in (a, b))
+    dtype = torch.float32 if exact else torch.float64
+    return torch.where(cond, torch.tensor(a, dtype=dtype, device=cond.device), torch.tensor(b, dtype=dtype, device=cond.device))
+
+
+def minimum(a, b):
+    g = _sym_of((a, b))
+    if g: return g.make("minimum", (a, b))
+    if _tensor_of((a, b)):
+        ref = a if isinstance(a, torch.Tensor) else b
+        return torch.minimum(_like(a, ref), _like(b, ref))
+    return _fold("minimum", a, b)
+
+
+def maximum(a, b):
+    g = _sym_of((a, b))
+    if g: return g.make("maximum", (a, b))
+    if _tensor_of((a, b)):
+        ref = a if isinstance(a, torch.Tensor) else b
+        return torch.maximum(_like(a, ref), _like(b, ref))
+    return _fold("maximum", a, b)
+
+
+def abs(x):  # noqa: A001  (the operation's name in the model namespace; Python's abs() on a model quantity comes here too)
+    g = _sym_of((x,))
+    if g: return g.make("abs", (x,))
+    return torch.abs(x) if _tensor_of((x,)) else math.fabs(x)
+
+
+def sqrt(x):
+    g = _sym_of((x,))
+    if g: return g.make("sqrt", (x,))
+    return torch.sqrt(x) if _tensor_of((x,)) else _fold("sqrt", x)  # (NaN below 0, as the kernels and torch)
+
+
+def erf(x):
+    g = _sym_of((x,))
+    if g: return g.make("erf", (x,))
+    return torch.erf(x) if _tensor_of((x,)) else math.erf(x)
+
+
+def erfc(x):
+    g = _sym_of((x,))
+    if g: return g.make("erfc", (x,))
+    return torch.erfc(x) if _tensor_of((x,)) else math.erfc(x)
+
+
 class _Namespace(object):
     """`op.exp(x)` ...: the operations as one object; any other name is refused with the list."""
 
     exp, log, pow, sigmoid, tanh, clamp = (staticmethod(f) for f in (exp, log, pow, sigmoid, tanh, clamp))
+    where, minimum, maximum, abs, sqrt, erf, erfc = (staticmethod(f) for f in (where, minimum, maximum, abs, sqrt, erf, erfc))
 
     def __getattr__(self, name):
         raise ModelDefinitionError("operation '%s' is not available to generated models (available: + - * / and %s)"
@@ -478,7 +690,22 @@ def vjp(g, outputs, seeds):
             acc(a[0], gb * (1.0 - n * n))
         elif n.op == "clamp":
             acc(a[0], gb * g.make("cpass", (a[0],), n.val))
-        elif n.op == "cpass":
+        elif n.op == "where":  # a select of the adjoint, never a product with a mask: what the other branch holds is not touched
+            zero = g.const(0.0)
+            acc(a[1], g.where(a[0], gb, zero)); acc(a[2], g.where(a[0], zero, gb))
+        elif n.op == "minimum":  # g to the selected argument, g / 2 to each at a tie
+            acc(a[0], gb * g.make("minpass", (a[0], a[1]))); acc(a[1], gb * g.make("minpass", (a[1], a[0])))
+        elif n.op == "maximum":
+            acc(a[0], gb * g.make("maxpass", (a[0], a[1]))); acc(a[1], gb * g.make("maxpass", (a[1], a[0])))
+        elif n.op == "abs":  # g sign(x), sign(0) = 0
+            acc(a[0], gb * g.make("sign", (a[0],)))
+        elif n.op == "sqrt":  # g / (2 sqrt(x)): infinite at 0, as torch's
+            acc(a[0], gb / (2.0 * n))
+        elif n.op == "erf":
+            acc(a[0], gb * (_TWO_OVER_SQRT_PI * g.make("exp", (-(a[0] * a[0]),))))
+        elif n.op == "erfc":
+            acc(a[0], -(gb * (_TWO_OVER_SQRT_PI * g.make("exp", (-(a[0] * a[0]),)))))
+        elif n.op in _PASS_NODES:
             pass  # piecewise constant
         else:
             raise AssertionError(n.op)
@@ -531,6 +758,21 @@ def evaluate(outputs, env):
         elif n.op == "tanh": v = torch.tanh(a[0])
         elif n.op == "clamp": v = torch.clamp(a[0], n.val[0], n.val[1])
         elif n.op == "cpass": v = ((a[0] >= n.val[0]) & (a[0] <= n.val[1])).to(a[0].dtype)
+        elif n.op == "lt": v = a[0] < a[1]
+        elif n.op == "le": v = a[0] <= a[1]
+        elif n.op == "and": v = a[0] & a[1]
+        elif n.op == "or": v = a[0] | a[1]
+        elif n.op == "not": v = ~a[0]
+        elif n.op == "where": v = torch.where(a[0], a[1], a[2])
+        elif n.op == "minimum": v = torch.minimum(a[0], a[1])
+        elif n.op == "maximum": v = torch.maximum(a[0], a[1])
+        elif n.op == "minpass": v = torch.where(a[0] == a[1], 0.5, 1.0).masked_fill(a[0] > a[1], 0.0).to(a[0].dtype)
+        elif n.op == "maxpass": v = torch.where(a[0] == a[1], 0.5, 1.0).masked_fill(a[0] < a[1], 0.0).to(a[0].dtype)
+        elif n.op == "abs": v = torch.abs(a[0])
+        elif n.op == "sign": v = torch.sign(a[0])
+        elif n.op == "sqrt": v = torch.sqrt(a[0])
+        elif n.op == "erf": v = torch.erf(a[0])
+        elif n.op == "erfc": v = torch.erfc(a[0])
         elif n.op == "net": v = net_forward_ref(n.g.networks[n.val], env[("w", n.val)], stack(a))[2]
         elif n.op == "netout": v = a[0][..., n.val]
         elif n.op == "netbwd":
@@ -714,8 +956,10 @@ def _lit(v):
 
 
 class _Emitter(object):
-    """Straight-line C++ for some DAG outputs: one `const float` per operation node.  fast=True is the time loop (frcp,
-    fdiv, fexp, sigmoid_f, ftanh); fast=False is prepare / init (IEEE division, expf, tanhf); both use powf / logf."""
+    """Straight-line C++ for some DAG outputs: one `const float` per operation node (`const bool` per condition).  fast=True
+    is the time loop (frcp, fdiv, fexp, sigmoid_f, ftanh, fsqrt); fast=False is prepare / init (IEEE division, expf, tanhf,
+    sqrtf); both use powf / logf / erff / erfcf and the selects of vihds_models.hpp (fsel, fmin_nan, fmax_nan and their
+    pass weights, fsign): no branch is ever emitted."""
 
     def __init__(self, fast, leaf_names, p_map=None):
         self.fast, self.leaf_names, self.p_map = fast, leaf_names, p_map or {}
@@ -748,6 +992,22 @@ class _Emitter(object):
         if n.op == "tanh": return ("ftanh(%s)" if f else "tanhf(%s)") % a[0]
         if n.op == "clamp": return "clampf(%s, %s, %s)" % (a[0], _lit(n.val[0]), _lit(n.val[1]))
         if n.op == "cpass": return "clamp_pass(%s, %s, %s)" % (a[0], _lit(n.val[0]), _lit(n.val[1]))
+        # conditions are bools, where is a select (one v_cndmask_b32): straight-line code, no branch
+        if n.op == "lt": return "%s < %s" % tuple(a)
+        if n.op == "le": return "%s <= %s" % tuple(a)
+        if n.op == "and": return "%s && %s" % tuple(a)
+        if n.op == "or": return "%s || %s" % tuple(a)
+        if n.op == "not": return "!%s" % a[0]
+        if n.op == "where": return "fsel(%s, %s, %s)" % tuple(a)
+        if n.op == "minimum": return "fmin_nan(%s, %s)" % tuple(a)
+        if n.op == "maximum": return "fmax_nan(%s, %s)" % tuple(a)
+        if n.op == "minpass": return "min_pass(%s, %s)" % tuple(a)
+        if n.op == "maxpass": return "max_pass(%s, %s)" % tuple(a)
+        if n.op == "abs": return "fabsf(%s)" % a[0]
+        if n.op == "sign": return "fsign(%s)" % a[0]
+        if n.op == "sqrt": return ("fsqrt(%s)" if f else "sqrtf(%s)") % a[0]
+        if n.op == "erf": return "erff(%s)" % a[0]
+        if n.op == "erfc": return "erfcf(%s)" % a[0]
         raise AssertionError(n.op)
 
     def emit(self, assignments):
@@ -759,7 +1019,7 @@ class _Emitter(object):
                 self._emit_net(n)
                 continue
             name = "v%d" % len(self.names)
-            self.lines.append("    const float %s = %s;" % (name, self.expr(n)))
+            self.lines.append("    const %s %s = %s;" % ("bool" if isinstance(n, Cond) else "float", name, self.expr(n)))
             self.names[n.id] = name
         for lhs, how, n in assignments:
             self.lines.append("    %s %s %s;" % (lhs, how, self.ref(n)))
@@ -887,7 +1147,9 @@ def generate_source(cls, neural=False):
             raise ModelDefinitionError(
                 "%s.initial_state: the derivative with respect to '%s' depends on theta or the treatments; the kernels' "
                 "init_vjp sees the state adjoint only, so the initial state must be affine in the parameters with constant "
-                "coefficients (move nonlinear maps into prepare... or into a parameter of its own)" % (cls.__name__, P[s]))
+                "coefficients (move nonlinear maps into prepare... or into a parameter of its own; where, minimum, maximum, "
+                "abs and sqrt of a parameter or a treatment are such maps: a condition on theta is refused here too)"
+                % (cls.__name__, P[s]))
         init_vjp.append(("thb[%d]" % s, "+=", e))
     # rhs / rhs_vjp
     rhs = [("dy[%d]" % j, "=", e) for j, e in enumerate(tr.dy)]
