@@ -123,6 +123,7 @@ contracted by vihds_gram_blocks -- fixed summation order, no atomics (ops.decode
 import hashlib
 import inspect
 import math
+import operator
 import os
 import sys
 
@@ -135,7 +136,6 @@ from vihds.ode import OdeModel
 MAX_STATES = 32  # ODE states of a generated model (all of them live in registers of one thread)
 OBSERVE_KINDS = {"default": ("OBS_DEFAULT", 6), "direct": ("OBS_DIRECT", 4)}  # kernel enum, species observe() reads
 OBSERVE_CUSTOM = "custom"  # observe_kind of a class that defines observe(y, p, c): the struct's own map, OBS_CUSTOM
-OPERATIONS = ("exp", "log", "pow", "sigmoid", "tanh", "clamp", "where", "minimum", "maximum", "abs", "sqrt", "erf", "erfc")
 # networks of a generated model (the hidden layer is walked one unit at a time, the inputs and outputs live in registers)
 MAX_NETWORKS, MAX_NET_INPUTS, MAX_NET_HIDDEN, MAX_NET_OUTPUTS = 2, 16, 32, 8
 NET_ACTIVATIONS = ("relu", "tanh")
@@ -186,14 +186,6 @@ _LEAVES = ("const", "th", "c", "y", "p", "t", "seed", "x")  # (x: the predicted 
 # adjoint) and the precisions (the constant slots or the values of the model's own precision map)
 _LEAVES += ("ob", "pr")
 _NO_ADJOINT = ("ob",)
-_COMMUTATIVE = ("add", "mul")
-# conditions: a < b and a <= b (a > b and a >= b are the same two with the arguments swapped), their combinations and the
-# constant ones that folding leaves.  A condition is no number: it selects in where(), has no adjoint and no arithmetic
-_COMPARISONS = ("lt", "le")
-_CONDITIONS = _COMPARISONS + ("and", "or", "not", "cconst")
-# nodes only vjp() builds: the backward weights of clamp, minimum / maximum and abs -- piecewise constant, no adjoint
-_PASS_NODES = ("cpass", "minpass", "maxpass", "sign")
-_TWO_OVER_SQRT_PI = 2.0 / math.sqrt(math.pi)
 
 
 def _control_flow(*_args, **_kw):
@@ -315,34 +307,136 @@ class Cond(Sym):
         return "Cond(%s#%d)" % (self.op, self.id)
 
 
-def _fold(op, a, b=None, val=None):
-    """Constant folding in float64 (IEEE semantics: inf / NaN instead of exceptions)."""
+# ---------------------------------------------------------------------------------------------------------------------
+# the operation table
+# ---------------------------------------------------------------------------------------------------------------------
+class Operation(object):
+    """One operation of the DAG and everything that is known about it.  TO ADD AN OPERATION, ADD ONE RECORD to OP_TABLE:
+    constant folding, the torch evaluation, the emitter, reverse mode, the module-level function and `op.<name>` all look
+    it up here.
+      arity      number of argument nodes
+      val        True when the node carries constants in `val` (clamp's bounds); fold, torch and c then take them last
+      fold       the operation on numpy float64 scalars (bools for the arguments that are conditions)
+      torch      the operation on tensors (evaluate, and the module-level function on tensors)
+      number     the module-level function on Python numbers, where it is not the fold (math.exp raises where the fold
+                 gives inf)
+      c          the C spelling, or (time loop, prepare / init) where the fast helpers of vihds_models.hpp differ from the
+                 IEEE ones; %s per argument, then per constant of val
+      peephole   (node, argument texts, fast) -> a cheaper spelling for this node, or None
+      adjoint    (g, node, args, gb, acc): calls acc(argument, contribution) for each argument IN TURN -- vjp's output
+                 depends on the order in which nodes are created, so a contribution is built right before it is
+                 accumulated (a tuple's entries are evaluated left to right); None for the kinds without one
+      kind       "value"; "condition" (a bool: selects in where, no adjoint, no arithmetic); "pass" (a node only vjp
+                 builds -- the backward weight of clamp, minimum / maximum, abs: piecewise constant, no adjoint)
+      public     a name of the model language: listed in OPERATIONS, a module attribute and an attribute of `op`"""
+
+    __slots__ = ("name", "arity", "val", "fold", "torch", "number", "c", "peephole", "adjoint", "kind", "commutative", "public")
+
+    def __init__(self, name, arity, fold, torch, c, adjoint=None, kind="value", val=False, commutative=False, public=False,
+                 number=None, peephole=None):
+        self.name, self.arity, self.fold, self.torch, self.adjoint, self.kind = name, arity, fold, torch, adjoint, kind
+        self.val, self.commutative, self.public, self.peephole = val, commutative, public, peephole
+        self.c = (c, c) if isinstance(c, str) else c
+        self.number = number or (lambda *a: _fold(name, *a))
+
+
+def _is_const(n, v):
+    return n.op == "const" and n.val == v
+
+
+def _like(v, other):
+    """A Python number as a tensor beside `other` (torch.minimum / maximum / where want tensors)."""
+    return v if isinstance(v, torch.Tensor) else torch.as_tensor(float(v), dtype=other.dtype, device=other.device)
+
+
+def _both_tensors(f):
+    return lambda a, b: f(_like(a, b if isinstance(b, torch.Tensor) else a), _like(b, a if isinstance(a, torch.Tensor) else b))
+
+
+def _pass_weight(a, b, beaten):
+    """The backward weight of minimum / maximum for a: 0 where b wins (`beaten`), 1/2 at a tie, else 1 (NaN included)."""
+    return torch.where(a == b, 0.5, 1.0).masked_fill(beaten, 0.0).to(a.dtype)
+
+
+_TWO_OVER_SQRT_PI = 2.0 / math.sqrt(math.pi)
+_O = Operation
+OP_TABLE = {r.name: r for r in (
+    _O("add", 2, operator.add, operator.add, "%s + %s", lambda g, n, a, gb, acc: (acc(a[0], gb), acc(a[1], gb)),
+       commutative=True),
+    _O("sub", 2, operator.sub, operator.sub, "%s - %s", lambda g, n, a, gb, acc: (acc(a[0], gb), acc(a[1], -gb))),
+    _O("mul", 2, operator.mul, operator.mul, "%s * %s", lambda g, n, a, gb, acc: (acc(a[0], gb * a[1]), acc(a[1], gb * a[0])),
+       commutative=True),
+    # torch: grad / other, -grad * ((self / other) / other)
+    _O("div", 2, operator.truediv, operator.truediv, ("fdiv(%s, %s)", "%s / %s"),
+       lambda g, n, a, gb, acc: (acc(a[0], gb / a[1]), acc(a[1], -(gb * (n / a[1])))),
+       peephole=lambda n, a, fast: "frcp(%s)" % a[1] if fast and _is_const(n.args[0], 1.0) else None),
+    _O("neg", 1, operator.neg, operator.neg, "-%s", lambda g, n, a, gb, acc: acc(a[0], -gb)),
+    _O("exp", 1, np.exp, torch.exp, ("fexp(%s)", "expf(%s)"), lambda g, n, a, gb, acc: acc(a[0], gb * n),
+       public=True, number=math.exp),
+    _O("log", 1, np.log, torch.log, "logf(%s)", lambda g, n, a, gb, acc: acc(a[0], gb / a[0]), public=True, number=math.log),
+    # pow_vjp: g n a^(n-1), g a^n log(a)  (unmasked at a = 0: see the module docstring)
+    _O("pow", 2, np.power, torch.pow, "powf(%s, %s)",
+       lambda g, n, a, gb, acc: (acc(a[0], gb * (a[1] * g.make("pow", (a[0], a[1] - 1.0)))),
+                                 acc(a[1], gb * (n * g.make("log", (a[0],))))),
+       public=True, number=math.pow,
+       peephole=lambda n, a, fast: "%s * %s" % (a[0], a[0]) if _is_const(n.args[1], 2.0) else None),
+    _O("sigmoid", 1, lambda a: 1.0 / (1.0 + np.exp(-a)), torch.sigmoid, ("sigmoid_f(%s)", "1.f / (1.f + expf(-%s))"),
+       lambda g, n, a, gb, acc: acc(a[0], gb * (n * (1.0 - n))), public=True, number=lambda x: 1.0 / (1.0 + math.exp(-x))),
+    _O("tanh", 1, np.tanh, torch.tanh, ("ftanh(%s)", "tanhf(%s)"), lambda g, n, a, gb, acc: acc(a[0], gb * (1.0 - n * n)),
+       public=True, number=math.tanh),
+    # (clamp and where are public with functions written out below: their arguments are checked)
+    _O("clamp", 1, lambda a, v: min(max(a, v[0]), v[1]) if a == a else a, lambda a, v: torch.clamp(a, v[0], v[1]),
+       "clampf(%s, %s, %s)", lambda g, n, a, gb, acc: acc(a[0], gb * g.make("cpass", (a[0],), n.val)), val=True, public=True),
+    _O("cpass", 1, lambda a, v: 1.0 if v[0] <= a <= v[1] else 0.0, lambda a, v: ((a >= v[0]) & (a <= v[1])).to(a.dtype),
+       "clamp_pass(%s, %s, %s)", kind="pass", val=True),
+    # conditions: a < b and a <= b (a > b and a >= b are the same two with the arguments swapped) and their combinations;
+    # a NaN operand makes every comparison false.  They are bools in C, where is a select (one v_cndmask_b32): straight-line
+    # code, no branch
+    _O("lt", 2, operator.lt, operator.lt, "%s < %s", kind="condition"),
+    _O("le", 2, operator.le, operator.le, "%s <= %s", kind="condition"),
+    _O("and", 2, operator.and_, operator.and_, "%s && %s", kind="condition"),
+    _O("or", 2, operator.or_, operator.or_, "%s || %s", kind="condition"),
+    _O("not", 1, operator.not_, operator.invert, "!%s", kind="condition"),
+    # a select of the adjoint, never a product with a mask: what the other branch holds is not touched
+    _O("where", 3, lambda c, a, b: a if c else b, torch.where, "fsel(%s, %s, %s)",
+       lambda g, n, a, gb, acc: (acc(a[1], g.where(a[0], gb, g.const(0.0))), acc(a[2], g.where(a[0], g.const(0.0), gb))),
+       public=True),
+    # np.minimum / np.maximum propagate NaN, as torch's; the adjoint: g to the selected argument, g / 2 to each at a tie
+    _O("minimum", 2, np.minimum, _both_tensors(torch.minimum), "fmin_nan(%s, %s)",
+       lambda g, n, a, gb, acc: (acc(a[0], gb * g.make("minpass", (a[0], a[1]))), acc(a[1], gb * g.make("minpass", (a[1], a[0])))),
+       public=True),
+    _O("maximum", 2, np.maximum, _both_tensors(torch.maximum), "fmax_nan(%s, %s)",
+       lambda g, n, a, gb, acc: (acc(a[0], gb * g.make("maxpass", (a[0], a[1]))), acc(a[1], gb * g.make("maxpass", (a[1], a[0])))),
+       public=True),
+    _O("minpass", 2, lambda a, b: 0.0 if a > b else (0.5 if a == b else 1.0), lambda a, b: _pass_weight(a, b, a > b),
+       "min_pass(%s, %s)", kind="pass"),
+    _O("maxpass", 2, lambda a, b: 0.0 if a < b else (0.5 if a == b else 1.0), lambda a, b: _pass_weight(a, b, a < b),
+       "max_pass(%s, %s)", kind="pass"),
+    # g sign(x), sign(0) = 0
+    _O("abs", 1, np.abs, torch.abs, "fabsf(%s)", lambda g, n, a, gb, acc: acc(a[0], gb * g.make("sign", (a[0],))), public=True),
+    _O("sign", 1, lambda a: 1.0 if a > 0.0 else (-1.0 if a < 0.0 else 0.0), torch.sign, "fsign(%s)", kind="pass"),
+    # g / (2 sqrt(x)): infinite at 0, as torch's; the value is NaN below 0, as the kernels' and torch's
+    _O("sqrt", 1, np.sqrt, torch.sqrt, ("fsqrt(%s)", "sqrtf(%s)"), lambda g, n, a, gb, acc: acc(a[0], gb / (2.0 * n)),
+       public=True),
+    _O("erf", 1, math.erf, torch.erf, "erff(%s)",
+       lambda g, n, a, gb, acc: acc(a[0], gb * (_TWO_OVER_SQRT_PI * g.make("exp", (-(a[0] * a[0]),)))), public=True),
+    _O("erfc", 1, math.erfc, torch.erfc, "erfcf(%s)",
+       lambda g, n, a, gb, acc: acc(a[0], -(gb * (_TWO_OVER_SQRT_PI * g.make("exp", (-(a[0] * a[0]),))))), public=True),
+)}
+del _O
+OPERATIONS = tuple(r.name for r in OP_TABLE.values() if r.public)
+_COMMUTATIVE = tuple(r.name for r in OP_TABLE.values() if r.commutative)
+# ("cconst": the constant conditions that folding leaves -- a leaf, like "const")
+_CONDITIONS = tuple(r.name for r in OP_TABLE.values() if r.kind == "condition") + ("cconst",)
+
+
+def _fold(op, *args, val=None):
+    """Constant folding in float64 (IEEE semantics: inf / NaN instead of exceptions); a condition folds to a bool."""
+    rec = OP_TABLE[op]
     with np.errstate(all="ignore"):
-        a = np.float64(a)
-        if op == "add": return float(a + b)
-        if op == "sub": return float(a - b)
-        if op == "mul": return float(a * b)
-        if op == "div": return float(a / np.float64(b))
-        if op == "neg": return float(-a)
-        if op == "exp": return float(np.exp(a))
-        if op == "log": return float(np.log(a))
-        if op == "pow": return float(np.power(a, np.float64(b)))
-        if op == "sigmoid": return float(1.0 / (1.0 + np.exp(-a)))
-        if op == "tanh": return float(np.tanh(a))
-        if op == "clamp": return float(min(max(a, val[0]), val[1])) if a == a else float(a)
-        if op == "cpass": return 1.0 if val[0] <= a <= val[1] else 0.0
-        if op == "lt": return bool(a < np.float64(b))  # (a NaN operand makes every comparison false)
-        if op == "le": return bool(a <= np.float64(b))
-        if op == "minimum": return float(np.minimum(a, np.float64(b)))  # (np.minimum / np.maximum propagate NaN, as torch's)
-        if op == "maximum": return float(np.maximum(a, np.float64(b)))
-        if op == "minpass": return 0.0 if a > b else (0.5 if a == b else 1.0)
-        if op == "maxpass": return 0.0 if a < b else (0.5 if a == b else 1.0)
-        if op == "abs": return float(np.abs(a))
-        if op == "sign": return 1.0 if a > 0.0 else (-1.0 if a < 0.0 else 0.0)
-        if op == "sqrt": return float(np.sqrt(a))
-        if op == "erf": return math.erf(a)
-        if op == "erfc": return math.erfc(a)
-    raise AssertionError(op)
+        args = [a if isinstance(a, (bool, np.bool_)) else np.float64(a) for a in args]
+        v = rec.fold(*args, val) if rec.val else rec.fold(*args)
+    return bool(v) if rec.kind == "condition" else float(v)
 
 
 class Graph(object):
@@ -409,7 +503,7 @@ class Graph(object):
         """c1 & c2 ("and"), c1 | c2 ("or"), ~c ("not"); constant conditions fold, c & c, c | c and ~~c simplify."""
         args = tuple(self._condition(c, {"and": "&", "or": "|", "not": "~"}[op]) for c in args)
         if op == "not":
-            if args[0].op == "cconst": return self._intern("cconst", (), not args[0].val)
+            if args[0].op == "cconst": return self._intern("cconst", (), _fold(op, args[0].val))
             if args[0].op == "not": return args[0].args[0]
             return self._intern(op, args, None)
         absorbing = op == "or"  # (the constant that decides the result: True for |, False for &)
@@ -484,38 +578,6 @@ def _number(x, what):
     return float(x)
 
 
-def exp(x):
-    g = _sym_of((x,))
-    if g: return g.make("exp", (x,))
-    return torch.exp(x) if _tensor_of((x,)) else math.exp(x)
-
-
-def log(x):
-    g = _sym_of((x,))
-    if g: return g.make("log", (x,))
-    return torch.log(x) if _tensor_of((x,)) else math.log(x)
-
-
-def pow(x, n):  # noqa: A001  (the operation's name in the model namespace)
-    g = _sym_of((x, n))
-    if g: return g.make("pow", (x, n))
-    if _tensor_of((x, n)):
-        return torch.pow(x, n)
-    return math.pow(x, n)
-
-
-def sigmoid(x):
-    g = _sym_of((x,))
-    if g: return g.make("sigmoid", (x,))
-    return torch.sigmoid(x) if _tensor_of((x,)) else 1.0 / (1.0 + math.exp(-x))
-
-
-def tanh(x):
-    g = _sym_of((x,))
-    if g: return g.make("tanh", (x,))
-    return torch.tanh(x) if _tensor_of((x,)) else math.tanh(x)
-
-
 def clamp(x, lo, hi):
     lo, hi = _number(lo, "clamp's lower bound"), _number(hi, "clamp's upper bound")
     if not lo <= hi:
@@ -525,11 +587,6 @@ def clamp(x, lo, hi):
     if _tensor_of((x,)):
         return torch.clamp(x, lo, hi)
     return min(max(x, lo), hi)
-
-
-def _like(v, other):
-    """A Python number as a tensor beside `other` (torch.minimum / maximum / where want tensors)."""
-    return v if isinstance(v, torch.Tensor) else torch.as_tensor(float(v), dtype=other.dtype, device=other.device)
 
 
 def where(cond, a, b):
@@ -553,55 +610,29 @@ def where(cond, a, b):
     return torch.where(cond, torch.tensor(a, dtype=dtype, device=cond.device), torch.tensor(b, dtype=dtype, device=cond.device))
 
 
-def minimum(a, b):
-    g = _sym_of((a, b))
-    if g: return g.make("minimum", (a, b))
-    if _tensor_of((a, b)):
-        ref = a if isinstance(a, torch.Tensor) else b
-        return torch.minimum(_like(a, ref), _like(b, ref))
-    return _fold("minimum", a, b)
+def _dispatching(rec):
+    """The module-level function of a table record: symbols build the node, tensors take torch, numbers take math."""
+    def f(*args):
+        if len(args) != rec.arity:
+            raise TypeError("%s() takes %d positional argument(s) but %d were given" % (rec.name, rec.arity, len(args)))
+        g = _sym_of(args)
+        if g: return g.make(rec.name, args)
+        return rec.torch(*args) if _tensor_of(args) else rec.number(*args)
+
+    f.__name__ = f.__qualname__ = rec.name
+    return f
 
 
-def maximum(a, b):
-    g = _sym_of((a, b))
-    if g: return g.make("maximum", (a, b))
-    if _tensor_of((a, b)):
-        ref = a if isinstance(a, torch.Tensor) else b
-        return torch.maximum(_like(a, ref), _like(b, ref))
-    return _fold("maximum", a, b)
-
-
-def abs(x):  # noqa: A001  (the operation's name in the model namespace; Python's abs() on a model quantity comes here too)
-    g = _sym_of((x,))
-    if g: return g.make("abs", (x,))
-    return torch.abs(x) if _tensor_of((x,)) else math.fabs(x)
-
-
-def sqrt(x):
-    g = _sym_of((x,))
-    if g: return g.make("sqrt", (x,))
-    return torch.sqrt(x) if _tensor_of((x,)) else _fold("sqrt", x)  # (NaN below 0, as the kernels and torch)
-
-
-def erf(x):
-    g = _sym_of((x,))
-    if g: return g.make("erf", (x,))
-    return torch.erf(x) if _tensor_of((x,)) else math.erf(x)
-
-
-def erfc(x):
-    g = _sym_of((x,))
-    if g: return g.make("erfc", (x,))
-    return torch.erfc(x) if _tensor_of((x,)) else math.erfc(x)
+# exp, log, pow, sigmoid, tanh, minimum, maximum, abs (Python's abs() on a model quantity comes here too), sqrt, erf, erfc
+globals().update((r.name, _dispatching(r)) for r in OP_TABLE.values() if r.public and r.name not in globals())
 
 
 class _Namespace(object):
     """`op.exp(x)` ...: the operations as one object; any other name is refused with the list."""
 
-    exp, log, pow, sigmoid, tanh, clamp = (staticmethod(f) for f in (exp, log, pow, sigmoid, tanh, clamp))
-    where, minimum, maximum, abs, sqrt, erf, erfc = (staticmethod(f) for f in (where, minimum, maximum, abs, sqrt, erf, erfc))
-
     def __getattr__(self, name):
+        if name in OPERATIONS:
+            return globals()[name]
         raise ModelDefinitionError("operation '%s' is not available to generated models (available: + - * / and %s)"
                                    % (name, ", ".join(OPERATIONS)))
 
@@ -667,48 +698,8 @@ def vjp(g, outputs, seeds):
             net_adj.setdefault(a[0].id, {})[n.val] = gb
         elif n.op in ("netbwd", "netbwd_in"):
             raise ModelDefinitionError("second derivatives of a network are not generated")
-        elif n.op == "add":
-            acc(a[0], gb); acc(a[1], gb)
-        elif n.op == "sub":
-            acc(a[0], gb); acc(a[1], -gb)
-        elif n.op == "mul":
-            acc(a[0], gb * a[1]); acc(a[1], gb * a[0])
-        elif n.op == "div":  # torch: grad / other, -grad * ((self / other) / other)
-            acc(a[0], gb / a[1]); acc(a[1], -(gb * (n / a[1])))
-        elif n.op == "neg":
-            acc(a[0], -gb)
-        elif n.op == "exp":
-            acc(a[0], gb * n)
-        elif n.op == "log":
-            acc(a[0], gb / a[0])
-        elif n.op == "pow":  # pow_vjp: g n a^(n-1), g a^n log(a)  (unmasked at a = 0: see the module docstring)
-            acc(a[0], gb * (a[1] * g.make("pow", (a[0], a[1] - 1.0))))
-            acc(a[1], gb * (n * g.make("log", (a[0],))))
-        elif n.op == "sigmoid":
-            acc(a[0], gb * (n * (1.0 - n)))
-        elif n.op == "tanh":
-            acc(a[0], gb * (1.0 - n * n))
-        elif n.op == "clamp":
-            acc(a[0], gb * g.make("cpass", (a[0],), n.val))
-        elif n.op == "where":  # a select of the adjoint, never a product with a mask: what the other branch holds is not touched
-            zero = g.const(0.0)
-            acc(a[1], g.where(a[0], gb, zero)); acc(a[2], g.where(a[0], zero, gb))
-        elif n.op == "minimum":  # g to the selected argument, g / 2 to each at a tie
-            acc(a[0], gb * g.make("minpass", (a[0], a[1]))); acc(a[1], gb * g.make("minpass", (a[1], a[0])))
-        elif n.op == "maximum":
-            acc(a[0], gb * g.make("maxpass", (a[0], a[1]))); acc(a[1], gb * g.make("maxpass", (a[1], a[0])))
-        elif n.op == "abs":  # g sign(x), sign(0) = 0
-            acc(a[0], gb * g.make("sign", (a[0],)))
-        elif n.op == "sqrt":  # g / (2 sqrt(x)): infinite at 0, as torch's
-            acc(a[0], gb / (2.0 * n))
-        elif n.op == "erf":
-            acc(a[0], gb * (_TWO_OVER_SQRT_PI * g.make("exp", (-(a[0] * a[0]),))))
-        elif n.op == "erfc":
-            acc(a[0], -(gb * (_TWO_OVER_SQRT_PI * g.make("exp", (-(a[0] * a[0]),)))))
-        elif n.op in _PASS_NODES:
-            pass  # piecewise constant
-        else:
-            raise AssertionError(n.op)
+        elif OP_TABLE[n.op].adjoint is not None:  # (conditions and pass nodes: piecewise constant)
+            OP_TABLE[n.op].adjoint(g, n, a, gb, acc)
     return adj
 
 
@@ -746,33 +737,6 @@ def evaluate(outputs, env):
         a = [vals[x.id] for x in n.args]
         if n.op == "const": v = torch.tensor(n.val, dtype=torch.float64)
         elif n.op in _LEAVES: v = env[(n.op, n.val)]
-        elif n.op == "add": v = a[0] + a[1]
-        elif n.op == "sub": v = a[0] - a[1]
-        elif n.op == "mul": v = a[0] * a[1]
-        elif n.op == "div": v = a[0] / a[1]
-        elif n.op == "neg": v = -a[0]
-        elif n.op == "exp": v = torch.exp(a[0])
-        elif n.op == "log": v = torch.log(a[0])
-        elif n.op == "pow": v = torch.pow(a[0], a[1])
-        elif n.op == "sigmoid": v = torch.sigmoid(a[0])
-        elif n.op == "tanh": v = torch.tanh(a[0])
-        elif n.op == "clamp": v = torch.clamp(a[0], n.val[0], n.val[1])
-        elif n.op == "cpass": v = ((a[0] >= n.val[0]) & (a[0] <= n.val[1])).to(a[0].dtype)
-        elif n.op == "lt": v = a[0] < a[1]
-        elif n.op == "le": v = a[0] <= a[1]
-        elif n.op == "and": v = a[0] & a[1]
-        elif n.op == "or": v = a[0] | a[1]
-        elif n.op == "not": v = ~a[0]
-        elif n.op == "where": v = torch.where(a[0], a[1], a[2])
-        elif n.op == "minimum": v = torch.minimum(a[0], a[1])
-        elif n.op == "maximum": v = torch.maximum(a[0], a[1])
-        elif n.op == "minpass": v = torch.where(a[0] == a[1], 0.5, 1.0).masked_fill(a[0] > a[1], 0.0).to(a[0].dtype)
-        elif n.op == "maxpass": v = torch.where(a[0] == a[1], 0.5, 1.0).masked_fill(a[0] < a[1], 0.0).to(a[0].dtype)
-        elif n.op == "abs": v = torch.abs(a[0])
-        elif n.op == "sign": v = torch.sign(a[0])
-        elif n.op == "sqrt": v = torch.sqrt(a[0])
-        elif n.op == "erf": v = torch.erf(a[0])
-        elif n.op == "erfc": v = torch.erfc(a[0])
         elif n.op == "net": v = net_forward_ref(n.g.networks[n.val], env[("w", n.val)], stack(a))[2]
         elif n.op == "netout": v = a[0][..., n.val]
         elif n.op == "netbwd":
@@ -781,7 +745,8 @@ def evaluate(outputs, env):
             if "wgrad" in env:
                 env["wgrad"][n.val] = wg
         elif n.op == "netbwd_in": v = a[0][..., n.val]
-        else: raise AssertionError(n.op)
+        elif OP_TABLE[n.op].val: v = OP_TABLE[n.op].torch(*a, n.val)
+        else: v = OP_TABLE[n.op].torch(*a)
         vals[n.id] = v
     return [vals[o.id] if isinstance(o, Sym) else torch.tensor(float(o), dtype=torch.float64) for o in outputs]
 
@@ -851,6 +816,98 @@ class _Networks(object):
         raise ModelDefinitionError("networks are read-only")
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the hook table
+# ---------------------------------------------------------------------------------------------------------------------
+def _settle_observe_kind(cls):
+    """A class with a map of its own (defined here or inherited) has observe_kind "custom", and none of the fixed kinds."""
+    if getattr(cls, "_observe_def", None) is None:
+        return
+    for k in cls.__mro__:
+        kind = k.__dict__.get("observe_kind", "default")
+        if kind != "default" and not (kind == OBSERVE_CUSTOM and k.__dict__.get("_observe_kind_set")):
+            raise ModelDefinitionError("%s defines observe and observe_kind = %r: a model has either a map of its "
+                                       "own or one of the fixed kinds (leave observe_kind at 'default')"
+                                       % (cls.__name__, kind))
+        if k is GeneratedOdeModel:
+            break
+    cls.observe_kind, cls._observe_kind_set = OBSERVE_CUSTOM, True
+
+
+_GROUP_ADJOINT = {"y": "yb", "x": "xpb", "pr": "prb", "p": "pb"}  # leaf kind -> the kernel's adjoint array ("ob": data, none)
+
+
+class Hook(object):
+    """One optional function of a model that the kernels call once per time point, inside the time loop; it returns four
+    values, is traced into the model's DAG (the operations of rhs: no t, no network calls) and is emitted with its
+    reverse-mode adjoint as two members of the struct.  TO ADD A HOOK, ADD ONE RECORD to HOOKS (in the order in which the
+    forward kernel calls them) and its call site in the kernels; tracing, code generation, the capture of the definition
+    when a class is defined and the torch restatement walk this table.
+      name, signature    the Python method, and how error messages spell it
+      groups             the lists of leaves it receives, in order, from "y" (the N species), "x" (the 4 predicted
+                         signals), "ob" (the 4 observations), "pr" (the 4 precisions); p and c always follow.  The adjoint
+                         adds into the adjoint array of each group that has one (_GROUP_ADJOINT), in this order, and last
+                         into pb of the named effective parameters (a treatment has no adjoint)
+      outputs            what the four returned values are, in error messages
+      attr, traced       the class attribute that holds the definition; the Trace attribute that holds its four nodes
+      c_out, seed        the C arrays of the values and of their adjoints
+      c_forward, c_adjoint   the members' signatures
+      switch, switch_note    what tells the kernels that the struct has the members: the value of OBS, or a constant of
+                         its own declared with this comment
+      excludes_neural    what the model then owns that NeuralPrecisions would own too (None: they combine)
+    and how the definition is taken from a class body (GeneratedOdeModel.__init_subclass__):
+      note               what the "must be a function" error adds to the signature
+      hides_method       the definition is removed from the class (observe would hide OdeModel.observe(x_sample, theta), the
+                         entry point the decoder calls on instances: the definition is kept as the class's map)
+      none_resets        `name = None` in a subclass returns to the kernels' default
+      checks_arguments   the definition must take exactly the arguments of the signature (more with defaults, and
+                         keyword-only helpers, are the author's own)
+      settle             called for every subclass after the capture"""
+
+    switch_note = excludes_neural = settle = None
+    note = ""
+    hides_method = none_resets = checks_arguments = False
+
+    def __init__(self, name, **fields):
+        self.name = name
+        self.__dict__.update(fields)
+
+    @property
+    def targets(self):
+        return [(k, _GROUP_ADJOINT[k]) for k in self.groups + ("p",) if k in _GROUP_ADJOINT]
+
+
+HOOKS = (
+    # the observation map: sees the species, the effective parameters and the treatments, like rhs without t
+    Hook("observe", signature="observe(self, y, p, c)", groups=("y",), outputs="the OD, RFP, YFP and CFP signals",
+         attr="_observe_def", traced="obs", c_out="xp", seed="xpb", switch="OBS_CUSTOM",
+         c_forward=["  __device__ static void observe(const float* y, const float* p, float* xp) {"],
+         c_adjoint=["  __device__ static void observe_vjp(const float* y, const float* p, const float* xpb, float* yb, float* pb) {"],
+         hides_method=True, settle=_settle_observe_kind),
+    # the observation noise: sees the species, the four predicted signals, the effective parameters and the treatments.  Its
+    # adjoint adds into xpb too (the predicted signals' adjoint, which observe_vjp then pulls back)
+    Hook("precision", signature="precision(self, y, x, p, c)", groups=("y", "x"),
+         outputs="the precisions of the OD, RFP, YFP and CFP signals", attr="_precision_def", traced="prec", c_out="pr", seed="prb",
+         switch="OWN_PREC", switch_note="the precisions are this struct's map: no prec_* / init_prec_* slots",
+         c_forward=["  __device__ static void precision(const float* y, const float* xp, const float* p, float* pr) {"],
+         c_adjoint=["  __device__ static void precision_vjp(const float* y, const float* xp, const float* p, const float* prb, float* yb,",
+                    "                                       float* xpb, float* pb) {"],
+         excludes_neural="precision map"),
+    # the observation log density: sees the four predicted signals, the four observations (data: no adjoint) and the four
+    # precisions of the time point, the effective parameters and the treatments -- no species, no t
+    Hook("log_likelihood", signature="log_likelihood(self, x, obs, pr, p, c)", groups=("x", "ob", "pr"),
+         outputs="the log densities of the OD, RFP, YFP and CFP signals at one time point", attr="_likelihood_def", traced="lik",
+         c_out="ll", seed="llb", switch="OWN_LIK", switch_note="the observation log density is this struct's: loglik / loglik_vjp",
+         c_forward=["  __device__ static void loglik(const float* xp, const float* ob, const float* pr, const float* p, float* ll) {"],
+         c_adjoint=["  __device__ static void loglik_vjp(const float* xp, const float* ob, const float* pr, const float* p, const float* llb,",
+                    "                                    float* xpb, float* prb, float* pb) {"],
+         excludes_neural="likelihood", none_resets=True, checks_arguments=True,
+         note=": it sees the predicted signals, the observations and the precisions of one time point, the effective parameters "
+              "and the treatments -- no t and no species (or None in a subclass, for the Gaussian)"),
+)
+HOOK = {h.name: h for h in HOOKS}
+
+
 class Trace(object):
     """The functions of a model class (prepare, initial_state, rhs and, when defined, observe, precision and log_likelihood)
     traced into one Graph."""
@@ -897,40 +954,18 @@ class Trace(object):
                 raise ModelDefinitionError("%s: network '%s' is declared but %s" % (
                     cls.__name__, name, "no derivative depends on its outputs" if name in self._called
                     else "never called in rhs"))
-        # observe (optional) sees the species, the effective parameters and the treatments, like rhs without t
-        self.obs = None
-        definition = getattr(cls, "_observe_def", None)
-        if definition is not None:
-            self._phase = "observe"
-            xp = definition(inst, [g.leaf("y", j) for j in range(N)], p, _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
-            if not isinstance(xp, (list, tuple)) or len(xp) != 4:
-                raise ModelDefinitionError("%s.observe must return a list of 4 entries (the OD, RFP, YFP and CFP signals)"
-                                           % cls.__name__)
-            self.obs = [g._arg(x) for x in xp]
-        # precision (optional) sees the species, the four predicted signals, the effective parameters and the treatments
-        self.prec = None
-        definition = getattr(cls, "_precision_def", None)
-        if definition is not None:
-            self._phase = "precision"
-            pr = definition(inst, [g.leaf("y", j) for j in range(N)], [g.leaf("x", j) for j in range(4)], p,
-                            _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
-            if not isinstance(pr, (list, tuple)) or len(pr) != 4:
-                raise ModelDefinitionError("%s.precision must return a list of 4 entries (the precisions of the OD, RFP, YFP "
-                                           "and CFP signals)" % cls.__name__)
-            self.prec = [g._arg(x) for x in pr]
-        # log_likelihood (optional) sees the four predicted signals, the four observations and the four precisions of the time
-        # point, the effective parameters and the treatments: no species, no t
-        self.lik = None
-        definition = getattr(cls, "_likelihood_def", None)
-        if definition is not None:
-            self._phase = "log_likelihood"
-            ll = definition(inst, [g.leaf("x", j) for j in range(4)], [g.leaf("ob", j) for j in range(4)],
-                            [g.leaf("pr", j) for j in range(4)], p, _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
-            if not isinstance(ll, (list, tuple)) or len(ll) != 4:
-                raise ModelDefinitionError("%s.log_likelihood must return a list of 4 entries (the log densities of the OD, "
-                                           "RFP, YFP and CFP signals at one time point)" % cls.__name__)
-            self.lik = [g._arg(x) for x in ll]
-        used = {n.val for n in _topo(self.dy + (self.obs or []) + (self.prec or []) + (self.lik or [])) if n.op == "p"}
+        # the hooks (optional) see their groups of leaves, the effective parameters and the treatments
+        for h in HOOKS:
+            setattr(self, h.traced, None)
+            definition = getattr(cls, h.attr, None)
+            if definition is not None:
+                self._phase = h.name
+                out = definition(inst, *[[g.leaf(k, j) for j in range(N if k == "y" else 4)] for k in h.groups], p,
+                                 _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
+                if not isinstance(out, (list, tuple)) or len(out) != 4:
+                    raise ModelDefinitionError("%s.%s must return a list of 4 entries (%s)" % (cls.__name__, h.name, h.outputs))
+                setattr(self, h.traced, [g._arg(x) for x in out])
+        used = {n.val for n in _topo(self.dy + [x for h in HOOKS for x in getattr(self, h.traced) or []]) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
@@ -974,41 +1009,11 @@ class _Emitter(object):
         return self.names[n.id]
 
     def expr(self, n):
-        a = [self.ref(x) for x in n.args]
-        f = self.fast
-        if n.op == "add": return "%s + %s" % tuple(a)
-        if n.op == "sub": return "%s - %s" % tuple(a)
-        if n.op == "mul": return "%s * %s" % tuple(a)
-        if n.op == "div":
-            if f and n.args[0].op == "const" and n.args[0].val == 1.0: return "frcp(%s)" % a[1]
-            return ("fdiv(%s, %s)" if f else "%s / %s") % tuple(a)
-        if n.op == "neg": return "-%s" % a[0]
-        if n.op == "exp": return ("fexp(%s)" if f else "expf(%s)") % a[0]
-        if n.op == "log": return "logf(%s)" % a[0]
-        if n.op == "pow":
-            if n.args[1].op == "const" and n.args[1].val == 2.0: return "%s * %s" % (a[0], a[0])
-            return "powf(%s, %s)" % tuple(a)
-        if n.op == "sigmoid": return ("sigmoid_f(%s)" if f else "1.f / (1.f + expf(-%s))") % a[0]
-        if n.op == "tanh": return ("ftanh(%s)" if f else "tanhf(%s)") % a[0]
-        if n.op == "clamp": return "clampf(%s, %s, %s)" % (a[0], _lit(n.val[0]), _lit(n.val[1]))
-        if n.op == "cpass": return "clamp_pass(%s, %s, %s)" % (a[0], _lit(n.val[0]), _lit(n.val[1]))
-        # conditions are bools, where is a select (one v_cndmask_b32): straight-line code, no branch
-        if n.op == "lt": return "%s < %s" % tuple(a)
-        if n.op == "le": return "%s <= %s" % tuple(a)
-        if n.op == "and": return "%s && %s" % tuple(a)
-        if n.op == "or": return "%s || %s" % tuple(a)
-        if n.op == "not": return "!%s" % a[0]
-        if n.op == "where": return "fsel(%s, %s, %s)" % tuple(a)
-        if n.op == "minimum": return "fmin_nan(%s, %s)" % tuple(a)
-        if n.op == "maximum": return "fmax_nan(%s, %s)" % tuple(a)
-        if n.op == "minpass": return "min_pass(%s, %s)" % tuple(a)
-        if n.op == "maxpass": return "max_pass(%s, %s)" % tuple(a)
-        if n.op == "abs": return "fabsf(%s)" % a[0]
-        if n.op == "sign": return "fsign(%s)" % a[0]
-        if n.op == "sqrt": return ("fsqrt(%s)" if f else "sqrtf(%s)") % a[0]
-        if n.op == "erf": return "erff(%s)" % a[0]
-        if n.op == "erfc": return "erfcf(%s)" % a[0]
-        raise AssertionError(n.op)
+        rec, a = OP_TABLE[n.op], [self.ref(x) for x in n.args]
+        text = rec.peephole(n, a, self.fast) if rec.peephole else None
+        if text is None:
+            text = rec.c[0 if self.fast else 1] % tuple(a + [_lit(v) for v in (n.val if rec.val else ())])
+        return text
 
     def emit(self, assignments):
         """assignments: [(lhs, '=' or '+=', node)] -> body lines."""
@@ -1025,31 +1030,27 @@ class _Emitter(object):
             self.lines.append("    %s %s %s;" % (lhs, how, self.ref(n)))
         return self.lines
 
-
-def _emit_net(self, n):
-    """Network nodes: the call nodes become one call of the struct's net<k>_forward / net<k>_vjp on small register arrays,
-    the output / input-adjoint nodes are elements of those arrays."""
-    k = n.val if n.op in ("net", "netbwd") else n.args[0].val
-    if n.op == "netout":
-        self.names[n.id] = "n%d_o[%d]" % (k, n.val)
-    elif n.op == "netbwd_in":
-        self.names[n.id] = "n%d_xb[%d]" % (k, n.val)
-    else:
-        I, _H, O = n.g.networks[k].sizes
-        refs = [self.ref(x) for x in n.args]
-        if n.op == "net":
-            self.lines += ["    const float n%d_x[%d] = {%s};" % (k, I, ", ".join(refs)),
-                           "    float n%d_o[%d];" % (k, O),
-                           "    net%d_forward(w, n%d_x, n%d_o);" % (k, k, k)]
+    def _emit_net(self, n):
+        """Network nodes: the call nodes become one call of the struct's net<k>_forward / net<k>_vjp on small register arrays,
+        the output / input-adjoint nodes are elements of those arrays."""
+        k = n.val if n.op in ("net", "netbwd") else n.args[0].val
+        if n.op == "netout":
+            self.names[n.id] = "n%d_o[%d]" % (k, n.val)
+        elif n.op == "netbwd_in":
+            self.names[n.id] = "n%d_xb[%d]" % (k, n.val)
         else:
-            self.lines += ["    const float n%d_bx[%d] = {%s};" % (k, I, ", ".join(refs[:I])),
-                           "    const float n%d_ob[%d] = {%s};" % (k, O, ", ".join(refs[I:])),
-                           "    float n%d_xb[%d];" % (k, I),
-                           "    net%d_vjp<Ctx::DUMP>(w, n%d_bx, n%d_ob, n%d_xb, D, fs);" % (k, k, k, k)]
-        self.names[n.id] = "n%d" % k
-
-
-_Emitter._emit_net = _emit_net
+            I, _H, O = n.g.networks[k].sizes
+            refs = [self.ref(x) for x in n.args]
+            if n.op == "net":
+                self.lines += ["    const float n%d_x[%d] = {%s};" % (k, I, ", ".join(refs)),
+                               "    float n%d_o[%d];" % (k, O),
+                               "    net%d_forward(w, n%d_x, n%d_o);" % (k, k, k)]
+            else:
+                self.lines += ["    const float n%d_bx[%d] = {%s};" % (k, I, ", ".join(refs[:I])),
+                               "    const float n%d_ob[%d] = {%s};" % (k, O, ", ".join(refs[I:])),
+                               "    float n%d_xb[%d];" % (k, I),
+                               "    net%d_vjp<Ctx::DUMP>(w, n%d_bx, n%d_ob, n%d_xb, D, fs);" % (k, k, k, k)]
+            self.names[n.id] = "n%d" % k
 
 
 def _network_functions(networks):
@@ -1114,17 +1115,21 @@ def generate_source(cls, neural=False):
     recomputed inside them) and the switches csrc/generated/ode_generated_model.hip reads.  Deterministic: the same
     definition gives byte-identical text; its hash (with the kernel headers') names the library."""
     tr = cls._trace
-    if neural and tr.prec is not None:
-        raise ModelDefinitionError("%s defines precision(self, y, x, p, c): a model with a precision map of its own does not "
-                                   "take NeuralPrecisions" % cls.__name__)
-    if neural and tr.lik is not None:
-        raise ModelDefinitionError("%s defines log_likelihood(self, x, obs, pr, p, c): a model with a likelihood of its own "
-                                   "does not take NeuralPrecisions" % cls.__name__)
+    for h in HOOKS:
+        if neural and h.excludes_neural and getattr(tr, h.traced) is not None:
+            raise ModelDefinitionError("%s defines %s: a model with a %s of its own does not take NeuralPrecisions"
+                                       % (cls.__name__, h.signature, h.excludes_neural))
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
-    obs_enum = "OBS_CUSTOM" if tr.obs is not None else OBSERVE_KINDS[cls.observe_kind][0]
+    obs_enum = HOOK["observe"].switch if tr.obs is not None else OBSERVE_KINDS[cls.observe_kind][0]
     sname = "GenModel_" + _ident(cls.model_key)
+
+    def pull(adj, targets):
+        """`target[j] += adjoint of leaf j` for the leaves of each (leaf kind, adjoint array) that the outputs depend on;
+        of p only the named effective parameters (a treatment has no adjoint)."""
+        return [("%s[%d]" % (target, j), "+=", adj[g.leaf(kind, j).id])
+                for kind, target in targets for j in range({"y": N, "p": NPU}.get(kind, 4)) if g.leaf(kind, j).id in adj]
 
     # prepare: named parameters, then the treatments rhs reads
     prep = [("p[%d]" % k, "=", e) for k, e in enumerate(tr.p_exprs)]
@@ -1155,42 +1160,7 @@ def generate_source(cls, neural=False):
     rhs = [("dy[%d]" % j, "=", e) for j, e in enumerate(tr.dy)]
     v = [g.leaf("seed", j) for j in range(N)]
     adj1 = vjp(g, tr.dy, v)
-    rhs_vjp = [("yb[%d]" % j, "+=", adj1[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj1]
-    rhs_vjp += [("pb[%d]" % k, "+=", adj1[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj1]
-
-    # observe / observe_vjp (a model with a map of its own): both run once per time point inside the time loop.  The adjoint
-    # adds into yb and into pb of the named effective parameters (a treatment has no adjoint)
-    obs_decl = []
-    if tr.obs is not None:
-        xpb = [g.leaf("seed", j) for j in range(4)]
-        adj2 = vjp(g, tr.obs, xpb)
-        obs = [("xp[%d]" % j, "=", e) for j, e in enumerate(tr.obs)]
-        obs_vjp = [("yb[%d]" % j, "+=", adj2[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj2]
-        obs_vjp += [("pb[%d]" % k, "+=", adj2[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj2]
-
-    # precision / precision_vjp (a model with a precision map of its own): once per time point inside the time loop, like
-    # the map.  The adjoint adds into yb, into xpb (the predicted signals' adjoint, which observe_vjp then pulls back) and
-    # into pb of the named effective parameters
-    prec_decl = []
-    if tr.prec is not None:
-        prb = [g.leaf("seed", j) for j in range(4)]
-        adj3 = vjp(g, tr.prec, prb)
-        prec = [("pr[%d]" % j, "=", e) for j, e in enumerate(tr.prec)]
-        prec_vjp = [("yb[%d]" % j, "+=", adj3[g.leaf("y", j).id]) for j in range(N) if g.leaf("y", j).id in adj3]
-        prec_vjp += [("xpb[%d]" % j, "+=", adj3[g.leaf("x", j).id]) for j in range(4) if g.leaf("x", j).id in adj3]
-        prec_vjp += [("pb[%d]" % k, "+=", adj3[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj3]
-
-    # loglik / loglik_vjp (a model with a likelihood of its own): once per time point inside the time loop.  The adjoint adds
-    # into xpb (the predicted signals), prb (the precisions) and pb of the named effective parameters; the observations are
-    # data and get none
-    lik_decl = []
-    if tr.lik is not None:
-        llb = [g.leaf("seed", j) for j in range(4)]
-        adj4 = vjp(g, tr.lik, llb)
-        lik = [("ll[%d]" % j, "=", e) for j, e in enumerate(tr.lik)]
-        lik_vjp = [("xpb[%d]" % j, "+=", adj4[g.leaf("x", j).id]) for j in range(4) if g.leaf("x", j).id in adj4]
-        lik_vjp += [("prb[%d]" % j, "+=", adj4[g.leaf("pr", j).id]) for j in range(4) if g.leaf("pr", j).id in adj4]
-        lik_vjp += [("pb[%d]" % k, "+=", adj4[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in adj4]
+    rhs_vjp = pull(adj1, [("y", "yb"), ("p", "pb")])
 
     def body(assign, fast, seed, p_map=None):
         names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp", "ob": "ob", "pr": "pr"}
@@ -1223,37 +1193,18 @@ def generate_source(cls, neural=False):
         vjp_sig = ["  __device__ static void rhs_vjp(float t, const float* y, const float* p, const float*, const float* v, float* yb,",
                    "                                 float* pb) {"]
         net_decl = []
-    if tr.obs is not None:
-        obs_decl = [
-            "  __device__ static void observe(const float* y, const float* p, float* xp) {",
-            body(obs, True, "xpb", tr.c_slot),
-            "  }",
-            "  __device__ static void observe_vjp(const float* y, const float* p, const float* xpb, float* yb, float* pb) {",
-            body(obs_vjp, True, "xpb", tr.c_slot),
-            "  }",
-        ]
-    if tr.prec is not None:
-        prec_decl = [
-            "  static constexpr bool OWN_PREC = true;  // the precisions are this struct's map: no prec_* / init_prec_* slots",
-            "  __device__ static void precision(const float* y, const float* xp, const float* p, float* pr) {",
-            body(prec, True, "prb", tr.c_slot),
-            "  }",
-            "  __device__ static void precision_vjp(const float* y, const float* xp, const float* p, const float* prb, float* yb,",
-            "                                       float* xpb, float* pb) {",
-            body(prec_vjp, True, "prb", tr.c_slot),
-            "  }",
-        ]
-    if tr.lik is not None:
-        lik_decl = [
-            "  static constexpr bool OWN_LIK = true;  // the observation log density is this struct's: loglik / loglik_vjp",
-            "  __device__ static void loglik(const float* xp, const float* ob, const float* pr, const float* p, float* ll) {",
-            body(lik, True, "llb", tr.c_slot),
-            "  }",
-            "  __device__ static void loglik_vjp(const float* xp, const float* ob, const float* pr, const float* p, const float* llb,",
-            "                                    float* xpb, float* prb, float* pb) {",
-            body(lik_vjp, True, "llb", tr.c_slot),
-            "  }",
-        ]
+    # the hooks a model defines: value and adjoint run once per time point inside the time loop
+    hook_decl = []
+    for h in HOOKS:
+        outs = getattr(tr, h.traced)
+        if outs is None:
+            continue
+        adj = vjp(g, outs, [g.leaf("seed", j) for j in range(4)])
+        if h.switch_note:
+            hook_decl.append("  static constexpr bool %s = true;  // %s" % (h.switch, h.switch_note))
+        hook_decl += h.c_forward + [body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in enumerate(outs)], True, h.seed, tr.c_slot),
+                                    "  }"]
+        hook_decl += h.c_adjoint + [body(pull(adj, h.targets), True, h.seed, tr.c_slot), "  }"]
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -1292,7 +1243,7 @@ def generate_source(cls, neural=False):
     ] + vjp_sig + [
         body(rhs_vjp, True, "v", tr.c_slot),
         "  }",
-    ] + obs_decl + prec_decl + lik_decl + [
+    ] + hook_decl + [
         "};",
         "}  // namespace vihds",
         "#define VIHDS_GEN_CORE %s" % sname,
@@ -1409,10 +1360,7 @@ class GeneratedOdeModel(OdeModel):
     parameter_names = None
     n_conditions = 0
     observe_kind = "default"
-    _observe_def = None  # the class's own observation map observe(self, y, p, c), when it defines one (module docstring)
-    _precision_def = None  # the class's own precision map precision(self, y, x, p, c), when it defines one (module docstring)
-    # the class's own observation log density log_likelihood(self, x, obs, pr, p, c), when it defines one (module docstring)
-    _likelihood_def = None
+    _observe_def = _precision_def = _likelihood_def = None  # the definitions of the hooks the class has (HOOKS: attr)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
 
     def __init_subclass__(cls, **kw):
@@ -1423,45 +1371,24 @@ class GeneratedOdeModel(OdeModel):
         if isinstance(declared, (list, tuple)):
             cls.parameter_names = list(declared)
             del cls.parameters
-        # ... and its observation map as `observe(self, y, p, c)`, which would hide OdeModel.observe(x_sample, theta), the
-        # entry point the decoder calls on instances: keep the definition as the class's map, the method as it is
-        definition = cls.__dict__.get("observe")
-        if definition is not None:
-            if not callable(definition):
-                raise ModelDefinitionError("%s.observe must be a function observe(self, y, p, c)" % cls.__name__)
-            cls._observe_def = definition
-            del cls.observe
-        if getattr(cls, "_observe_def", None) is not None:
-            for k in cls.__mro__:
-                kind = k.__dict__.get("observe_kind", "default")
-                if kind != "default" and not (kind == OBSERVE_CUSTOM and k.__dict__.get("_observe_kind_set")):
-                    raise ModelDefinitionError("%s defines observe and observe_kind = %r: a model has either a map of its "
-                                               "own or one of the fixed kinds (leave observe_kind at 'default')"
-                                               % (cls.__name__, kind))
-                if k is GeneratedOdeModel:
-                    break
-            cls.observe_kind, cls._observe_kind_set = OBSERVE_CUSTOM, True
-        definition = cls.__dict__.get("precision")
-        if definition is not None:
-            if not callable(definition):
-                raise ModelDefinitionError("%s.precision must be a function precision(self, y, x, p, c)" % cls.__name__)
-            cls._precision_def = definition
-        if "log_likelihood" in cls.__dict__:
-            definition = cls.__dict__["log_likelihood"]
-            if definition is None:  # (a subclass returns to the kernels' Gaussian)
-                cls._likelihood_def = None
-            else:
-                # the five arguments the tracer passes, self in front; arguments with defaults and keyword-only helpers are the
-                # author's own
-                required = [q for q in inspect.signature(definition).parameters.values()
-                            if q.default is q.empty and q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD)] \
-                    if callable(definition) else None
-                if required is None or len(required) != 6:
-                    raise ModelDefinitionError("%s.log_likelihood must be a function log_likelihood(self, x, obs, pr, p, c): it "
-                                               "sees the predicted signals, the observations and the precisions of one time "
-                                               "point, the effective parameters and the treatments -- no t and no species (or "
-                                               "None in a subclass, for the Gaussian)" % cls.__name__)
-                cls._likelihood_def = definition
+        # ... and its hooks (HOOKS says how each is taken from the class body)
+        for h in HOOKS:
+            definition = cls.__dict__.get(h.name)
+            if definition is not None:
+                ok = callable(definition)
+                if ok and h.checks_arguments:
+                    required = [q for q in inspect.signature(definition).parameters.values()
+                                if q.default is q.empty and q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD)]
+                    ok = len(required) == len(h.groups) + 3  # (self, the groups, p, c)
+                if not ok:
+                    raise ModelDefinitionError("%s.%s must be a function %s%s" % (cls.__name__, h.name, h.signature, h.note))
+                setattr(cls, h.attr, definition)
+                if h.hides_method:
+                    delattr(cls, h.name)
+            elif h.none_resets and h.name in cls.__dict__:
+                setattr(cls, h.attr, None)
+            if h.settle:
+                h.settle(cls)
         if cls.__dict__.get("model_key") is None and getattr(cls, "_trace", None) is not None:
             cls._trace = Trace(cls)  # (a subclass that only changes __init__)
             return
@@ -1598,8 +1525,7 @@ class GeneratedOdeModel(OdeModel):
         N = len(cls.species)
         B, S = th[cls.parameter_names[0]].shape
         ref = th[cls.parameter_names[0]]
-        tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
-        cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+        cs = _treatments_torch(cls, cond, ref, S)
         thn = _Named([(n, th[n]) for n in cls.parameter_names], "parameter")
         full = lambda v: v if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
         p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
@@ -1620,7 +1546,7 @@ class GeneratedOdeModel(OdeModel):
         if cls._observe_def is None:
             raise ModelDefinitionError("%s defines no observe(self, y, p, c): its map is the fixed kind '%s'"
                                        % (cls.__name__, cls.observe_kind))
-        return _observe_torch(cls, cls.__new__(cls), y[:, :, :len(cls.species), :], theta, cond)
+        return _hook_torch(cls, HOOK["observe"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond)
 
     @classmethod
     def torch_precision(cls, y, theta, cond):
@@ -1634,12 +1560,12 @@ class GeneratedOdeModel(OdeModel):
         inst = cls.__new__(cls)
         y = y[:, :, :len(cls.species), :]
         if cls._observe_def is not None:
-            x = _observe_torch(cls, inst, y, theta, cond)
+            x = _hook_torch(cls, HOOK["observe"], inst, [y], theta, cond)
         else:
             fixed = OdeModel.__new__(OdeModel)  # (the fixed maps of OdeModel._observe_map read observe_kind only)
             fixed.__dict__["observe_kind"] = cls.observe_kind
             x = OdeModel._observe_map(fixed, y)
-        return _precision_torch(cls, inst, y, x, theta, cond)
+        return _hook_torch(cls, HOOK["precision"], inst, [y, x], theta, cond)
 
     @classmethod
     def torch_log_likelihood(cls, x, obs, prec, theta, cond):
@@ -1650,73 +1576,52 @@ class GeneratedOdeModel(OdeModel):
         if cls._likelihood_def is None:
             raise ModelDefinitionError("%s defines no log_likelihood(self, x, obs, pr, p, c): its observation log density is "
                                        "the Gaussian's" % cls.__name__)
-        ref = x[:, :, 0, :]
-        S = ref.shape[1]
-        inst = cls.__new__(cls)
-        tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
-        cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
-        thn = _Named([(n, theta[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
-        over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
-        p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
-        ob = obs.to(ref.dtype)[:, None].expand(x.shape)
-        pr = prec.to(ref.dtype).expand(x.shape)
-        ll = cls._likelihood_def(inst, list(torch.unbind(x, dim=2)), list(torch.unbind(ob, dim=2)), list(torch.unbind(pr, dim=2)),
-                                 p, _Conditions([over_time(v) for v in cs]))
-        full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
-        return torch.stack([full(v) for v in ll], dim=2)
+        obs, prec = obs.to(x.dtype)[:, None].expand(x.shape), prec.to(x.dtype).expand(x.shape)
+        return _hook_torch(cls, HOOK["log_likelihood"], cls.__new__(cls), [x, obs, prec], theta, cond)
 
     def _log_likelihood_map(self, x_predict, observations, precisions):
         """The model's own log density on tensors of the host paths (the host-driven adaptive route, the plugin fallback of
         Training.cost), with theta and the treatments of the last solve, as _observe_map: x_predict [B,S,4,T], observations
         [B,4,T], precisions broadcastable to x_predict -> [B,S,4,T]."""
-        if self._last_inputs is None:
-            raise RuntimeError("%s.log_likelihood reads theta and the treatments of the last solve, and nothing has been "
-                               "solved yet" % type(self).__name__)
-        packed, row_of, cond = self._last_inputs
-        dev = x_predict.device
-        theta = {n: packed[row_of[n]].to(dev) for n in type(self).parameter_names}
-        return type(self).torch_log_likelihood(x_predict, observations.to(dev), precisions, theta, cond.to(dev))
+        theta, cond = self._last_theta(x_predict.device, "%s.log_likelihood reads theta and the treatments of the last solve, and "
+                                       "nothing has been solved yet")
+        return type(self).torch_log_likelihood(x_predict, observations.to(x_predict.device), precisions, theta, cond)
 
     def _observe_map(self, x_sample):
         """OdeModel.observe on a tensor that is not the last solution: the model's own map (torch_observe) with theta and
         the treatments of the last solve."""
         if type(self)._observe_def is None:
             return super(GeneratedOdeModel, self)._observe_map(x_sample)
+        theta, cond = self._last_theta(x_sample.device, "%s.observe: the map reads theta and the treatments of the last solve, and "
+                                       "nothing has been solved yet")
+        return type(self).torch_observe(x_sample, theta, cond)
+
+    def _last_theta(self, dev, nothing_solved):
+        """({parameter name: [B,S]}, cond [B,C]) of the last solve on `dev`, for the host paths that evaluate a hook on
+        tensors that are not the last solution."""
         if self._last_inputs is None:
-            raise RuntimeError("%s.observe: the map reads theta and the treatments of the last solve, and nothing has been "
-                               "solved yet" % type(self).__name__)
+            raise RuntimeError(nothing_solved % type(self).__name__)
         packed, row_of, cond = self._last_inputs
-        theta = {n: packed[row_of[n]].to(x_sample.device) for n in type(self).parameter_names}
-        return type(self).torch_observe(x_sample, theta, cond.to(x_sample.device))
+        return {n: packed[row_of[n]].to(dev) for n in type(self).parameter_names}, cond.to(dev)
 
 
-def _observe_torch(cls, inst, y, th, cond):
-    """The class's map with torch ops: y [B,S,N,T], th {parameter name: [B,S]}, cond [B,C] -> [B,S,4,T]."""
-    ref = y[:, :, 0, :]
-    S = ref.shape[1]
-    tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
-    cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+def _treatments_torch(cls, cond, like, S):
+    """The treatments c of cond [B,C] (as the data holds it) in `like`'s dtype: C tensors [B,S]."""
+    tt = torch.clamp(torch.exp(cond.to(like.dtype)) - 1.0, 1e-12, 1e6)
+    return [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+
+
+def _hook_torch(cls, h, inst, groups, th, cond):
+    """The class's definition of hook h with torch ops in the dtype of its first group: groups of [B,S,.,T] tensors (in
+    the hook's order), th {parameter name: [B,S]} -- prepare is applied to it -- and cond [B,C] -> [B,S,4,T]."""
+    ref = groups[0][:, :, 0, :]
+    cs = _treatments_torch(cls, cond, ref, ref.shape[1])
     thn = _Named([(n, th[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
     over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
     p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
-    xp = cls._observe_def(inst, list(torch.unbind(y, dim=2)), p, _Conditions([over_time(v) for v in cs]))
+    out = getattr(cls, h.attr)(inst, *[list(torch.unbind(v, dim=2)) for v in groups], p, _Conditions([over_time(v) for v in cs]))
     full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
-    return torch.stack([full(v) for v in xp], dim=2)
-
-
-def _precision_torch(cls, inst, y, x, th, cond):
-    """The class's precision map with torch ops: y [B,S,N,T], x [B,S,4,T], th {parameter name: [B,S]}, cond [B,C] -> [B,S,4,T]."""
-    ref = y[:, :, 0, :]
-    S = ref.shape[1]
-    tt = torch.clamp(torch.exp(cond.to(ref.dtype)) - 1.0, 1e-12, 1e6)
-    cs = [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
-    thn = _Named([(n, th[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
-    over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
-    p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
-    pr = cls._precision_def(inst, list(torch.unbind(y, dim=2)), list(torch.unbind(x, dim=2)), p,
-                            _Conditions([over_time(v) for v in cs]))
-    full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
-    return torch.stack([full(v) for v in pr], dim=2)
+    return torch.stack([full(v) for v in out], dim=2)
 
 
 def _validate(cls):
