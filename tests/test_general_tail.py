@@ -176,7 +176,7 @@ def test_sampling_stage_inside_the_forward_launch(name, rng):
 def test_fused_forward_node_differentiates_through_autograd_too():
     """ops.ThetaOdeFused's own backward (a caller that runs loss.backward() on the fused forward's outputs): replays the unfused
     ops on the saved draws -- gradients of q's tables and the network weights against the unfused autograd path."""
-    from vihds import ops
+    from vihds.ode import THETA_ODE_FUSED, TRAIN, ForwardRequest
 
     fx = Fixture("relay_constant_precisions_tiny_modeuler")
     args, settings, model, training, batch = _build(fx, False)
@@ -185,13 +185,9 @@ def test_fused_forward_node_differentiates_through_autograd_too():
         np.random.seed(3)
         torch.manual_seed(3)
         model.zero_grad(set_to_none=True)
-        model._fuse_theta_ode = fused
-        try:
-            results, theta, q, p = model(batch, args.train_samples)
-        finally:
-            model._fuse_theta_ode = False
-        node = results.solution.logp_buffer.grad_fn
-        assert (type(node).__name__ == "ThetaOdeFusedBackward") == fused
+        results, theta, q, p = model(batch, args.train_samples, request=ForwardRequest(TRAIN, fuse_sampling=fused))
+        assert (results.solution.record.route == THETA_ODE_FUSED) == fused
+        assert results.solution.record.ode_node is results.solution.logp_buffer.grad_fn
         loss = training.cost(batch, results, theta, q, p).elbo
         loss.backward()
         outs.append((float(loss), {k: v.grad.detach().clone() for k, v in model.named_parameters() if v.grad is not None}))

@@ -162,6 +162,25 @@ def test_lookup_has_reference_keys():
         assert getattr(models.LOOKUP[k], "model_key", None) in hip.MODELS, k
 
 
+def test_every_model_takes_the_forward_request():
+    """Decoder.forward hands `request=` to simulate: every class of models.LOOKUP (the three overrides included) accepts the
+    keyword, after the reference's positional signature; a default-constructed request asks for nothing."""
+    import inspect
+
+    import models
+    from vihds.ode import PLAIN, PLAIN_FORWARD, ForwardRecord, ForwardRequest
+
+    for key, cls in models.LOOKUP.items():
+        params = inspect.signature(cls.simulate).parameters
+        assert list(params)[:8] == ["self", "config", "times", "theta", "conditions", "dev_1hot", "condition_on_device",
+                                    "observations"], key
+        assert "request" in params and params["request"].default is None, key
+    assert ForwardRequest() == PLAIN_FORWARD == (PLAIN, False, False, False)
+    with pytest.raises(AttributeError):  # (immutable: a request cannot be left set by accident)
+        PLAIN_FORWARD.general_tail = True
+    assert ForwardRecord() == (None, None, None, None, True, False, None)
+
+
 def test_device_conditioner_reproduces_reference_values():
     """aR/aS of the full fixture = 1 + relu(w . (dev_1hot * relevance)) with the reference's tiling quirk."""
     import e2e_util as E

@@ -21,10 +21,11 @@ class Degrader_Constant(OdeModel):
     def condition_theta(self, theta, dev_1hot, writer, epoch):
         return theta
 
-    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None):
+    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None,
+                 request=None):
         self.aR, self.aS = theta.aR, theta.aS
-        return super(Degrader_Constant, self).simulate(config, times, theta, conditions, dev_1hot,
-                                                       condition_on_device, observations)
+        return super(Degrader_Constant, self).simulate(config, times, theta, conditions, dev_1hot, condition_on_device,
+                                                       observations, request=request)
 
     def summaries(self, writer, epoch):
         variable_summaries(writer, epoch, self.aR, "aR.conditioned")

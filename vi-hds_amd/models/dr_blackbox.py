@@ -89,6 +89,12 @@ class DR_Blackbox(OdeModel):
             setattr(theta, pname, getattr(theta, pname) + offset[:, i: i + 1])
         return theta
 
+    def offset_source_row(self, names):
+        """The row of y1 among `names` when y1 .. y<n_y> sit back to back there (the one-launch form of condition_theta
+        inside a fused forward), else -1."""
+        rows = [names.index("y%d" % (i + 1)) if ("y%d" % (i + 1)) in names else -1 for i in range(self.n_y)]
+        return rows[0] if rows[0] >= 0 and rows == list(range(rows[0], rows[0] + self.n_y)) else -1
+
     def neural_weights(self):
         return self._flat(self.neural_states.weight_tensors() + self.precisions.weight_tensors())
 

@@ -26,10 +26,11 @@ class DR_Constant(OdeModel):
         """aR, aS = device_conditioner(ones) (reference dr_constant.py:124-131)."""
         return self.condition_ones(theta, ["aR", "aS"], dev_1hot)
 
-    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None):
+    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None,
+                 request=None):
         self.aR, self.aS = theta.aR, theta.aS
         return super(DR_Constant, self).simulate(config, times, theta, conditions, dev_1hot, condition_on_device,
-                                                 observations)
+                                                 observations, request=request)
 
     def summaries(self, writer, epoch):
         variable_summaries(writer, epoch, self.aR, "aR.conditioned")

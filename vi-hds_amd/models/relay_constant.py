@@ -26,10 +26,11 @@ class Relay_Constant(OdeModel):
         # aR / aS are ordinary (global_conditioned) parameters of the relay spec (relay_constant.py:69-70)
         return theta
 
-    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None):
+    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None,
+                 request=None):
         self.aR, self.aS = theta.aR, theta.aS
         return super(Relay_Constant, self).simulate(config, times, theta, conditions, dev_1hot, condition_on_device,
-                                                    observations)
+                                                    observations, request=request)
 
     def summaries(self, writer, epoch):
         variable_summaries(writer, epoch, self.aR, "aR.conditioned")

@@ -37,6 +37,21 @@ class LazyDecoderResult(DecoderResult):
         return 3
 
 
+def on_demand_result(ode_model, theta, times, solution, states=None):
+    """A LazyDecoderResult around `solution` (a DecodedSolution without x_predict, or a LazySolution): the tuple is built the
+    ordinary way, from `states` ([B,S,N,T]; default: the solution's own, materialised if need be), when somebody asks."""
+
+    def build():
+        x = solution.sol if states is None else states
+        xs, prec = ode_model.expand_precisions(theta, times, x)
+        return xs, ode_model.observe(x, theta), prec
+
+    result = LazyDecoderResult(build)
+    result.solution = solution
+    result.log_p_by_species = solution.log_p_by_species if solution.has_logp else None
+    return result
+
+
 class Decoder(nn.Module):
     def __init__(self, config, condition_on_device):
         super(Decoder, self).__init__()
@@ -47,42 +62,26 @@ class Decoder(nn.Module):
         self.condition_on_device = condition_on_device
         self.config = config
 
-    def forward(self, theta, data, writer, epoch):
+    def forward(self, theta, data, writer, epoch, request=None):
         if self.condition_on_device:
             theta_conditioned = self.ode_model.condition_theta(theta, data.dev_1hot, writer, epoch)
         else:
             theta_conditioned = theta
         fused = self.ode_model.solve_for_training(self.config, data.times, theta_conditioned, data.inputs,
-                                                  data.dev_1hot, data.get("observations", None))
-        if fused is not None:  # log-likelihood + unit-weight adjoint in one launch; the rest only on demand
-
-            def build():
-                full = fused.full()
-                xs, prec = self.ode_model.expand_precisions(theta_conditioned, data.times, full.sol)
-                return xs, self.ode_model.observe(full.sol, theta_conditioned), prec
-
-            result = LazyDecoderResult(build)
-            result.solution = fused
-            result.log_p_by_species = fused.log_p_by_species
-            return result, theta_conditioned
+                                                  data.dev_1hot, data.get("observations", None), request=request)
+        if fused is not None:  # the log-likelihood without the trajectory's round trip; the rest only on demand
+            return on_demand_result(self.ode_model, theta_conditioned, data.times, fused), theta_conditioned
         solution = self.ode_model.simulate(
             self.config, data.times, theta_conditioned, data.inputs, data.dev_1hot,
-            condition_on_device=self.condition_on_device, observations=data.get("observations", None),
-        )
+            condition_on_device=self.condition_on_device, observations=data.get("observations", None), request=request)
         last = self.ode_model._last
         if writer is not None:
             self.ode_model.summaries(writer, epoch)
-        if not getattr(last, "has_x_predict", True):  # params.lazy_x_predict under no_grad: the tuple on demand
-
-            def build_eval():
-                xs, prec = self.ode_model.expand_precisions(theta_conditioned, data.times, solution)
-                return xs, self.ode_model.observe(solution, theta_conditioned), prec
-
-            result = LazyDecoderResult(build_eval)
-        else:
-            x_states, precisions = self.ode_model.expand_precisions(theta_conditioned, data.times, solution)
-            x_predict = self.ode_model.observe(solution, theta_conditioned)
-            result = DecoderResult((x_states, x_predict, precisions))
+        if not getattr(last, "has_x_predict", True):  # params.lazy_x_predict: the tuple on demand
+            return on_demand_result(self.ode_model, theta_conditioned, data.times, last, solution), theta_conditioned
+        x_states, precisions = self.ode_model.expand_precisions(theta_conditioned, data.times, solution)
+        x_predict = self.ode_model.observe(solution, theta_conditioned)
+        result = DecoderResult((x_states, x_predict, precisions))
         result.solution = last
         result.log_p_by_species = last.log_p_by_species if getattr(last, "has_logp", False) else None
         return result, theta_conditioned

@@ -31,6 +31,7 @@ class DotOperatorSamples(object):
         object.__setattr__(self, "_rebound", {})
         object.__setattr__(self, "_log_prob_cache", {})
         object.__setattr__(self, "_u", None)
+        object.__setattr__(self, "_node", None)  # autograd node of the packed sampling launch these samples came out of
         object.__setattr__(self, "_sample_window", None)  # (S_total, s_offset) when S is sharded over ranks
         object.__setattr__(self, "_row_offset", None)  # (offset [B,n], (src, dst, n)): see ops.OdeSolveObserve
 
@@ -239,6 +240,7 @@ class ChainedDistribution(object):
         self.slot_dependencies = OrderedDict()
         self._image = None      # (kind_dev, mu_PB, prec_PB)
         self._packed_q = None   # (kind_dev, q_all [2P,B] = [mu ; log_prec], names) supplied by the Encoder
+        self._enc_node = None   # ops.EncoderQTables' autograd node when q_all came out of that launch
         self._builder = None    # fills _distributions on first use (the hot path never needs the member objects)
         self._clip_cache = {}
 
@@ -260,13 +262,14 @@ class ChainedDistribution(object):
     def attach_image(self, kind_dev, mu, prec):
         self._image = (kind_dev, mu, prec)
 
-    def attach_packed(self, kind_dev, q_all, names, builder, q_rows=None):
+    def attach_packed(self, kind_dev, q_all, names, builder, q_rows=None, enc_node=None):
         """q_all [2P,B]: means and log-precisions; q_rows [2P] (int32, device): the row of mu_p, then of log_prec_p
-        (None: [mu rows ; log_prec rows])."""
+        (None: [mu rows ; log_prec rows]); enc_node: q_all.grad_fn where ops.EncoderQTables produced it."""
         P = len(names)
         if q_rows is None:
             q_rows = torch.arange(2 * P, dtype=torch.int32, device=q_all.device)
         self._packed_q = (kind_dev, q_all, list(names))
+        self._enc_node = enc_node
         self._q_rows = q_rows
         self._builder = builder
 
@@ -339,8 +342,9 @@ class ChainedDistribution(object):
             lo, hi = p.clip_image(stddevs, dev)
         return names, P, p_mu, p_prec, lo, hi
 
-    def _wrap_samples(self, names, theta, log_q, log_p, p, u_used):
+    def _wrap_samples(self, names, theta, log_q, log_p, p, u_used, node=None):
         samples = DotOperatorSamples.from_packed(names, theta)
+        object.__setattr__(samples, "_node", node)
         # the standard-normal draws behind these samples (an output when the kernel drew them)
         object.__setattr__(samples, "_u", u_used)
         samples._log_prob_cache[id(self)] = log_q
@@ -361,12 +365,13 @@ class ChainedDistribution(object):
             kind, q_all, _ = self._packed_q
             theta, log_q, log_p, u_used = ops.ThetaSampleLogProbPacked.apply(q_all, kind, p_mu, p_prec, lo, hi,
                                                                              list_of_u, P + n_extra_rows, self._q_rows)
+            node = theta.grad_fn
         else:
             kind, q_mu, q_prec = self.image(dev, n_batch)
             theta, log_q, log_p = ops.ThetaSampleLogProb.apply(q_mu, q_prec, kind, p_mu, p_prec, lo, hi, list_of_u,
                                                                P + n_extra_rows)
-            u_used = list_of_u
-        return self._wrap_samples(names, theta, log_q, log_p, p, u_used)
+            u_used, node = list_of_u, None
+        return self._wrap_samples(names, theta, log_q, log_p, p, u_used, node)
 
     def decoder_step_fused(self, list_of_u, p, stddevs, n_extra_rows, spec_of, cond, times, obs, dev1hot, cond_job):
         """sample_clip_log_prob AND the decoder (conditioner rows, log-likelihood, unit-weight adjoint) in one launch
@@ -393,7 +398,7 @@ class ChainedDistribution(object):
         theta, log_q, log_p, u_used, traj, logp = ops.ThetaOdeFused.apply(
             q_all, kind, p_mu, p_prec, lo, hi, list_of_u, P + n_extra_rows, self._q_rows, spec_of(names), cond, times, obs,
             dev1hot, weights, off_w, off_b, off_rows)
-        return self._wrap_samples(names, theta, log_q, log_p, p, u_used), traj, logp
+        return self._wrap_samples(names, theta, log_q, log_p, p, u_used, theta.grad_fn), traj, logp
 
     # ---- reference-compatible entry points -------------------------------------------------------------
     def sample(self, list_of_u, device, stop_grad=False):

@@ -220,7 +220,8 @@ class Encoder(nn.Module):
                 self._shapes[B] = None
             else:
                 q = ChainedDistribution(name="q")
-                q.attach_packed(self.kind, q_all, self.names, lambda chain: self._build_members(chain, q_all), self.q_rows)
+                q.attach_packed(self.kind, q_all, self.names, lambda chain: self._build_members(chain, q_all), self.q_rows,
+                                enc_node=q_all.grad_fn)
                 return q
         encoded = self.conditional(delta_obs)
         local_t = gcond_t = None

@@ -4,9 +4,10 @@
 loop -- and, fused in the same kernel, observe + the Gaussian log-likelihood -- as ONE HIP kernel
 (vihds_ode_fwd) with a hand-written discrete adjoint (vihds_ode_bwd).  There is no torchdiffeq and no CPU path.
 """
-import numpy as np
 import math
+from collections import namedtuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -14,13 +15,36 @@ from vihds import ops
 from vihds.utils import default_get_value
 
 
+PLAIN, TRAIN, EVALUATE = "plain", "train", "evaluate"
+
+# What the caller will do with a forward, passed down as `request=` (None: PLAIN_FORWARD, a call that asks for nothing):
+# purpose; general_tail: the step's backward is ops.GeneralTail, so nobody reads x_predict; fuse_sampling: the sampling
+# stage may run inside the forward launch; online_summaries: the summaries-on-the-way evaluation form is allowed
+ForwardRequest = namedtuple("ForwardRequest", "purpose general_tail fuse_sampling online_summaries",
+                            defaults=(PLAIN, False, False, False))
+PLAIN_FORWARD = ForwardRequest()
+
+# the routes that produce a log-likelihood, named by the ops entry that launches them
+DECODER_STEP_FUSED, THETA_ODE_FUSED, ODE_SOLVE_OBSERVE, ODE_LOGLIK_FUSED, ODE_LOGP_ONLY, ADAPTIVE_HOST, ADAPTIVE_DEVICE = (
+    "DecoderStepFused", "ThetaOdeFused", "OdeSolveObserve", "OdeLogLikFused", "ode_logp_only", "adaptive_grid",
+    "AdaptiveOdeSolve")
+GENERAL_TAIL = "GeneralTail"  # (not a forward route: the key of the step tail's declines in the same cache)
+
+# What a forward ran, written where it is known and handed to the solution's constructor: the route, its autograd nodes
+# (the outputs' grad_fn at the .apply call site; theta_node: the sampling launch's, ThetaOdeFused's own node when it held
+# the sampling stage), the generator state a fused forward left for the tail to step, and what Training.cost may do
+ForwardRecord = namedtuple("ForwardRecord", "route ode_node theta_node rng_state has_logp defer_iwae online_summaries",
+                           defaults=(None, None, None, None, True, False, None))
+
+
 class DecodedSolution(object):
     """What one fused kernel launch produced for a batch: views in the reference's layouts."""
 
-    def __init__(self, traj, xpred, logp, observe=None):
+    def __init__(self, traj, xpred, logp, record, observe=None):
         self.traj_buffer, self._xpred, self.logp_buffer = traj, xpred, logp  # [T,N,B,S], [T,4,B,S], [4,B,S]
         self.sol = traj.permute(2, 3, 1, 0)          # [B,S,N,T]  (reference ode.py:82)
         self.log_p_by_species = logp.permute(1, 2, 0)  # [B,S,4] (reference training.py:24-33)
+        self.record, self.has_logp, self.online_summaries = record, record.has_logp, record.online_summaries
         self._observe = observe  # xpred None (params.lazy_x_predict): the map that forms it from `sol` if somebody asks
 
     @property
@@ -42,10 +66,10 @@ class LazySolution(object):
     """What the fused training kernel produced: the per-species log-likelihood only.  Trajectory and x_predict are
     computed (by the ordinary forward kernel, as a fresh autograd node on the same theta) if and when somebody asks."""
 
-    def __init__(self, logp, materialise):
+    def __init__(self, logp, record, materialise):
         self.logp_buffer = logp
         self.log_p_by_species = logp.permute(1, 2, 0)
-        self.has_logp = True
+        self.record, self.has_logp, self.online_summaries = record, record.has_logp, record.online_summaries
         self._materialise, self._full = materialise, None
 
     def full(self):
@@ -57,6 +81,72 @@ class LazySolution(object):
     xpred_buffer = property(lambda self: self.full().xpred_buffer)
     sol = property(lambda self: self.full().sol)
     x_predict = property(lambda self: self.full().x_predict)
+
+
+def sampling_route(request, vae, q, data, samples):
+    """The launch that holds the sampling stage of a forward under autograd -- DECODER_STEP_FUSED or THETA_ODE_FUSED -- or
+    None: the sampling kernel on its own, then the decoder (likelihood_route).  A route that raises
+    ops.FusedTrainingUnsupported is entered into `_fused_declined` by BaseVAE.forward, which asks again."""
+    import vihds.hip as hip
+
+    ode, prm = vae.decoder.ode_model, vae.decoder.config.params
+    obs = data.get("observations", None) if hasattr(data, "get") else None
+    if (not torch.is_grad_enabled() or obs is None or not obs.is_cuda or getattr(q, "_packed_q", None) is None
+            or prm.solver in hip.ADAPTIVE_SOLVERS):
+        return None
+    declined, shape = ode._fused_declined, (tuple(obs.shape), samples, prm.solver)
+    if (default_get_value(prm, "fused_ode_training", True) and default_get_value(prm, "fused_decoder_step", True)
+            and ode.model_key in ode.fused_training_keys and not declined.get((DECODER_STEP_FUSED,) + shape)):
+        return DECODER_STEP_FUSED
+    # the models whose forward kernels carry the sampling stage: relay / degrader / prpr / auto_constant (+ _precisions) --
+    # a device conditioner is no stage of theirs -- and dr_blackbox at the built-in sizes, whose condition_theta is one when
+    # it runs on the device and the offset layer's source rows sit back to back
+    if not request.fuse_sampling or vae.shard is not None or declined.get((THETA_ODE_FUSED,) + shape):
+        return None
+    if ode.model_key != "dr_blackbox":
+        return None if getattr(ode, "extra_theta_names", ()) else THETA_ODE_FUSED
+    if ode.n_y > 0 and (not vae.decoder.condition_on_device or ode.offset_source_row(q.names()) < 0):
+        return None
+    return THETA_ODE_FUSED
+
+
+def likelihood_route(request, ode, config, theta, times, observations):
+    """(route, packed theta, spec) of a forward once theta is sampled.  Under autograd ODE_LOGLIK_FUSED where the model has
+    that launch; under no_grad ODE_LOGP_ONLY, the summaries-on-the-way form, which is opt-in per call (Training.evaluate
+    asks for it): any other forward under no_grad -- plots, xval scripts, plugin code that reads x_states / x_predict --
+    keeps the stored trajectory, for which the lazy solution's full solve would be a THIRD integration.  Otherwise
+    (ODE_SOLVE_OBSERVE, None, None): the ordinary forward.  theta is packed only where a route gets that far."""
+    import vihds.hip as hip
+
+    prm, grad, plain = config.params, torch.is_grad_enabled(), (ODE_SOLVE_OBSERVE, None, None)
+    if grad:
+        fits = ode.model_key in ode.fused_training_keys and default_get_value(prm, "fused_ode_training", True)
+    else:
+        fits = (request.purpose == EVALUATE and request.online_summaries and default_get_value(prm, "online_summaries", True)
+                and default_get_value(prm, "lazy_x_predict", True) and not getattr(theta, "_row_offset", None))
+    if not fits or observations is None or prm.solver in hip.ADAPTIVE_SOLVERS:
+        return plain
+    packed, row_of = theta.pack(ode.kernel_slots())
+    if not packed.is_cuda or (grad and not packed.requires_grad):
+        return plain
+    spec, shape = ode._spec(config, row_of, packed.shape[0]), (packed.shape[1], packed.shape[2], times.shape[0])
+    if grad:
+        fits = not ode._fused_declined.get((ODE_LOGLIK_FUSED,) + shape + (prm.solver,))
+    else:
+        fits = ops.ode_fwd_summaries_supported(spec, *shape)
+    return (ODE_LOGLIK_FUSED if grad else ODE_LOGP_ONLY, packed, spec) if fits else plain
+
+
+def x_predict_on_demand(request, ode, config):
+    """Whether the ordinary forward leaves x_predict to whoever asks for it.  Evaluation passes (no graph to differentiate)
+    do: Training.cost's summaries form it inside their kernel, plugin code reading DecoderResult gets it from the
+    observation map; so do training steps whose backward is ops.GeneralTail (request.general_tail): nobody reads it there.
+    A map of the model's own -- observe_kind "custom", vihds/modelgen.py -- exists in its kernels only and may read theta:
+    such a model always stores x_predict, and the summaries take it from that buffer; so does a model with a precision map
+    of its own -- its precision rows go to vihds_iw_summaries, which takes x_predict as a buffer."""
+    return ((not torch.is_grad_enabled() or request.general_tail)
+            and bool(default_get_value(config.params, "lazy_x_predict", True)) and ode.observe_kind != "custom"
+            and ode.precision_kind != "custom")
 
 
 class DeviceConditioner(nn.Module):
@@ -101,7 +191,7 @@ class OdeModel(nn.Module):
         self._tile_index = {}
         self._relevance_dev = {}
         self._rng_state = None
-        self._fused_unsupported = {}
+        self._fused_declined = {}  # (route, shape...) -> True: what a launch has declined once is not asked for again
         self._last = None
         self._last_inputs = None  # (packed theta, row_of, treatments) of the last solve: what a custom observation map reads
 
@@ -235,11 +325,12 @@ class OdeModel(nn.Module):
                                                        C=self.n_treatments, D=self.device_depth, **kw)
         return self._spec_cache[key]
 
-    def solve(self, config, times, theta, conditions, dev_1hot, observations=None):
+    def solve(self, config, times, theta, conditions, dev_1hot, observations=None, request=None):
         """One fused launch: trajectory, observed signals and (if observations are given) the per-species
         log-likelihood.  Returns a DecodedSolution."""
         import vihds.hip as hip
 
+        request = request or PLAIN_FORWARD
         slots = self.kernel_slots()
         packed, row_of = theta.pack(slots)
         self._last_inputs = (packed, row_of, conditions)
@@ -252,69 +343,35 @@ class OdeModel(nn.Module):
         if obs is None:  # likelihood not requested: feed zeros (logp output is then meaningless and unused)
             obs = torch.zeros((packed.shape[1], 4, times.shape[0]), device=dev)
         row_offset, row_offset_map = getattr(theta, "_row_offset", None) or (None, None)
-        # evaluation passes (no graph to differentiate) leave x_predict to whoever asks for it: Training.cost's summaries
-        # form it inside their kernel, plugin code reading DecoderResult gets it from the map below
-        # (... and so do training steps whose backward is ops.GeneralTail: nobody reads x_predict there)
-        # (a map of the model's own -- observe_kind "custom", vihds/modelgen.py -- exists in its kernels only and may read
-        # theta: such a model always stores x_predict, and the summaries take it from that buffer; so does a model with a
-        # precision map of its own -- its precision rows go to vihds_iw_summaries, which takes x_predict as a buffer)
-        lazy = ((not torch.is_grad_enabled() or getattr(self, "_train_without_x_predict", False))
-                and bool(default_get_value(config.params, "lazy_x_predict", True)) and self.observe_kind != "custom"
-                and self.precision_kind != "custom")
+        lazy = x_predict_on_demand(request, self, config)
         traj, xpred, logp = ops.OdeSolveObserve.apply(spec, packed, conditions.to(dev), times, obs.to(dev),
                                                       dev_1hot.to(dev) if dev_1hot is not None else None,
                                                       self.neural_weights(), row_offset, row_offset_map, not lazy)
-        self._last = DecodedSolution(traj, xpred, logp, observe=lambda sol: self._observe_map(sol))
-        self._last.has_logp = observations is not None
+        record = ForwardRecord(ODE_SOLVE_OBSERVE, logp.grad_fn, getattr(theta, "_node", None),
+                               has_logp=observations is not None)
+        self._last = DecodedSolution(traj, xpred, logp, record, observe=lambda sol: self._observe_map(sol))
         return self._last
 
-    def _solve_adaptive(self, config, spec, packed, row_of, times, theta, conditions, dev_1hot, observations):
-        """torchdiffeq's adaptive pairs (reference ode.py:79-81; dopri5 / bosh3 / adaptive_heun): the controller picks ONE
-        accepted grid for the batch (ops.adaptive_grid), the ordinary kernels integrate on it with the pair's
-        higher-order tableau, the rows of the output times are gathered, and the log-likelihood (observations exist at
-        the output times only) is evaluated with torch ops on the gathered x_predict -- autograd then hands the adjoint
-        kernel upstream gradients for the trajectory / x_predict on the accepted grid."""
-        dev = packed.device
-        cond = conditions.to(dev)
-        d1 = dev_1hot.to(dev) if dev_1hot is not None else None
-        weights = self.neural_weights()
-        rtol = float(default_get_value(config.params, "solver_rtol", 1e-7))  # torchdiffeq.odeint defaults
-        atol = float(default_get_value(config.params, "solver_atol", 1e-9))
-        # The accepted grid lives in a caller-sized buffer: params.solver_max_grid (default 4096 points); when the controller
-        # runs out of it the buffer is quadrupled up to 2^17 points before giving up with a message that names the cause --
-        # all arithmetic is fp32, so tolerances near its epsilon (torchdiffeq's defaults 1e-7 / 1e-9 with a low-order pair
-        # such as adaptive_heun) ask for step sizes the state cannot resolve
-        max_grid = int(default_get_value(config.params, "solver_max_grid", 4096))
-        # torchdiffeq's own algorithm, resident on the device (round 4): steps run past the output times, outputs come from
-        # the accepted step's quartic interpolant, the adjoint walks the logged accepted steps -- models without shared
-        # neural weights; params.adaptive_device: false keeps the clipped-grid controller below for them too
-        B, S = packed.shape[1], packed.shape[2]
-        # (round 5: also the *_precisions models without a hidden layer -- the library says which problems it takes)
-        if (bool(default_get_value(config.params, "adaptive_device", True))
-                and ops.adaptive_device_supported(spec, B, S, int(times.shape[0]), max_grid) is not None):
-            return self._solve_adaptive_device(config, spec, packed, row_of, times, cond, d1, observations, rtol, atol, max_grid,
-                                               weights)
+    @staticmethod
+    def _with_room(config, rtol, atol, size, overflow, run):
+        """run(size), with the caller-sized buffer quadrupled up to 2^17 points while run raises `overflow(exc)`: only the
+        controller running out of its buffer is worth a larger one; anything else is re-raised as it is."""
         while True:
             try:
-                grid, index = ops.adaptive_grid(spec, packed, cond, times, d1, weights, rtol, atol, max_grid=max_grid)
-                break
+                return run(size)
             except RuntimeError as e:
-                # only the controller running out of its buffer is worth a larger one (the C ABI's message for that exact
-                # condition); step-size underflow, a non-finite error estimate or bad arguments are re-raised as they are
-                if "does not fit max_grid" not in str(e):
+                if not overflow(e):
                     raise
-                if max_grid >= (1 << 17):
+                if size >= (1 << 17):
                     raise RuntimeError(
                         "solver %r with rtol=%g, atol=%g needs more than %d accepted steps on this batch: in fp32 a relative "
                         "tolerance below ~1e-6 is at rounding level for a low-order pair -- raise params.solver_rtol / "
-                        "solver_atol (or params.solver_max_grid)" % (config.params.solver, rtol, atol, max_grid)) from e
-                max_grid *= 4
-        self.last_adaptive_grid = grid
-        dummy = torch.zeros((packed.shape[1], 4, grid.shape[0]), device=dev)
-        row_offset, row_offset_map = getattr(theta, "_row_offset", None) or (None, None)
-        traj_g, xpred_g, _ = ops.OdeSolveObserve.apply(spec, packed, cond, grid, dummy, d1, weights, row_offset,
-                                                       row_offset_map)
-        traj, xpred = traj_g.index_select(0, index), xpred_g.index_select(0, index)  # [T,N,B,S], [T,4,B,S]
+                        "solver_atol (or params.solver_max_grid)" % (config.params.solver, rtol, atol, size)) from e
+                size *= 4
+
+    def _adaptive_solution(self, route, spec, packed, row_of, traj, xpred, observations):
+        """The DecodedSolution of an adaptive route: the log-likelihood at the output times with torch ops (observations
+        exist there only) from the precision rows -- autograd then hands the adjoint kernel its upstream gradients."""
         if observations is not None:
             if spec.n_species < spec.n_states:  # neural precisions: the last four states (reference precisions.py:89-94)
                 prec = traj[:, spec.n_species:, :, :]
@@ -327,121 +384,108 @@ class OdeModel(nn.Module):
                 ll = self._log_likelihood_map(xpred.permute(2, 3, 1, 0), observations, prec.permute(2, 3, 1, 0))
                 logp = ll.sum(3).permute(2, 0, 1)
             else:
-                err = xpred - observations.to(dev).permute(2, 1, 0)[:, :, :, None]
+                err = xpred - observations.to(packed.device).permute(2, 1, 0)[:, :, :, None]
                 logp = (-0.5 * (math.log(2 * math.pi) - torch.log(prec) + prec * err * err)).sum(0)  # training.py:24-44
         else:
-            logp = torch.zeros((4,) + tuple(packed.shape[1:]), device=dev)
-        self._last = DecodedSolution(traj, xpred, logp)
-        self._last.has_logp = observations is not None
+            logp = torch.zeros((4,) + tuple(packed.shape[1:]), device=packed.device)
+        self._last = DecodedSolution(traj, xpred, logp, ForwardRecord(route, has_logp=observations is not None))
         return self._last
+
+    def _solve_adaptive(self, config, spec, packed, row_of, times, theta, conditions, dev_1hot, observations):
+        """torchdiffeq's adaptive pairs (reference ode.py:79-81; dopri5 / bosh3 / adaptive_heun): the controller picks ONE
+        accepted grid for the batch (ops.adaptive_grid), the ordinary kernels integrate on it with the pair's
+        higher-order tableau, the rows of the output times are gathered, and the log-likelihood is evaluated on the
+        gathered x_predict (_adaptive_solution)."""
+        dev = packed.device
+        cond = conditions.to(dev)
+        d1 = dev_1hot.to(dev) if dev_1hot is not None else None
+        weights = self.neural_weights()
+        rtol = float(default_get_value(config.params, "solver_rtol", 1e-7))  # torchdiffeq.odeint defaults
+        atol = float(default_get_value(config.params, "solver_atol", 1e-9))
+        # The accepted grid lives in a caller-sized buffer: params.solver_max_grid (default 4096 points); when the controller
+        # runs out of it the buffer is quadrupled (_with_room) before giving up with a message that names the cause --
+        # all arithmetic is fp32, so tolerances near its epsilon (torchdiffeq's defaults 1e-7 / 1e-9 with a low-order pair
+        # such as adaptive_heun) ask for step sizes the state cannot resolve
+        max_grid = int(default_get_value(config.params, "solver_max_grid", 4096))
+        # torchdiffeq's own algorithm, resident on the device (round 4): steps run past the output times, outputs come from
+        # the accepted step's quartic interpolant, the adjoint walks the logged accepted steps -- models without shared
+        # neural weights; params.adaptive_device: false keeps the clipped-grid controller below for them too
+        B, S = packed.shape[1], packed.shape[2]
+        # (round 5: also the *_precisions models without a hidden layer -- the library says which problems it takes)
+        if (bool(default_get_value(config.params, "adaptive_device", True))
+                and ops.adaptive_device_supported(spec, B, S, int(times.shape[0]), max_grid) is not None):
+            return self._solve_adaptive_device(config, spec, packed, row_of, times, cond, d1, observations, rtol, atol, max_grid,
+                                               weights)
+        # (the C ABI's message for the controller running out of its buffer; step-size underflow, a non-finite error estimate
+        # or bad arguments are re-raised as they are)
+        grid, index = self._with_room(
+            config, rtol, atol, max_grid, lambda e: "does not fit max_grid" in str(e),
+            lambda n: ops.adaptive_grid(spec, packed, cond, times, d1, weights, rtol, atol, max_grid=n))
+        self.last_adaptive_grid = grid
+        dummy = torch.zeros((packed.shape[1], 4, grid.shape[0]), device=dev)
+        row_offset, row_offset_map = getattr(theta, "_row_offset", None) or (None, None)
+        traj_g, xpred_g, _ = ops.OdeSolveObserve.apply(spec, packed, cond, grid, dummy, d1, weights, row_offset,
+                                                       row_offset_map)
+        traj, xpred = traj_g.index_select(0, index), xpred_g.index_select(0, index)  # [T,N,B,S], [T,4,B,S]
+        return self._adaptive_solution(ADAPTIVE_HOST, spec, packed, row_of, traj, xpred, observations)
 
     def _solve_adaptive_device(self, config, spec, packed, row_of, times, cond, d1, observations, rtol, atol, max_steps,
                                weights=None):
-        """ops.AdaptiveOdeSolve + the observation map and the Gaussian log-likelihood with torch ops on the solution at the
-        output times (autograd hands the adjoint kernel the upstream gradient of the trajectory)."""
+        """ops.AdaptiveOdeSolve + the observation map and the log-likelihood with torch ops on the solution at the output
+        times (autograd hands the adjoint kernel the upstream gradient of the trajectory)."""
         check = bool(default_get_value(config.params, "adaptive_check", True))  # False: no synchronisation (capturable)
         stats = [0, 0, 0]
-        while True:
-            try:
-                traj = ops.AdaptiveOdeSolve.apply(spec, packed, cond, times, d1, rtol, atol, max_steps, check, stats, weights)
-                break
-            except ops.GridOverflow as e:
-                if max_steps >= (1 << 17):
-                    raise RuntimeError(
-                        "solver %r with rtol=%g, atol=%g needs more than %d accepted steps on this batch: in fp32 a relative "
-                        "tolerance below ~1e-6 is at rounding level for a low-order pair -- raise params.solver_rtol / "
-                        "solver_atol (or params.solver_max_grid)" % (config.params.solver, rtol, atol, max_steps)) from e
-                max_steps *= 4
+        traj = self._with_room(
+            config, rtol, atol, max_steps, lambda e: isinstance(e, ops.GridOverflow),
+            lambda n: ops.AdaptiveOdeSolve.apply(spec, packed, cond, times, d1, rtol, atol, n, check, stats, weights))
         self.last_adaptive_stats = {"accepted": stats[1], "rejected": stats[2]}
         self.last_adaptive_grid = None
-        sol = traj.permute(2, 3, 1, 0)                               # [B,S,N,T]
-        xpred = self._observe_map(sol).permute(3, 2, 0, 1)           # [T,4,B,S]
-        dev = packed.device
-        if observations is not None:
-            if spec.n_species < spec.n_states:  # neural precisions: the last four states (reference precisions.py:89-94)
-                prec = traj[:, spec.n_species:, :, :]
-            else:
-                rows = [row_of[n] for n in spec.slots[-4:]]          # constant precisions (reference precisions.py:31-35)
-                prec = packed[rows][None]
-            err = xpred - observations.to(dev).permute(2, 1, 0)[:, :, :, None]
-            logp = (-0.5 * (math.log(2 * math.pi) - torch.log(prec) + prec * err * err)).sum(0)  # training.py:24-44
-        else:
-            logp = torch.zeros((4,) + tuple(packed.shape[1:]), device=dev)
-        self._last = DecodedSolution(traj, xpred.contiguous(), logp)
-        self._last.has_logp = observations is not None
-        return self._last
+        xpred = self._observe_map(traj.permute(2, 3, 1, 0)).permute(3, 2, 0, 1).contiguous()  # [B,S,N,T] -> [T,4,B,S]
+        return self._adaptive_solution(ADAPTIVE_DEVICE, spec, packed, row_of, traj, xpred, observations)
 
     fused_training_keys = ("dr_constant", "dr_constant_v2")
 
-    def solve_for_training(self, config, times, theta, conditions, dev_1hot, observations):
-        """Training fast path (params.fused_ode_training): ONE launch gives the log-likelihood and the unit-weight
-        adjoint (ops.OdeLogLikFused); returns a LazySolution, or None when the path does not apply (then use solve)."""
-        import vihds.hip as hip
-
-        if observations is not None and not torch.is_grad_enabled():
-            return self._solve_for_evaluation(config, times, theta, conditions, dev_1hot, observations)
-        if (observations is None or self.model_key not in self.fused_training_keys or not torch.is_grad_enabled()
-                or not default_get_value(config.params, "fused_ode_training", True)
-                or config.params.solver in hip.ADAPTIVE_SOLVERS):
-            return None
-        slots = self.kernel_slots()
-        packed, row_of = theta.pack(slots)
-        if not packed.is_cuda or not packed.requires_grad:
-            return None
-        spec = self._spec(config, row_of, packed.shape[0])
-        key = (packed.shape[1], packed.shape[2], times.shape[0], config.params.solver)
-        if self._fused_unsupported.get(key):
+    def solve_for_training(self, config, times, theta, conditions, dev_1hot, observations, request=None):
+        """The forward that leaves the trajectory out, where the request and the model allow one (likelihood_route): under autograd ONE launch gives the log-likelihood and the unit-weight adjoint
+        (params.fused_ode_training, ops.OdeLogLikFused); under no_grad the evaluation without the trajectory's round trip
+        (_solve_for_evaluation).  Returns a LazySolution, or None when neither applies (then use solve)."""
+        route, packed, spec = likelihood_route(request or PLAIN_FORWARD, self, config, theta, times, observations)
+        if route == ODE_SOLVE_OBSERVE:
             return None
         dev = packed.device
-        args = (spec, packed, conditions.to(dev), times.to(dev), observations.to(dev),
-                dev_1hot.to(dev) if dev_1hot is not None else None)
+        args = (packed, conditions.to(dev), times.to(dev), dev_1hot.to(dev) if dev_1hot is not None else None)
+        full = lambda: self.solve(config, times, theta, conditions, dev_1hot, observations)  # noqa: E731
+        if route == ODE_LOGP_ONLY:
+            return self._solve_for_evaluation(spec, args + (self.neural_weights(),), observations.to(dev), full)
         try:
-            logp = ops.OdeLogLikFused.apply(*args)
+            logp = ops.OdeLogLikFused.apply(spec, args[0], args[1], args[2], observations.to(dev), args[3])
         except ops.FusedTrainingUnsupported:
-            self._fused_unsupported[key] = True
+            self._fused_declined[(route, packed.shape[1], packed.shape[2], times.shape[0], config.params.solver)] = True
             return None
-        self._last = LazySolution(logp, lambda: self.solve(config, times, theta, conditions, dev_1hot, observations))
+        self._last = LazySolution(logp, ForwardRecord(route, logp.grad_fn), full)
         return self._last
 
-    def _solve_for_evaluation(self, config, times, theta, conditions, dev_1hot, observations):
+    def _solve_for_evaluation(self, spec, args, observations, full):
         """Evaluation without the trajectory's round trip (params.online_summaries, default on): the forward launch writes
         the log-likelihoods ONLY, and Results' importance-weighted summaries come from a second forward launch that adds
         them up on the way (ops.ode_fwd_summaries) -- the trajectory (644 MB at 234 rows x 1 000 samples) is neither
         allocated, written nor read back: 1.33 GB -> 0.12 GB of HBM traffic for the two launches, at the same time per pass
         (0.68 ms either way: the integration is VALU-bound, the second one costs what streaming the trajectory back did;
         DESIGN.md section 1; profiles/LOG.md, round 5).  `online_summaries: false` keeps the stored form.
-        Returns a LazySolution carrying `online_summaries(log_w, lse)`; trajectory and x_predict are computed (the ordinary
-        forward launch) only if somebody asks.  None where the path does not apply (dr_blackbox, the adaptive solvers,
-        launches below the evaluation size, which run other kernel families): then use solve."""
-        import vihds.hip as hip
-
-        # (opt-in per call: Training.evaluate sets `_evaluating` around its passes.  Any other forward under no_grad -- plots, xval
-        # scripts, plugin code that reads x_states / x_predict -- keeps the stored trajectory: for it the lazy solution's full
-        # solve would be a THIRD integration; ADVICE r05)
-        if (not getattr(self, "_evaluating", False)
-                or not default_get_value(config.params, "online_summaries", True) or not default_get_value(config.params, "lazy_x_predict", True)
-                or config.params.solver in hip.ADAPTIVE_SOLVERS or getattr(theta, "_row_offset", None)
-                or getattr(self, "_no_online_summaries", False)):  # (Training: samples sharded over ranks)
-            return None
-        packed, row_of = theta.pack(self.kernel_slots())
-        if not packed.is_cuda:
-            return None
-        spec = self._spec(config, row_of, packed.shape[0])
-        if not ops.ode_fwd_summaries_supported(spec, packed.shape[1], packed.shape[2], times.shape[0]):
-            return None
-        dev = packed.device
-        args = (packed, conditions.to(dev), times.to(dev), dev_1hot.to(dev) if dev_1hot is not None else None,
-                self.neural_weights())
-        logp = ops.ode_logp_only(spec, args[0], args[1], args[2], observations.to(dev), args[3], args[4])
-        self._last = LazySolution(logp, lambda: self.solve(config, times, theta, conditions, dev_1hot, observations))
-        self._last.online_summaries = lambda log_w, lse: ops.ode_fwd_summaries(spec, args[0], args[1], args[2], args[3],
-                                                                               args[4], log_w, lse)
+        Returns a LazySolution whose record carries `online_summaries(log_w, lse)`; trajectory and x_predict are computed
+        (the ordinary forward launch, `full`) only if somebody asks.  likelihood_route says where the form applies (not
+        dr_blackbox, the adaptive solvers, launches below the evaluation size, which run other kernel families)."""
+        logp = ops.ode_logp_only(spec, args[0], args[1], args[2], observations, args[3], args[4])
+        online = lambda log_w, lse: ops.ode_fwd_summaries(spec, *args, log_w, lse)  # noqa: E731
+        self._last = LazySolution(logp, ForwardRecord(ODE_LOGP_ONLY, online_summaries=online), full)
         return self._last
 
     # ---- reference entry points ---------------------------------------------------------------------
-    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None):
-        """reference ode.py:66-82 -> [B,S,N,T]."""
-        return self.solve(config, times, theta, conditions, dev_1hot, observations).sol
+    def simulate(self, config, times, theta, conditions, dev_1hot, condition_on_device=True, observations=None,
+                 request=None):
+        """reference ode.py:66-82 -> [B,S,N,T].  `request`: what the caller will do with the forward (ForwardRequest);
+        an override that does not pass it on gets the plain forward, which is correct and stores x_predict."""
+        return self.solve(config, times, theta, conditions, dev_1hot, observations, request=request).sol
 
     def expand_precisions(self, theta, times, x_states):
         return self.precisions.expand(theta, len(times), x_states)

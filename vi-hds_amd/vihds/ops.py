@@ -594,8 +594,9 @@ class DecoderStepFused(torch.autograd.Function):
 class ThetaOdeFused(torch.autograd.Function):
     """The sampling stage inside the ODE FORWARD launch (vihds_theta_ode_fwd): theta = clip(sample(q, u)) with log q / log p,
     dr_blackbox's condition_theta (offset layer) and the trajectory + log-likelihood, one launch where ThetaSampleLogProbPacked
-    [+ OffsetRows] + OdeSolveObserve are two or three.  Training fast path of the models WITHOUT a fused decoder step; the
-    step's backward is ops.GeneralTail (which reads this node's saved tensors).  Returns (theta, log_q, log_p, u, traj, logp).
+    [+ OffsetRows] + OdeSolveObserve are two or three.  Training fast path of the models WITHOUT a fused decoder step, taken
+    when the forward's request allows it (ode.ForwardRequest.fuse_sampling); the step's backward is ops.GeneralTail (which
+    reads this node's saved tensors through the forward's record).  Returns (theta, log_q, log_p, u, traj, logp).
     backward (a caller that runs autograd after all): the unfused ops are replayed on the saved draws and differentiated."""
 
     SAVED = ("q_all", "kind", "p_mu", "p_prec", "clip_lo", "clip_hi", "u", "q_rows", "theta", "cond", "times", "obs", "traj",
@@ -1412,15 +1413,17 @@ class GeneralTail(StepTail):
         return self._maps[key]
 
     @staticmethod
-    def forward_state(theta_node, ode_node):
-        """The step's forward state as GeneralTail.launch takes it, by name: the saved tensors of ThetaSampleLogProbPacked's
-        and OdeSolveObserve's backward nodes -- or of the one node of ThetaOdeFused (pass it twice) -- plus spec, prob, rom
-        (the row-offset map), logp and rng_advance (the generator state the fused forward left for the tail to step)."""
-        if type(ode_node).__name__ == "ThetaOdeFusedBackward":
+    def forward_state(record):
+        """The step's forward state as GeneralTail.launch takes it, by name, from the forward's record (ode.ForwardRecord): the
+        saved tensors of ThetaSampleLogProbPacked's and OdeSolveObserve's backward nodes -- or of the one node of ThetaOdeFused
+        -- plus spec, prob, rom (the row-offset map), logp and rng_advance (the generator state the fused forward left for the
+        tail to step)."""
+        ode_node = record.ode_node
+        if record.route == ThetaOdeFused.__name__:
             fwd = saved_state(ode_node, ThetaOdeFused)
-            fwd.rng_advance = ode_node.rng_state
+            fwd.rng_advance = record.rng_state
         else:
-            fwd = SimpleNamespace(rng_advance=None, **vars(saved_state(theta_node, ThetaSampleLogProbPacked)),
+            fwd = SimpleNamespace(rng_advance=None, **vars(saved_state(record.theta_node, ThetaSampleLogProbPacked)),
                                   **vars(saved_state(ode_node, OdeSolveObserve)))
         fwd.spec, fwd.prob, fwd.rom, fwd.logp = ode_node.spec, ode_node.prob, ode_node.row_offset_map, ode_node.logp_out
         return fwd

@@ -15,6 +15,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from vihds import hostdraws, ops, parallel
+from vihds import ode as O
 from vihds.encoders import LocalAndGlobal
 from vihds.utils import Results, TrainingLogData, attrify, default_get_value, variable_summaries
 
@@ -33,12 +34,6 @@ def log_prob_observations(model, x_predict, x_obs, precisions, use_laplace=False
         # a generated model's own log density (vihds/modelgen.py), with theta and the treatments of its last solve
         return torch.sum(ode_model._log_likelihood_map(x_predict, x_obs, precisions), 3)
     return torch.sum(log_prob_gaussian(torch.unsqueeze(x_obs, 1), x_predict, precisions), 3)
-
-
-def _node_of(tensor, function):
-    """tensor.grad_fn when that is the backward node of the ops Function `function`, else None."""
-    node = getattr(tensor, "grad_fn", None)
-    return node if type(node).__name__ == function.__name__ + "Backward" else None
 
 
 def _delta_obs(obs):
@@ -249,7 +244,6 @@ class Training:
         self.fused_tail = bool(default_get_value(p, "fused_step_tail", True)) and on_gpu
         self._tail, self._tail_ok, self._tail_shapes = None, False, {}
         self._gtail, self._gtail_ok = None, None  # ops.GeneralTail (any model); None: not decided yet
-        self._gtail_declined = set()  # (batch shape, n_iwae) pairs GeneralTail.launch has declined
         if on_gpu:
             self.optimizer.gate = None
         self._graphs = {}
@@ -263,8 +257,10 @@ class Training:
         self._steps = 0
 
     # ------------------------------------------------------------------------------------------------
-    def cost(self, batch_data, batch_results, theta, q, p, full_output=False, writer=None, epoch=None):
-        """reference training.py:127-174.  Returns {"elbo": -ELBO} (sic) or a Results object."""
+    def cost(self, batch_data, batch_results, theta, q, p, full_output=False, writer=None, epoch=None, defer_iwae=False):
+        """reference training.py:127-174.  Returns {"elbo": -ELBO} (sic) or a Results object.
+        defer_iwae: the caller runs backward() with the unit seed right after (Training.step), so a forward whose record
+        allows it may leave the loss to its theta-adjoint launch."""
         fused = getattr(batch_results, "log_p_by_species", None)
         sol = getattr(batch_results, "solution", None)
         if fused is None or (full_output and sol is None):  # (the kernel paths never materialise these)
@@ -283,10 +279,9 @@ class Training:
         group = (self.shard.group or torch.distributed.group.WORLD) if self.shard is not None else None
         # (fused decoder step + params.fused_iwae_backward: the loss is evaluated inside the step's theta-adjoint launch,
         # i.e. `iwae_cost` holds its value once backward() has run -- Training.step returns it after that)
-        # Only inside Training.step, which is known to run backward() with the unit seed right after: a caller that
-        # evaluates cost() on its own gets the loss value immediately, as in the reference.
-        defer = (not full_output and group is None and torch.is_grad_enabled() and getattr(self, "_in_step", False)
-                 and getattr(getattr(batch_results, "solution", None), "defer_iwae", False))
+        # Only on request: a caller that evaluates cost() on its own gets the loss value immediately, as in the reference.
+        defer = (defer_iwae and not full_output and group is None and torch.is_grad_enabled()
+                 and getattr(getattr(sol, "record", None), "defer_iwae", False))
         iwae_cost, log_unnormalized_iws, lse = ops.iwae_loss(logp, log_p_theta, log_q_theta, n_iwae_total=n_iwae,
                                                              group=group, defer=defer)
         if not full_output:
@@ -348,19 +343,11 @@ class Training:
         Results copies to the host into one buffer -- is captured once per (data set, sample count) and replayed: the pass
         is some 25 launches whose host-side cost was a third of its time.  The draws come from the device generators, which
         advance inside the kernels, so every replay is a fresh evaluation, as in the eager pass."""
-        ode_model = self.model.decoder.ode_model
-        ode_model._no_online_summaries = self.shard is not None
-        ode_model._evaluating = True  # (the summaries-on-the-way form of the pass is this method's: OdeModel._solve_for_evaluation)
-        try:
-            return self._evaluate(data, n_samples, writer, epoch)
-        finally:
-            ode_model._evaluating = False
-
-    def _evaluate(self, data, n_samples, writer, epoch):
         dev_ok = (self.eval_graph and self.use_graph and writer is None and self.shard is None and self.replica is None)
+        request = self._evaluation_request()
         if not dev_ok:
             with torch.no_grad():
-                results, theta, q, p = self.model(data, n_samples, writer=writer, epoch=epoch)
+                results, theta, q, p = self.model(data, n_samples, writer=writer, epoch=epoch, request=request)
                 return self.cost(data, results, theta, q, p, full_output=True, writer=writer, epoch=epoch)
         # keyed by the data object's identity; the entry HOLDS the object, so its id cannot be reused by another batch of
         # another shape while the graph that captured its tensors is cached (ADVICE r03); a caller that evaluates many
@@ -375,7 +362,7 @@ class Training:
                 self._graphs_off(exc)
                 self.eval_graph = False
                 with torch.no_grad():
-                    results, theta, q, p = self.model(data, n_samples, writer=writer, epoch=epoch)
+                    results, theta, q, p = self.model(data, n_samples, writer=writer, epoch=epoch, request=request)
                     return self.cost(data, results, theta, q, p, full_output=True, writer=writer, epoch=epoch)
             staged["data"] = data
             self._eval_graphs[key] = (g, staged)
@@ -403,15 +390,15 @@ class Training:
         staged["ring_refs"][k] = weakref.ref(out)
         return out
 
+    def _evaluation_request(self):
+        """(the summaries-on-the-way form of the pass is an evaluation's own -- ode.likelihood_route -- and not for samples
+        sharded over ranks)"""
+        return O.ForwardRequest(O.EVALUATE, online_summaries=self.shard is None)
+
     def _evaluation_device_side(self, data, n_samples):
-        ode_model = self.model.decoder.ode_model
-        was, ode_model._evaluating = getattr(ode_model, "_evaluating", False), True
-        try:
-            with torch.no_grad():
-                results, theta, q, p = self.model(data, n_samples)
-                elbo, summ = self.cost(data, results, theta, q, p, full_output="device")
-        finally:
-            ode_model._evaluating = was
+        with torch.no_grad():
+            results, theta, q, p = self.model(data, n_samples, request=self._evaluation_request())
+            elbo, summ = self.cost(data, results, theta, q, p, full_output="device")
         q_tensors = [t.detach() for t in q.get_tensors()]
         parts = q_tensors + [elbo.detach().reshape(1)] + [x.detach() for x in summ]
         flat = torch.cat([t.reshape(-1).float() for t in parts])  # ONE device->host transfer per pass
@@ -484,24 +471,21 @@ class Training:
     def step(self, batch, zero_grad=True):
         """One ELBO training step on a device batch: forward, cost, backward, (gradient all-reduce), Adam.
         Returns the loss tensor (-ELBO) without synchronising."""
-        ode = self.model.decoder.ode_model
         # (a step whose backward is ops.GeneralTail reads neither trajectory views nor x_predict: the forward skips the latter)
         # (a batch shape the tail has declined once -- LDS budget, offset layer, row layout -- keeps the ordinary forward: the fused
         # one would integrate twice and spend a vihds_rng_advance launch per step for nothing; ADVICE r05)
         obs = getattr(batch, "observations", None)
-        shape_key = (tuple(obs.shape) if obs is not None else None, int(self.args.train_samples))
-        gtail_on = bool(self._gtail_ok) and shape_key not in self._gtail_declined
-        ode._train_without_x_predict = gtail_on
+        shape_key = (O.GENERAL_TAIL, tuple(obs.shape) if obs is not None else None, int(self.args.train_samples))
+        declined = self.model.decoder.ode_model._fused_declined  # (one cache for every route's declines, the tail's included)
+        gtail_on = bool(self._gtail_ok) and not declined.get(shape_key)
         # (... and the sampling stage can run inside the forward launch: params.fused_theta_ode, vihds_theta_ode_fwd)
-        self.model._fuse_theta_ode = gtail_on and bool(default_get_value(self.settings.params, "fused_theta_ode", True))
-        try:
-            batch_results, theta, q, p = self.model(batch, self.args.train_samples)
-        finally:
-            ode._train_without_x_predict = False
-            self.model._fuse_theta_ode = False
+        request = O.ForwardRequest(O.TRAIN, general_tail=gtail_on, fuse_sampling=gtail_on and bool(
+            default_get_value(self.settings.params, "fused_theta_ode", True)))
+        batch_results, theta, q, p = self.model(batch, self.args.train_samples, request=request)
         loss = self._general_tail(batch_results, theta, q, p)
+        record = getattr(getattr(batch_results, "solution", None), "record", None) or O.ForwardRecord()
         if loss is None and gtail_on:
-            self._gtail_declined.add(shape_key)
+            declined[shape_key] = True
         if loss is not None:
             # params.fused_step_tail, any model: IWAE loss, ODE adjoint, weight gradients, theta / encoder adjoints and Adam
             # ran as GeneralTail's launches; autograd's backward and optimizer.step() do not run for this step
@@ -512,19 +496,14 @@ class Training:
             if zero_grad:
                 self.optimizer.zero_grad(set_to_none=True)
             return loss.detach()
-        node = _node_of(getattr(getattr(batch_results, "solution", None), "logp_buffer", None), ops.ThetaOdeFused)
-        if node is not None and node.rng_state is not None:
+        if record.rng_state is not None:
             # (the fused forward left the generator's step to the tail, which did not take this step after all)
             from vihds import hip
 
-            hip.check(hip.lib().vihds_rng_advance(hip.ptr(node.rng_state), hip.current_stream()), "vihds_rng_advance")
-        self._in_step = True
+            hip.check(hip.lib().vihds_rng_advance(hip.ptr(record.rng_state), hip.current_stream()), "vihds_rng_advance")
         ops._PENDING_IWAE.clear()  # (a deferred loss whose backward never ran must not be mistaken for this step's)
-        try:
-            elbo = self.cost(batch, batch_results, theta, q, p).elbo
-        finally:
-            self._in_step = False
-        if self._step_tail(batch_results, q) is not None:
+        elbo = self.cost(batch, batch_results, theta, q, p, defer_iwae=True).elbo
+        if self._step_tail(record, q) is not None:
             # params.fused_step_tail: loss, backward and Adam ran as vihds_step_tail's two launches
             if self.replica is not None:
                 # row replicas: the tail formed this rank's gradients (no Adam); ONE in-place all-reduce over the arena they
@@ -563,16 +542,14 @@ class Training:
             self.optimizer.zero_grad(set_to_none=True)
         return elbo.detach()
 
-    def _step_tail(self, batch_results, q):
+    def _step_tail(self, record, q):
         """params.fused_step_tail (single process, fused decoder step with a deferred IWAE loss, all trainable parameters
         in the encoder): hand the rest of the step to ops.StepTail.  Returns the loss tensor, or None when it does not
         apply (the caller then runs autograd's backward and optimizer.step())."""
         if not self.fused_tail or self.shard is not None or len(ops._PENDING_IWAE) != 1:
             return None
-        dec_node = _node_of(getattr(getattr(batch_results, "solution", None), "logp_buffer", None), ops.DecoderStepFused)
-        packed = getattr(q, "_packed_q", None)
-        enc_node = _node_of(packed[1], ops.EncoderQTables) if packed is not None else None
-        if dec_node is None or enc_node is None:
+        dec_node, enc_node = record.ode_node, getattr(q, "_enc_node", None)
+        if record.route != O.DECODER_STEP_FUSED or dec_node is None or enc_node is None:
             return None
         if self._tail is None:
             self._tail = ops.StepTail(self.model.encoder, self.optimizer)
@@ -598,20 +575,18 @@ class Training:
     def _general_tail(self, batch_results, theta, q, p):
         """params.fused_step_tail for the models WITHOUT a fused decoder step (anything but dr_constant: relay / degrader /
         prpr / auto and their _precisions forms, dr_blackbox, dr_constant_precisions; reference training.py:324-340 is
-        model-agnostic): the forward ran as encoder -> theta kernel -> [conditioning] -> vihds_ode_fwd; hand everything
-        behind it to ops.GeneralTail.  Returns the loss tensor, or None when it does not apply (the caller then runs cost(),
+        model-agnostic): the forward ran as encoder -> theta kernel -> [conditioning] -> vihds_ode_fwd, or with the sampling
+        stage inside that launch (`record` says which, and holds the launches' autograd nodes); hand everything behind it
+        to ops.GeneralTail.  Returns the loss tensor, or None when it does not apply (the caller then runs cost(),
         autograd's backward and optimizer.step())."""
         if not self.fused_tail or self.shard is not None or self._gtail_ok is False:
             return None
-        sol = getattr(batch_results, "solution", None)
-        logp = getattr(sol, "logp_buffer", None)
-        packed = getattr(theta, "_packed", None)
-        pq = getattr(q, "_packed_q", None)
-        enc_node = _node_of(pq[1], ops.EncoderQTables) if pq is not None else None
-        ode_node, theta_node = _node_of(logp, ops.ThetaOdeFused), _node_of(packed, ops.ThetaOdeFused)
-        if ode_node is None or theta_node is None:  # (not the fused forward: the theta kernel, then vihds_ode_fwd)
-            ode_node, theta_node = _node_of(logp, ops.OdeSolveObserve), _node_of(packed, ops.ThetaSampleLogProbPacked)
-        if ode_node is None or theta_node is None or enc_node is None or not getattr(sol, "has_logp", False):
+        record = getattr(getattr(batch_results, "solution", None), "record", None)
+        packed, enc_node = getattr(theta, "_packed", None), getattr(q, "_enc_node", None)
+        # (the packed theta handed on must still be the sampling launch's own output)
+        if (record is None or record.route not in (O.THETA_ODE_FUSED, O.ODE_SOLVE_OBSERVE) or not record.has_logp
+                or record.ode_node is None or enc_node is None or record.theta_node is None or packed is None
+                or packed.grad_fn is not record.theta_node):
             return None
         if self._gtail is None:
             self._gtail = ops.GeneralTail(self.model.encoder, self.optimizer, self.model.decoder.ode_model)
@@ -619,12 +594,12 @@ class Training:
             self._gtail_ok = self._gtail.applicable()
             if not self._gtail_ok:
                 return None
-        fwd = ops.GeneralTail.forward_state(theta_node, ode_node)
+        fwd = ops.GeneralTail.forward_state(record)
         # the integrator must have read the sampling kernel's own buffer (nothing re-bound into a copy on the way)
         if fwd.theta.data_ptr() != packed.data_ptr() or not self._tail_shape_supported(enc_node.shape, fwd.q_all, fwd.u):
             return None
-        return self._gtail.launch(fwd, enc_node, q.log_prob(theta), p.log_prob(theta), logp.shape[2],
-                                  apply_adam=self.replica is None)
+        return self._gtail.launch(fwd, enc_node, q.log_prob(theta), p.log_prob(theta),
+                                  batch_results.solution.logp_buffer.shape[2], apply_adam=self.replica is None)
 
     def _snapshot_training_state(self):
         """Parameters + optimizer state before a capture's warm-up steps (a new batch shape, e.g. an epoch's last partial

@@ -4,7 +4,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from vihds.decoders import Decoder
+from vihds import ode as O
+from vihds import ops
+from vihds.decoders import Decoder, on_demand_result
 from vihds.encoders import Encoder
 from vihds.utils import default_get_value
 
@@ -20,7 +22,6 @@ class BaseVAE(nn.Module):
         self.shard = shard  # vihds.parallel.SampleShard or None
         self._rng_state = None
         self._u_staging = {}
-        self._fused_declined = {}
 
     def sample_u(self, n_batch, n_samples, device=None):
         """Standard-normal draws u [B,S,P].  "numpy" = the reference's host RNG stream (vae.py:22-24);
@@ -30,8 +31,6 @@ class BaseVAE(nn.Module):
         if self.u_rng == "device":
             return torch.randn((n_batch, n_samples, self.n_theta), device=self.device)
         if self.u_rng == "kernel":
-            from vihds import ops
-
             if self._rng_state is None:  # seeded once from torch's generator so torch.manual_seed controls it
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
                 self._rng_state = ops.KernelNormal.new_state(seed, self.device)
@@ -64,7 +63,11 @@ class BaseVAE(nn.Module):
         ring["events"][k].record()
         return u
 
-    def forward(self, data, samples, writer=None, epoch=None):
+    def forward(self, data, samples, writer=None, epoch=None, request=None):
+        """reference vae.py:26-37.  `request` (ode.ForwardRequest): what the caller will do with the forward; None asks for
+        nothing.  Which launches run is ode.sampling_route's answer; a route that declines is remembered and the next one
+        tried."""
+        request = request or O.PLAIN_FORWARD
         u = self.sample_u(len(data.inputs), samples)
         if self.shard is not None:
             u = self.shard.take(u)  # every rank drew the same full u; keep this rank's slice of S
@@ -72,40 +75,30 @@ class BaseVAE(nn.Module):
         p = self.encoder.p
         ode_model = self.decoder.ode_model
         n_extra = len(ode_model.extra_theta_names) if self.decoder.condition_on_device else 0
-        fused = self._decoder_step_fused(data, samples, u, q, p, n_extra)
-        if fused is not None:
-            return fused + (q, p)
-        fused = self._theta_ode_fused(data, samples, u, q, p, n_extra)
-        if fused is not None:
-            return fused + (q, p)
+        attempts = ((O.DECODER_STEP_FUSED, self._decoder_step_fused), (O.THETA_ODE_FUSED, self._theta_ode_fused))
+        for route, attempt in attempts:
+            if O.sampling_route(request, self, q, data, samples) != route:
+                continue
+            try:
+                fused = attempt(data, samples, u, q, p, n_extra)
+            except ops.FusedTrainingUnsupported:  # (remembered: this shape does not ask for the route again)
+                shape = (tuple(data.observations.shape), samples, self.decoder.config.params.solver)
+                ode_model._fused_declined[(route,) + shape] = True
+                continue
+            if fused is not None:
+                return fused + (q, p)
         clipped_theta = q.sample_clip_log_prob(u, p, stddevs=4, n_extra_rows=n_extra)
         if self.shard is not None:
             lo, _ = self.shard.bounds(samples)
             object.__setattr__(clipped_theta, "_sample_window", (samples, lo))
-        result, conditioned_theta = self.decoder(clipped_theta, data, writer, epoch)
+        result, conditioned_theta = self.decoder(clipped_theta, data, writer, epoch, request=request)
         return result, conditioned_theta, q, p
 
-
-def _bind_fused(BaseVAE):
     def _decoder_step_fused(self, data, samples, u, q, p, n_extra):
         """Training fast path (params.fused_ode_training): sampling, device conditioning, log-likelihood and the
-        unit-weight adjoint in ONE launch (ops.DecoderStepFused).  None when it does not apply."""
-        from vihds import hip, ops
-        from vihds.decoders import LazyDecoderResult
-        from vihds.ode import LazySolution
-
+        unit-weight adjoint in ONE launch (ops.DecoderStepFused).  None when it turns out not to apply after all."""
         dec = self.decoder
-        ode = dec.ode_model
-        cfg = dec.config
-        obs = data.get("observations", None) if hasattr(data, "get") else None
-        if (not torch.is_grad_enabled() or obs is None or not default_get_value(cfg.params, "fused_ode_training", True)
-                or not default_get_value(cfg.params, "fused_decoder_step", True) or ode.model_key not in ode.fused_training_keys or getattr(q, "_packed_q", None) is None
-                or not obs.is_cuda or (n_extra and not dec.condition_on_device)
-                or cfg.params.solver in hip.ADAPTIVE_SOLVERS):
-            return None
-        key = (tuple(obs.shape), samples, cfg.params.solver)
-        if self._fused_declined.get(key):
-            return None
+        ode, cfg, obs = dec.ode_model, dec.config, data.observations
         extra = list(ode.extra_theta_names) if n_extra else []
         window = None
         if self.shard is not None:
@@ -116,76 +109,40 @@ def _bind_fused(BaseVAE):
             row_of = {n: k for k, n in enumerate(list(names) + extra)}
             return ode._spec(cfg, row_of, len(names) + len(extra))
 
+        n_q = len(q.names())
         cond_job = None
         if extra:
             rel, dflt, z, mean, std, rng_state = ode.conditioner_job(extra, data.dev_1hot)
-            cond_job = (len(extra), None, mean, std, z, rng_state, rel, dflt)
-        try:
-            n_q = len(q.names())
-            if cond_job is not None:
-                cond_job = (cond_job[0], n_q) + cond_job[2:]
-            if window is not None and not isinstance(u, ops.KernelNormal):
-                return None  # (the conditioner tiling needs the window; only the in-kernel draw carries it)
-            theta, logp = q.decoder_step_fused(u, p, 4, n_extra, spec_of, data.inputs, data.times.to(obs.device), obs,
-                                               data.dev_1hot, cond_job)
-        except ops.FusedTrainingUnsupported:
-            self._fused_declined[key] = True
-            return None
+            cond_job = (len(extra), n_q, mean, std, z, rng_state, rel, dflt)
+        if window is not None and not isinstance(u, ops.KernelNormal):
+            return None  # (the conditioner tiling needs the window; only the in-kernel draw carries it)
+        theta, logp = q.decoder_step_fused(u, p, 4, n_extra, spec_of, data.inputs, data.times.to(obs.device), obs,
+                                           data.dev_1hot, cond_job)
         for k, n in enumerate(extra):
             theta.bind_reserved_row(n, n_q + k)
         if window is not None:
             object.__setattr__(theta, "_sample_window", window)
         if hasattr(ode, "aR") and extra:
             ode.aR, ode.aS = getattr(theta, "aR", None), getattr(theta, "aS", None)
-        sol = LazySolution(logp, lambda: ode.solve(cfg, data.times, theta, data.inputs, data.dev_1hot, obs))
         # params.fused_iwae_backward: Training.cost may leave the IWAE loss to this step's theta-adjoint launch
-        sol.defer_iwae = bool(default_get_value(cfg.params, "fused_iwae_backward", True)) and self.shard is None
+        defer = bool(default_get_value(cfg.params, "fused_iwae_backward", True)) and self.shard is None
+        sol = O.LazySolution(logp, O.ForwardRecord(O.DECODER_STEP_FUSED, logp.grad_fn, defer_iwae=defer),
+                             lambda: ode.solve(cfg, data.times, theta, data.inputs, data.dev_1hot, obs))
         ode._last = sol
-
-        def build():
-            full = sol.full()
-            xs, prec = ode.expand_precisions(theta, data.times, full.sol)
-            return xs, ode.observe(full.sol, theta), prec
-
-        result = LazyDecoderResult(build)
-        result.solution = sol
-        result.log_p_by_species = sol.log_p_by_species
-        return result, theta
-
-    BaseVAE._decoder_step_fused = _decoder_step_fused
+        return on_demand_result(ode, theta, data.times, sol), theta
 
     def _theta_ode_fused(self, data, samples, u, q, p, n_extra):
-        """Training steps whose backward is ops.GeneralTail (Training.step sets `_fuse_theta_ode`): the sampling stage, for
-        dr_blackbox also condition_theta, runs inside the ODE forward launch (ops.ThetaOdeFused, vihds_theta_ode_fwd) -- the
-        models whose forward kernels carry it: relay / degrader / prpr / auto_constant (+ _precisions), dr_blackbox at the
-        built-in sizes.  None when it does not apply (then the separate launches)."""
-        from vihds import hip, ops
-        from vihds.decoders import LazyDecoderResult
-        from vihds.ode import DecodedSolution
-
+        """Training steps whose backward is ops.GeneralTail and whose request allows it (fuse_sampling): the sampling stage,
+        for dr_blackbox also condition_theta, runs inside the ODE forward launch (ops.ThetaOdeFused, vihds_theta_ode_fwd).
+        ode.sampling_route says for which models."""
         dec = self.decoder
-        ode, cfg = dec.ode_model, dec.config
-        obs = data.get("observations", None) if hasattr(data, "get") else None
-        if (not getattr(self, "_fuse_theta_ode", False) or not torch.is_grad_enabled() or obs is None or not obs.is_cuda
-                or getattr(q, "_packed_q", None) is None or self.shard is not None or cfg.params.solver in hip.ADAPTIVE_SOLVERS):
-            return None
+        ode, cfg, obs = dec.ode_model, dec.config, data.observations
         blackbox = ode.model_key == "dr_blackbox"
-        if not blackbox and (n_extra or getattr(ode, "extra_theta_names", ())):
-            return None  # (a device conditioner: not a stage of these kernels)
-        key = ("theta_ode", tuple(obs.shape), samples, cfg.params.solver)
-        if self._fused_declined.get(key):
-            return None
         extra = list(ode.extra_theta_names) if (blackbox and n_extra) else []
         n_q = len(q.names())
         offset = None
-        if blackbox and getattr(ode, "n_y", 0) > 0:
-            if not extra:
-                return None
-            names = q.names()
-            rows = [names.index("y%d" % (i + 1)) if ("y%d" % (i + 1)) in names else -1 for i in range(ode.n_y)]
-            if rows != list(range(rows[0], rows[0] + ode.n_y)) or rows[0] < 0:
-                return None
-            offset = (ode.offset_layer.weight, ode.offset_layer.bias, (rows[0], n_q, ode.n_y))
+        if blackbox and ode.n_y > 0:
+            offset = (ode.offset_layer.weight, ode.offset_layer.bias, (ode.offset_source_row(q.names()), n_q, ode.n_y))
 
         def spec_of(names):
             row_of = {n: k for k, n in enumerate(list(names) + extra)}
@@ -194,32 +151,16 @@ def _bind_fused(BaseVAE):
                     row_of["y%d" % (i + 1)] = n_q + i
             return ode._spec(cfg, row_of, len(names) + len(extra))
 
-        try:
-            theta, traj, logp = q.theta_ode_fused(u, p, 4, len(extra), spec_of, data.inputs, data.times.to(obs.device), obs,
-                                                  data.dev_1hot, ode.neural_weights(), offset)
-        except ops.FusedTrainingUnsupported:
-            self._fused_declined[key] = True
-            return None
+        theta, traj, logp = q.theta_ode_fused(u, p, 4, len(extra), spec_of, data.inputs, data.times.to(obs.device), obs,
+                                              data.dev_1hot, ode.neural_weights(), offset)
         if blackbox:
             for i in range(ode.n_y):  # (what condition_theta does: the attribute now names the conditioned row)
                 theta.bind_reserved_row("y%d" % (i + 1), n_q + i)
-        sol = DecodedSolution(traj, None, logp, observe=lambda s_: ode._observe_map(s_))
-        sol.has_logp = True
+        node = logp.grad_fn
+        sol = O.DecodedSolution(traj, None, logp, O.ForwardRecord(O.THETA_ODE_FUSED, node, node, node.rng_state),
+                                observe=lambda s_: ode._observe_map(s_))
         ode._last = sol
-
-        def build():
-            xs, prec = ode.expand_precisions(theta, data.times, sol.sol)
-            return xs, ode.observe(sol.sol, theta), prec
-
-        result = LazyDecoderResult(build)
-        result.solution = sol
-        result.log_p_by_species = sol.log_p_by_species
-        return result, theta
-
-    BaseVAE._theta_ode_fused = _theta_ode_fused
-
-
-_bind_fused(BaseVAE)
+        return on_demand_result(ode, theta, data.times, sol), theta
 
 
 def build_model(args, settings, dataset, parameters, shard=None):
