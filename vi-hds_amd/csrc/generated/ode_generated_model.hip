@@ -69,7 +69,8 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
   using namespace vihds;
   static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, traj_rows<GenM>::value, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
                                    slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
-                                   net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0};
+                                   net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
+                                   n_forcings<GenM>::value};
   return &r;
 }
 #endif

@@ -42,6 +42,9 @@ struct GenModelRecord {
   // 1: the generated struct has a precision map of its own (precision / precision_vjp, vihds_models.hpp own_prec<>): no
   // prec_* / init_prec_* slot rows and no weights of its own; never together with neural_prec
   int own_prec;
+  // forcings of the generated struct (vihds_models.hpp n_forcings<>): a data row of cond holds n_forcings series of T samples
+  // behind its treatments, so a problem needs C >= n_cond + n_forcings * T; such a model takes the fixed-grid solvers only
+  int n_forcings;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

@@ -952,6 +952,25 @@ struct own_lik : std::false_type {};
 template <class M>
 struct own_lik<M, std::void_t<decltype(M::OWN_LIK)>> : std::bool_constant<M::OWN_LIK> {};
 
+// A core generated with time-varying inputs (forcings, vihds/modelgen.py) declares N_FORCINGS = K > 0 and reserves 2 K + 1
+// entries of p behind its own: per forcing a value and a slope, and one interval start.  rhs reads forcing k at stage time t
+// as value + (t - start) * slope; the per-time-point hooks read the value.  Two members, called by the time loops of the
+// forward and the adjoint kernel, write those entries (nothing else does: prepare leaves them alone, no adjoint reads their
+// pb entries -- a forcing is data and gets no gradient):
+//   set_interval(p, t_lo, inv_dt, u_lo, u_hi)   ahead of the step over [t_lo, t_lo + 1 / inv_dt]: the linear interpolant of the
+//                                               row's samples u_lo[K], u_hi[K] at the interval's ends
+//   set_point(p, u)                             ahead of the hooks of a time point: the sample itself, slope 0
+// The samples of data row b are cond[b * C + (C - K T) + k * T + point]: K series of T values behind the row's treatments.
+// 0 for every hand-written model; WithPrec<> forwards its core's.
+template <class M, class = void>
+struct n_forcings {
+  static constexpr int value = 0;
+};
+template <class M>
+struct n_forcings<M, std::void_t<decltype(M::N_FORCINGS)>> {
+  static constexpr int value = M::N_FORCINGS;
+};
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};
@@ -1003,6 +1022,12 @@ struct WithPrec {
   __device__ static void observe_vjp(const float* y, const float* p, const float* xpb, float* yb, float* pb) {
     Core::observe_vjp(y, p, xpb, yb, pb);
   }
+  // a core with forcings: its entries of p are its own (the hidden-unit count sits behind them)
+  static constexpr int N_FORCINGS = n_forcings<Core>::value;
+  __device__ static void set_interval(float* p, float t_lo, float inv_dt, const float* u_lo, const float* u_hi) {
+    Core::set_interval(p, t_lo, inv_dt, u_lo, u_hi);
+  }
+  __device__ static void set_point(float* p, const float* u) { Core::set_point(p, u); }
   __device__ static void hidden(float t, const float* y, float* h) {
     h[0] = ftanh(t);
     VIHDS_UNROLL for (int i = 0; i < NS; ++i) h[i + 1] = ftanh(y[i]);

@@ -334,6 +334,18 @@ __device__ __forceinline__ const float* stage_weights(const OdeArgs& a, float* l
 #ifndef VIHDS_NT_TRAJ
 #define VIHDS_NT_TRAJ 1
 #endif
+// What the time loops keep for a model with forcings (n_forcings<M> = NF > 0, vihds_models.hpp): where the thread's data row
+// has its samples -- cond[b * C + (C - NF T) + j * T + k], or the block's staged copy -- and the samples at the two ends of
+// the current interval and at the point requested one iteration ahead.  Empty for every other model: their kernels declare
+// nothing and every use sits behind `if constexpr (NF > 0)`.
+template <int NF>
+struct ForcingFeed {
+  const float* src;  // the row's samples in cond (the unstaged forward, the adjoint)
+  int lds;           // ... in in_lds (the staged forward)
+  float lo[NF], hi[NF], ahead[NF];
+};
+template <>
+struct ForcingFeed<0> {};
 // ---- forward -------------------------------------------------------------------------------------
 // LDS_IN: the time grid and the observation rows of the data rows this block spans are staged in LDS once, so the
 // time loop holds no vector-memory loads and its trajectory / x_predict stores are never waited on (see
@@ -344,19 +356,28 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   constexpr int NT = traj_rows<M>::value;  // rows per time point of traj: N, + 4 precision rows of a model with its own map
   constexpr bool OWN_PREC = own_prec<M>::value;
   constexpr bool OWN_LIK = own_lik<M>::value;  // the log density is the model's own member (vihds_models.hpp)
+  constexpr int NF = n_forcings<M>::value;     // forcings: K series of T samples per data row behind its treatments in cond
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
-  extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations
+  extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations | [nb][NF][T] forcing samples
   const float* wts = stage_weights<M>(a, wlds);
   int ob_off = 0;
+  ForcingFeed<NF> ff;
   if (LDS_IN) {
     const int first = blockIdx.x * blockDim.x, last = min(first + (int)blockDim.x, a.n) - 1;
     const int b0 = first / a.S, nb = last / a.S - b0 + 1;
     for (int q = threadIdx.x; q < a.T; q += blockDim.x) in_lds[q] = a.times[q];
     const float* src = a.obs + (size_t)b0 * 4 * a.T;
     for (int q = threadIdx.x; q < nb * 4 * a.T; q += blockDim.x) in_lds[a.T + q] = src[q];
+    if constexpr (NF > 0) {  // (a row's samples are contiguous, the rows are C apart)
+      const int per_row = NF * a.T, f_base = a.T + nb * 4 * a.T;
+      const float* fsrc = a.cond + (size_t)b0 * a.C + (a.C - per_row);
+      for (int q = threadIdx.x; q < nb * per_row; q += blockDim.x)
+        in_lds[f_base + q] = fsrc[(size_t)(q / per_row) * a.C + q % per_row];
+    }
     __syncthreads();
     const int ii = min((int)(blockIdx.x * blockDim.x + threadIdx.x), a.n - 1);
     ob_off = a.T + (ii / a.S - b0) * 4 * a.T;
+    if constexpr (NF > 0) ff.lds = a.T + nb * 4 * a.T + (ii / a.S - b0) * NF * a.T;
   }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
@@ -393,16 +414,38 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   float tA = time_at(0), tB = time_at(1);
   float obc[4], obn[4];
   VIHDS_UNROLL for (int j = 0; j < 4; ++j) { obc[j] = a.logp ? obs_at(j, 0) : 0.f; obn[j] = 0.f; }
+  // forcing samples travel with the times: ff.lo / ff.hi at tA / tB, the next point's requested one iteration ahead like tC
+  if constexpr (NF > 0) {
+    ff.src = a.cond + (size_t)b * a.C + (a.C - NF * a.T);
+    VIHDS_UNROLL for (int j = 0; j < NF; ++j) {
+      ff.lo[j] = LDS_IN ? in_lds[ff.lds + j * a.T] : ff.src[j * a.T];
+      ff.hi[j] = LDS_IN ? in_lds[ff.lds + j * a.T + 1] : ff.src[j * a.T + 1];
+    }
+  }
   for (int k = 0; k < a.T; ++k) {
     const float tC = (k + 1 < a.T) ? time_at(k + 1) : tB;
     if (a.logp && k + 1 < a.T) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) obn[j] = obs_at(j, k + 1);
     }
+    if constexpr (NF > 0) {
+      VIHDS_UNROLL for (int j = 0; j < NF; ++j) {
+        ff.ahead[j] = ff.hi[j];
+        if (k + 1 < a.T) ff.ahead[j] = LDS_IN ? in_lds[ff.lds + j * a.T + k + 1] : ff.src[j * a.T + k + 1];
+      }
+    }
     if (k > 0) {
+      if constexpr (NF > 0) M::set_interval(p, tA, 1.f / (tB - tA), ff.lo, ff.hi);
       ode_step<M, SOLVER>(tA, tB, h0, y, p, wts);
       tA = tB;
+      if constexpr (NF > 0) {
+        VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.lo[j] = ff.hi[j];
+      }
     }
     tB = tC;
+    if constexpr (NF > 0) {  // the hooks of this time point read the sample itself
+      VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.hi[j] = ff.ahead[j];
+      M::set_point(p, ff.lo);
+    }
     if (a.traj) {
       if (nt_traj) {  // (streaming stores at evaluation-sized launches: see nt_traj)
         VIHDS_UNROLL for (int j = 0; j < N; ++j) __builtin_nontemporal_store(y[j], &a.traj[((size_t)k * NT + j) * n + i]);
@@ -636,6 +679,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   constexpr int NT = traj_rows<M>::value;  // rows per time point of traj_in / g_traj (the precision rows of traj_in are never read)
   constexpr bool OWN_PREC = own_prec<M>::value;
   constexpr bool OWN_LIK = own_lik<M>::value;  // the log density's adjoint is the model's own member (vihds_models.hpp)
+  constexpr int NF = n_forcings<M>::value;     // forcings: K series of T samples per data row behind its treatments in cond
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   const float* wts = stage_weights<M>(a, wlds);
   const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -673,18 +717,38 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(a.T - 1) * NT + j) * n + i];
   VIHDS_UNROLL for (int j = 0; j < 4; ++j) obn[j] = ob[j * a.T + a.T - 1];
   float tHi = a.times[a.T - 1], tLo = tHi;
+  // forcing samples travel with the times: ff.hi at tHi, ff.lo at tK, the next lower point's (ff.ahead) requested one
+  // iteration ahead like tLo
+  ForcingFeed<NF> ff;
+  if constexpr (NF > 0) {
+    ff.src = a.cond + (size_t)b * a.C + (a.C - NF * a.T);
+    VIHDS_UNROLL for (int j = 0; j < NF; ++j) { ff.ahead[j] = ff.src[j * a.T + a.T - 1]; ff.hi[j] = ff.ahead[j]; }
+  }
   for (int k = a.T - 1; k >= 0; --k) {
     float y[N], obk[4];
     VIHDS_UNROLL for (int j = 0; j < N; ++j) y[j] = yn[j];
     VIHDS_UNROLL for (int j = 0; j < 4; ++j) obk[j] = obn[j];
     const float tK = tLo;
+    if constexpr (NF > 0) {
+      VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.lo[j] = ff.ahead[j];
+    }
     if (k > 0) {
       VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(k - 1) * NT + j) * n + i];
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) obn[j] = ob[j * a.T + k - 1];
       tLo = a.times[k - 1];
+      if constexpr (NF > 0) {
+        VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.ahead[j] = ff.src[j * a.T + k - 1];
+      }
+    }
+    if constexpr (NF > 0) {  // the interval (k, k + 1) ...
+      if (k < a.T - 1) M::set_interval(p, tK, 1.f / (tHi - tK), ff.lo, ff.hi);
     }
     if (k < a.T - 1) ode_step_vjp<M, SOLVER>(tK, tHi, h0, y, p, wts, lam, pb, wtsb);
     tHi = tK;
+    if constexpr (NF > 0) {  // ... then the point k, whose hook adjoints follow
+      VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.hi[j] = ff.lo[j];
+      M::set_point(p, ff.lo);
+    }
     // gradient injected at time k: log-likelihood term, x_predict and trajectory upstream grads
     float xp[4], xpb[4];
     if constexpr (M::OBS == OBS_CUSTOM) M::observe(y, p, xp);
@@ -813,7 +877,8 @@ template <class M, int SOLVER>
 inline void launch_fwd_s(const OdeArgs& a, hipStream_t st) {
   const int blk = pick_block(a.n);
   const int nb = min(a.B, (blk - 1) / a.S + 2);
-  const size_t lds = ((size_t)a.T + (size_t)nb * 4 * a.T) * sizeof(float);
+  size_t lds = ((size_t)a.T + (size_t)nb * 4 * a.T) * sizeof(float);
+  lds += (size_t)nb * n_forcings<M>::value * a.T * sizeof(float);  // (the rows' forcing samples behind the observations)
   if (lds <= 32 * 1024)
     hipLaunchKernelGGL((ode_fwd_kernel<M, SOLVER, true>), dim3((a.n + blk - 1) / blk), dim3(blk), lds, st, a);
   else
@@ -862,8 +927,38 @@ constexpr bool solver_built_in(int sv) { return ONLY < 0 || sv == ONLY; }
 #include "vihds_rk_adaptive_device.hpp"
 namespace vihds {
 
+template <class M, int ONLY>
+inline int launch_ode_any(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode);
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+  if constexpr (n_forcings<M>::value > 0) {
+    // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
+    // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
+    // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it
+    if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
+#define VIHDS_CASE(SV)                                           \
+  case SV:                                                       \
+    if constexpr (solver_built_in<ONLY>(SV)) {                   \
+      if (backward) launch_bwd_s<M, SV>(a, st);                  \
+      else launch_fwd_s<M, SV>(a, st);                           \
+      return VIHDS_OK;                                           \
+    }                                                            \
+    break;
+    switch (solver) {
+      VIHDS_CASE(VIHDS_SOLVER_MODEULER)
+      VIHDS_CASE(VIHDS_SOLVER_MODEULERWHILE)
+      VIHDS_CASE(VIHDS_SOLVER_EULER)
+      VIHDS_CASE(VIHDS_SOLVER_MIDPOINT)
+      VIHDS_CASE(VIHDS_SOLVER_RK4)
+    }
+#undef VIHDS_CASE
+    return VIHDS_E_BADARG;
+  } else {
+    return launch_ode_any<M, ONLY>(backward, solver, a, st, mode);
+  }
+}
+template <class M, int ONLY>
+inline int launch_ode_any(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if constexpr (net_fields<M>::value > 0 || M::OBS == OBS_CUSTOM || own_prec<M>::value || own_lik<M>::value) {
     // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers;
     // a model with an observation map of its own: the one-pass summaries know the fixed maps only; a model with a precision

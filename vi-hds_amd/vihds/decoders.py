@@ -67,12 +67,13 @@ class Decoder(nn.Module):
             theta_conditioned = self.ode_model.condition_theta(theta, data.dev_1hot, writer, epoch)
         else:
             theta_conditioned = theta
-        fused = self.ode_model.solve_for_training(self.config, data.times, theta_conditioned, data.inputs,
+        inputs = self.ode_model.row_inputs(data)  # (the treatments; a model with forcings appends their samples)
+        fused = self.ode_model.solve_for_training(self.config, data.times, theta_conditioned, inputs,
                                                   data.dev_1hot, data.get("observations", None), request=request)
         if fused is not None:  # the log-likelihood without the trajectory's round trip; the rest only on demand
             return on_demand_result(self.ode_model, theta_conditioned, data.times, fused), theta_conditioned
         solution = self.ode_model.simulate(
-            self.config, data.times, theta_conditioned, data.inputs, data.dev_1hot,
+            self.config, data.times, theta_conditioned, inputs, data.dev_1hot,
             condition_on_device=self.condition_on_device, observations=data.get("observations", None), request=request)
         last = self.ode_model._last
         if writer is not None:

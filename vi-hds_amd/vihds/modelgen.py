@@ -104,6 +104,30 @@ logp is untouched, and the evaluation summaries (iw_variance, iw_predict_std) ke
 variances.  For a Student-t with nu degrees of freedom and scale 1 / sqrt(pr) the variance is nu / (nu - 2) / pr (nu > 2), so
 those two summaries understate the spread by that factor unless the model's precision already carries it.
 
+Forcings.  An input that changes over the experiment and differs from well to well -- a light or inducer schedule, a logged
+temperature, the measured OD as a growth driver -- is declared by name and read as an attribute:
+
+        forcings = ["light", "temp"]                 # at most MAX_FORCINGS; identifiers, no species or parameter name
+
+        def rhs(self, t, y, p, c):
+            drive = p.aYFP * self.forcing.light      # ... where(self.forcing.light > 0.5, ...), self.net.gate([self.forcing.temp, ...])
+
+Every data row brings one sample per forcing and time point of the observation grid (the batch key "forcings", [rows, K, T]).
+In rhs the value at stage time t is the linear interpolant of the row's samples -- on [t_k, t_k+1] that is u_k + (t - t_k)
+(u_k+1 - u_k) / (t_k+1 - t_k), continuous, so a stage on a grid point is unambiguous; in observe, precision and log_likelihood
+it is exactly the sample u_k of the time point.  Values are used raw (no log1p / exp round trip as the treatments have), a NaN
+sample propagates.  A forcing may be a network input and may be compared; reading one in prepare or initial_state raises (they
+run once, before the first time point).  It is data, like the observations: a leaf of the DAG with no adjoint -- no gradient
+with respect to the samples exists.  The samples travel in the rows of `cond`, behind the treatments: [n_conditions
+treatments | K x T samples, forcing-major], so the problem's C is n_conditions + K T (the data's treatment count, where the
+data carry more treatments than the model reads: the samples are the last K T entries of a row) and the C ABI has no new field;
+OdeModel.row_inputs(data) builds those rows for a batch (data.inputs for every other model) and solve checks the width.  The
+encoder does not see forcings.  In the kernels the generated struct keeps 2 K + 1 more entries of p (per forcing a value and a
+slope, and the interval's start) that its members set_interval / set_point write from the time loop; rhs reads p[v] + (t -
+p[t0]) p[s].  The adaptive solvers integrate on a grid that is not the observation grid: a model with forcings declines them
+(solve raises before anything is queued, the library answers VIHDS_E_UNSUPPORTED), as it declines the one-pass summaries.
+torch_problem takes the wide cond and `times`, the torch hooks cut the samples from the wide cond.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -138,6 +162,7 @@ OBSERVE_KINDS = {"default": ("OBS_DEFAULT", 6), "direct": ("OBS_DIRECT", 4)}  # 
 OBSERVE_CUSTOM = "custom"  # observe_kind of a class that defines observe(y, p, c): the struct's own map, OBS_CUSTOM
 # networks of a generated model (the hidden layer is walked one unit at a time, the inputs and outputs live in registers)
 MAX_NETWORKS, MAX_NET_INPUTS, MAX_NET_HIDDEN, MAX_NET_OUTPUTS = 2, 16, 32, 8
+MAX_FORCINGS = 4  # time-varying inputs of a generated model (each costs the kernels two registers and a sample in flight)
 NET_ACTIVATIONS = ("relu", "tanh")
 
 
@@ -185,7 +210,9 @@ _LEAVES = ("const", "th", "c", "y", "p", "t", "seed", "x")  # (x: the predicted 
 # ... and the two leaf kinds only log_likelihood() reads: the observations of the time point (forward only: data have no
 # adjoint) and the precisions (the constant slots or the values of the model's own precision map)
 _LEAVES += ("ob", "pr")
-_NO_ADJOINT = ("ob",)
+# ... and the forcings (rhs and the hooks): per-row time series, data like the observations
+_LEAVES += ("f",)
+_NO_ADJOINT = ("ob", "f")
 
 
 def _control_flow(*_args, **_kw):
@@ -816,6 +843,31 @@ class _Networks(object):
         raise ModelDefinitionError("networks are read-only")
 
 
+def _class_forcings(cls):
+    return list(getattr(cls, "forcings", None) or ())
+
+
+class _Forcings(object):
+    """`self.forcing` of the instance the functions run on: `self.forcing.<name>` is the value of that forcing where the
+    function is evaluated.  read(k, name) does the work (symbolic or torch)."""
+
+    def __init__(self, cls, read):
+        object.__setattr__(self, "_names", _class_forcings(cls))
+        object.__setattr__(self, "_read", read)
+        object.__setattr__(self, "_cls", cls.__name__)
+
+    def __getattr__(self, name):
+        if name not in self._names:
+            raise ModelDefinitionError("unknown forcing '%s' (%s.forcings declares: %s)"
+                                       % (name, self._cls, ", ".join(self._names) or "none"))
+        return self._read(self._names.index(name), name)
+
+    __getitem__ = __getattr__
+
+    def __setattr__(self, name, value):
+        raise ModelDefinitionError("forcings are read-only")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the hook table
 # ---------------------------------------------------------------------------------------------------------------------
@@ -930,6 +982,17 @@ class Trace(object):
             return g.net(k, inputs)
 
         object.__setattr__(inst, "net", _Networks(cls, call))
+        self.forcings = _class_forcings(cls)
+
+        def read(k, name):
+            if self._phase in ("prepare", "initial_state"):
+                raise ModelDefinitionError(
+                    "forcing '%s' read in %s: a forcing changes over the experiment, and %s is evaluated once, before the "
+                    "first time point -- forcings are read in rhs (the interpolant at the stage time), observe, precision and "
+                    "log_likelihood (the sample of the time point)" % (name, self._phase, self._phase))
+            return g.leaf("f", k)
+
+        object.__setattr__(inst, "forcing", _Forcings(cls, read))
         N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
         th = _Named([(n, g.leaf("th", s)) for s, n in enumerate(P)], "parameter")
         cs = [g.leaf("c", q) for q in range(C)]
@@ -970,6 +1033,8 @@ class Trace(object):
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
         self.c_slot = {NPU + q: NPU + k for k, q in enumerate(self.c_in_rhs)}
+        # the forcings' entries of p follow: K values, K slopes, one interval start (the struct's set_interval / set_point)
+        self.F0 = self.NP
 
     def _state_list(self, v, what, N):
         if not isinstance(v, (list, tuple)) or len(v) != N:
@@ -1002,6 +1067,8 @@ class _Emitter(object):
 
     def ref(self, n):
         if n.op == "const": return _lit(n.val)
+        if n.op == "f":  # (a forcing: the text of its value where this function is evaluated)
+            return self.leaf_names["f"][n.val]
         if n.op in _LEAVES:
             base = self.leaf_names[n.op]
             idx = self.p_map.get(n.val, n.val) if n.op == "p" else n.val
@@ -1162,8 +1229,15 @@ def generate_source(cls, neural=False):
     adj1 = vjp(g, tr.dy, v)
     rhs_vjp = pull(adj1, [("y", "yb"), ("p", "pb")])
 
-    def body(assign, fast, seed, p_map=None):
-        names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp", "ob": "ob", "pr": "pr"}
+    # forcings: entries F0 .. of p hold K values, K slopes and the interval start; rhs (and its adjoint) reads the interpolant
+    # at its stage time, a hook the value (set_point: the sample of the time point)
+    K, F0 = len(tr.forcings), tr.F0
+    f_at_t = ["(p[%d] + (t - p[%d]) * p[%d])" % (F0 + k, F0 + 2 * K, F0 + K + k) for k in range(K)]
+    f_at_point = ["p[%d]" % (F0 + k) for k in range(K)]
+
+    def body(assign, fast, seed, p_map=None, forcing=None):
+        names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp", "ob": "ob", "pr": "pr",
+                 "f": forcing}
         return "\n".join(_Emitter(fast, names, p_map).emit(assign))
 
     names = ", ".join('"%s"' % n for n in P)
@@ -1202,9 +1276,24 @@ def generate_source(cls, neural=False):
         adj = vjp(g, outs, [g.leaf("seed", j) for j in range(4)])
         if h.switch_note:
             hook_decl.append("  static constexpr bool %s = true;  // %s" % (h.switch, h.switch_note))
-        hook_decl += h.c_forward + [body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in enumerate(outs)], True, h.seed, tr.c_slot),
-                                    "  }"]
-        hook_decl += h.c_adjoint + [body(pull(adj, h.targets), True, h.seed, tr.c_slot), "  }"]
+        hook_decl += h.c_forward + [body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in enumerate(outs)], True, h.seed, tr.c_slot,
+                                         f_at_point), "  }"]
+        hook_decl += h.c_adjoint + [body(pull(adj, h.targets), True, h.seed, tr.c_slot, f_at_point), "  }"]
+    forcing_decl = []
+    if K:
+        forcing_decl = [
+            "  static constexpr int N_FORCINGS = %d;  // %s: p[%d ..] values, p[%d ..] slopes, p[%d] the interval start" % (
+                K, ", ".join(tr.forcings), F0, F0 + K, F0 + 2 * K),
+            "  __device__ static void set_interval(float* p, float t_lo, float inv_dt, const float* u_lo, const float* u_hi) {",
+        ] + ["    p[%d] = u_lo[%d];" % (F0 + k, k) for k in range(K)] + [
+            "    p[%d] = (u_hi[%d] - u_lo[%d]) * inv_dt;" % (F0 + K + k, k, k) for k in range(K)] + [
+            "    p[%d] = t_lo;" % (F0 + 2 * K),
+            "  }",
+            "  __device__ static void set_point(float* p, const float* u) {",
+        ] + ["    p[%d] = u[%d];" % (F0 + k, k) for k in range(K)] + [
+            "    p[%d] = 0.f;" % (F0 + K + k) for k in range(K)] + [
+            "  }",
+        ]
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -1219,8 +1308,8 @@ def generate_source(cls, neural=False):
         "  static constexpr int NC = %d;" % C,
         "  static constexpr int OBS = %s;" % obs_enum,
         "  static constexpr int NSLOT = %d;" % len(P),
-        "  static constexpr int NP = %d;" % max(tr.NP, 1),
-    ] + net_decl + [
+        "  static constexpr int NP = %d;" % (max(tr.NP, 1) if not K else tr.NP + 2 * K + 1),
+    ] + forcing_decl + net_decl + [
         "  __host__ static const char* slot_name(int s) {",
         "    static const char* n[] = {%s};" % names,
         "    return n[s];",
@@ -1238,10 +1327,10 @@ def generate_source(cls, neural=False):
         body(init_vjp, False, "yb"),
         "  }",
     ] + rhs_sig + [
-        body(rhs, True, "v", tr.c_slot),
+        body(rhs, True, "v", tr.c_slot, f_at_t),
         "  }",
     ] + vjp_sig + [
-        body(rhs_vjp, True, "v", tr.c_slot),
+        body(rhs_vjp, True, "v", tr.c_slot, f_at_t),
         "  }",
     ] + hook_decl + [
         "};",
@@ -1362,6 +1451,7 @@ class GeneratedOdeModel(OdeModel):
     observe_kind = "default"
     _observe_def = _precision_def = _likelihood_def = None  # the definitions of the hooks the class has (HOOKS: attr)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
+    forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -1419,6 +1509,39 @@ class GeneratedOdeModel(OdeModel):
                 self.nets[name] = m
             self._flat_all = None
             object.__setattr__(self, "net", _Networks(type(self), self._torch_call(self.network_weights)))
+
+    # forcings: the samples travel in the rows of cond, behind the treatments
+    def row_inputs(self, data):
+        K = len(_class_forcings(type(self)))
+        if not K:
+            return data.inputs
+        f = data.get("forcings", None) if hasattr(data, "get") else getattr(data, "forcings", None)
+        if f is None:
+            raise RuntimeError("%s declares forcings %s: every batch needs 'forcings' [rows, %d, times] beside 'inputs'"
+                               % (type(self).__name__, list(type(self).forcings), K))
+        B = data.inputs.shape[0]
+        if f.dim() != 3 or f.shape[0] != B or f.shape[1] != K:
+            raise RuntimeError("%s: 'forcings' must be [%d rows, %d forcings, times], got %s"
+                               % (type(self).__name__, B, K, list(f.shape)))
+        return torch.cat([data.inputs, f.to(data.inputs.device, data.inputs.dtype).reshape(B, -1)], dim=1)
+
+    def cond_width(self, n_times=None):
+        K = len(_class_forcings(type(self)))
+        if K and n_times is None:
+            raise RuntimeError("%s declares forcings: the width of a row of cond depends on the number of time points"
+                               % type(self).__name__)
+        return self.n_treatments + (K * int(n_times) if K else 0)
+
+    def solve(self, config, times, theta, conditions, dev_1hot, observations=None, request=None):
+        K = len(_class_forcings(type(self)))
+        if K:  # (checked before anything is built or queued)
+            if config.params.solver in hip.ADAPTIVE_SOLVERS:
+                raise NotImplementedError(
+                    "%s declares forcings, whose samples live on the observation grid: the adaptive solver '%s' integrates on a "
+                    "grid of its own and is not available to it (fixed-grid solvers: %s)" % (
+                        type(self).__name__, config.params.solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+            _check_forcing_width(type(self), conditions.shape[1], len(times), self.n_treatments)
+        return super(GeneratedOdeModel, self).solve(config, times, theta, conditions, dev_1hot, observations, request=request)
 
     def __setattr__(self, name, value):
         if name == "precisions" and value is not None and type(self)._precision_def is not None:
@@ -1510,9 +1633,11 @@ class GeneratedOdeModel(OdeModel):
         return call
 
     @classmethod
-    def torch_problem(cls, th, cond, weights=None):
+    def torch_problem(cls, th, cond, weights=None, times=None):
         """(rhs, x0) in the convention of oracle.make_*: th maps parameter names to [B, S] tensors, cond is [B, C] (log(1 +
-        treatment), as the data holds it); rhs(t, state [B, S, N]) -> [B, S, N] of the species (no precision states).
+        treatment), as the data holds it; for a class with K forcings the wide rows [n_conditions treatments | K x T samples,
+        forcing-major], and `times` [T] is then required: rhs interpolates the samples linearly at its t); rhs(t, state
+        [B, S, N]) -> [B, S, N] of the species (no precision states).
         weights: {network name: (W1 [H][I], b1 [H], W2 [O][H], b2 [O])} for a model with networks (an instance's
         network_weights(), or tensors of the caller's own that require grad: autograd then gives the weight gradients)."""
         inst = cls.__new__(cls)
@@ -1526,6 +1651,18 @@ class GeneratedOdeModel(OdeModel):
         B, S = th[cls.parameter_names[0]].shape
         ref = th[cls.parameter_names[0]]
         cs = _treatments_torch(cls, cond, ref, S)
+        names, now = _class_forcings(cls), {}
+        if names:
+            if times is None:
+                raise ValueError("%s.torch_problem needs times=: the class declares forcings %s, sampled on the time grid"
+                                 % (cls.__name__, names))
+            tg = torch.as_tensor(times).to(ref.dtype).to(ref.device)
+            series = _forcing_series(cls, cond, ref, tg.shape[0])  # [B, K, T]
+
+            def no_forcing(_k, name):
+                raise ModelDefinitionError("forcing '%s' read outside rhs" % name)
+
+            object.__setattr__(inst, "forcing", _Forcings(cls, lambda k, name: now["u"][k] if now else no_forcing(k, name)))
         thn = _Named([(n, th[n]) for n in cls.parameter_names], "parameter")
         full = lambda v: v if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
         p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
@@ -1533,6 +1670,13 @@ class GeneratedOdeModel(OdeModel):
 
         def rhs(t, state):
             y = list(torch.unbind(state[:, :, :N], dim=2))
+            if names:
+                # the linear interpolant of the row's samples at t: on [t_k, t_k+1], u_k + (t - t_k) (u_k+1 - u_k) / (t_k+1 - t_k)
+                tt = torch.as_tensor(t, dtype=ref.dtype, device=ref.device)
+                k = int(torch.searchsorted(tg, tt.reshape(1), right=True)[0]) - 1
+                k = min(max(k, 0), tg.shape[0] - 2)
+                u = series[:, :, k] + (tt - tg[k]) * (series[:, :, k + 1] - series[:, :, k]) / (tg[k + 1] - tg[k])
+                now["u"] = [u[:, j, None].expand(B, S) for j in range(len(names))]
             return torch.stack([full(v) for v in inst.rhs(t, y, p, _Conditions(cs))], dim=2)
 
         return rhs, x0
@@ -1607,8 +1751,25 @@ class GeneratedOdeModel(OdeModel):
 
 def _treatments_torch(cls, cond, like, S):
     """The treatments c of cond [B,C] (as the data holds it) in `like`'s dtype: C tensors [B,S]."""
-    tt = torch.clamp(torch.exp(cond.to(like.dtype)) - 1.0, 1e-12, 1e6)
-    return [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(int(cls.n_conditions))]
+    C = int(cls.n_conditions)
+    tt = torch.clamp(torch.exp(cond[:, :C].to(like.dtype)) - 1.0, 1e-12, 1e6)  # (forcing samples may follow: used raw)
+    return [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(C)]
+
+
+def _check_forcing_width(cls, width, n_times, n_treatments=None):
+    """A row of cond is [treatments | K x T samples].  n_treatments: how many treatments the rows hold (an instance knows: its
+    data may carry more than the n_conditions the model reads); None: at least the model's n_conditions."""
+    K, C = len(_class_forcings(cls)), int(cls.n_conditions) if n_treatments is None else int(n_treatments)
+    if width - C != K * n_times and (n_treatments is not None or width - K * n_times < C):
+        raise ValueError("%s reads %d forcing(s) on %d time points: a row of cond must hold %d samples behind its %d treatment(s), "
+                         "and holds %d (width %d)" % (cls.__name__, K, n_times, K * n_times, C, width - C, width))
+
+
+def _forcing_series(cls, cond, like, n_times):
+    """The forcing samples of the wide cond [B, C] in `like`'s dtype: [B, K, T], the last K * T columns of each row, raw."""
+    K = len(_class_forcings(cls))
+    _check_forcing_width(cls, cond.shape[1], n_times)
+    return cond[:, cond.shape[1] - K * n_times:].to(like.dtype).to(like.device).reshape(cond.shape[0], K, n_times)
 
 
 def _hook_torch(cls, h, inst, groups, th, cond):
@@ -1619,6 +1780,9 @@ def _hook_torch(cls, h, inst, groups, th, cond):
     thn = _Named([(n, th[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
     over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
     p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
+    if _class_forcings(cls):  # the samples of every time point, [B,1,T] each
+        series = _forcing_series(cls, cond, ref, ref.shape[-1])
+        object.__setattr__(inst, "forcing", _Forcings(cls, lambda k, _name: series[:, k, None, :]))
     out = getattr(cls, h.attr)(inst, *[list(torch.unbind(v, dim=2)) for v in groups], p, _Conditions([over_time(v) for v in cs]))
     full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
     return torch.stack([full(v) for v in out], dim=2)
@@ -1654,6 +1818,18 @@ def _validate(cls):
             ", 4 of them for the precisions" if n_prec_slots else ": a model with a precision map of its own has all of them"))
     if not isinstance(cls.n_conditions, int) or cls.n_conditions < 0:
         raise ModelDefinitionError("%s.n_conditions must be an integer >= 0" % name)
+    forc = getattr(cls, "forcings", None) or ()
+    if not isinstance(forc, (list, tuple)) or not all(isinstance(f, str) and f.isidentifier() for f in forc):
+        raise ModelDefinitionError("%s.forcings must be a list of names (valid identifiers)" % name)
+    if len(set(forc)) != len(forc):
+        raise ModelDefinitionError("%s.forcings has duplicates" % name)
+    clash = [f for f in forc if f in cls.species or f in cls.parameter_names]
+    if clash:
+        raise ModelDefinitionError("%s.forcings: %s %s also a species or a parameter; a forcing needs a name of its own"
+                                   % (name, ", ".join("'%s'" % f for f in clash), "is" if len(clash) == 1 else "are"))
+    if len(forc) > MAX_FORCINGS:
+        raise ModelDefinitionError("%s: %d forcings; a generated model reads at most %d (MAX_FORCINGS)"
+                                   % (name, len(forc), MAX_FORCINGS))
     nets = getattr(cls, "networks", None)
     if nets is None:
         return

@@ -129,7 +129,7 @@ def likelihood_route(request, ode, config, theta, times, observations):
     packed, row_of = theta.pack(ode.kernel_slots())
     if not packed.is_cuda or (grad and not packed.requires_grad):
         return plain
-    spec, shape = ode._spec(config, row_of, packed.shape[0]), (packed.shape[1], packed.shape[2], times.shape[0])
+    spec, shape = ode._spec(config, row_of, packed.shape[0], times.shape[0]), (packed.shape[1], packed.shape[2], times.shape[0])
     if grad:
         fits = not ode._fused_declined.get((ODE_LOGLIK_FUSED,) + shape + (prm.solver,))
     else:
@@ -312,8 +312,18 @@ class OdeModel(nn.Module):
 
         return hip.model_slots(self.model_key)
 
-    def _spec(self, config, row_of, n_rows):
-        key = (config.params.solver, n_rows, tuple(sorted(row_of.items())))
+    def row_inputs(self, data):
+        """The rows of `cond` the kernels read for a batch: the treatments.  (A generated model with forcings appends their
+        samples, vihds/modelgen.py; callers that solve for a batch pass this, not data.inputs.)"""
+        return data.inputs
+
+    def cond_width(self, n_times=None):
+        """Floats per row of cond (the problem's C) on a grid of n_times points."""
+        return self.n_treatments
+
+    def _spec(self, config, row_of, n_rows, n_times=None):
+        C = self.cond_width(n_times)
+        key = (config.params.solver, n_rows, tuple(sorted(row_of.items())), C)
         if key not in self._spec_cache:
             # params.adjoint_solver (reference ode.py:80: torchdiffeq.odeint_adjoint, the continuous adjoint) selects
             # nothing here: every solver differentiates through the discrete adjoint of its own accepted steps, which is
@@ -322,7 +332,7 @@ class OdeModel(nn.Module):
             # params.kernel_variant: 0 = the library's choice, 1 thread-per-trajectory, 2 lane-split, 3 time-parallel
             kw.setdefault("kernel_variant", int(default_get_value(config.params, "kernel_variant", 0)))
             self._spec_cache[key] = ops.OdeProblemSpec(self.model_key, config.params.solver, row_of, n_rows,
-                                                       C=self.n_treatments, D=self.device_depth, **kw)
+                                                       C=C, D=self.device_depth, **kw)
         return self._spec_cache[key]
 
     def solve(self, config, times, theta, conditions, dev_1hot, observations=None, request=None):
@@ -334,7 +344,7 @@ class OdeModel(nn.Module):
         slots = self.kernel_slots()
         packed, row_of = theta.pack(slots)
         self._last_inputs = (packed, row_of, conditions)
-        spec = self._spec(config, row_of, packed.shape[0])
+        spec = self._spec(config, row_of, packed.shape[0], len(times))
         dev = packed.device
         times = times.to(dev)
         if config.params.solver in hip.ADAPTIVE_SOLVERS:

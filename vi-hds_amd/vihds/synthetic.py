@@ -176,7 +176,7 @@ def simulate_observations(settings, parameters, dataset, device, seed=0, noise=0
     for name in ode.kernel_slots():
         if name not in th.samples:  # aR / aS of the double-receiver family
             setattr(th, name, torch.full((n, 1), 1.5, device=device))
-    sol = ode.solve(settings, dataset.times, th, dataset.inputs.to(device), dev1)
+    sol = ode.solve(settings, dataset.times, th, ode.row_inputs(dataset).to(device), dev1)
     xp = sol.x_predict[:, 0].detach().cpu()  # [n,4,T]
     scale = xp.amax(dim=(0, 2), keepdim=True).clamp_min(1e-6)
     obs = xp / scale + noise * torch.randn(xp.shape, generator=g)

@@ -46,6 +46,8 @@ def batch_to_device(times, device, d):
     d["dev_1hot"] = d["dev_1hot"].to(device)
     d["inputs"] = d["inputs"].to(device)
     d["observations"] = d["observations"].to(device).contiguous()
+    if d.get("forcings", None) is not None:  # per-row time series of a generated model with forcings [rows, K, T]
+        d["forcings"] = d["forcings"].to(device).float().contiguous()
     return attrify(d)
 
 
@@ -57,6 +59,8 @@ def collate_merged(times, device, batch):
         "inputs": torch.stack([torch.as_tensor(b["inputs"], dtype=torch.float32) for b in batch]),
         "observations": torch.stack([torch.as_tensor(b["observations"], dtype=torch.float32) for b in batch]),
     }
+    if batch and "forcings" in batch[0]:
+        dd["forcings"] = torch.stack([torch.as_tensor(b["forcings"], dtype=torch.float32) for b in batch])
     return batch_to_device(times, device, dd)
 
 
@@ -785,7 +789,7 @@ class Training:
                 return out
         g, static, loss = self._graphs[key]
         if self._staged.get(key) is not batch:  # a batch that is already resident in the graph's inputs is not re-copied
-            for k in ("dev_1hot", "inputs", "observations", "times"):
+            for k in ("dev_1hot", "inputs", "observations", "times") + (("forcings",) if "forcings" in static else ()):
                 static[k].copy_(batch[k], non_blocking=True)
             static["delta_obs"].copy_(_delta_obs(static.observations))
             self._staged[key] = batch
@@ -816,6 +820,10 @@ class Training:
                                           hip.ptr(out.inputs), hip.ptr(out.dev_1hot), hip.ptr(out.delta_obs),
                                           hip.current_stream())
         hip.check(rc, "vihds_gather_batch")
+        if "forcings" in src:  # (a generated model's per-row time series travel with the rows)
+            if "forcings" not in out:
+                out["forcings"] = torch.empty((B,) + tuple(src.forcings.shape[1:]), device=dev)
+            torch.index_select(src.forcings, 0, rows, out=out.forcings)
         return out
 
     class _IndexStaging:

@@ -107,7 +107,7 @@ class BaseVAE(nn.Module):
 
         def spec_of(names):
             row_of = {n: k for k, n in enumerate(list(names) + extra)}
-            return ode._spec(cfg, row_of, len(names) + len(extra))
+            return ode._spec(cfg, row_of, len(names) + len(extra), len(data.times))
 
         n_q = len(q.names())
         cond_job = None
@@ -116,7 +116,7 @@ class BaseVAE(nn.Module):
             cond_job = (len(extra), n_q, mean, std, z, rng_state, rel, dflt)
         if window is not None and not isinstance(u, ops.KernelNormal):
             return None  # (the conditioner tiling needs the window; only the in-kernel draw carries it)
-        theta, logp = q.decoder_step_fused(u, p, 4, n_extra, spec_of, data.inputs, data.times.to(obs.device), obs,
+        theta, logp = q.decoder_step_fused(u, p, 4, n_extra, spec_of, ode.row_inputs(data), data.times.to(obs.device), obs,
                                            data.dev_1hot, cond_job)
         for k, n in enumerate(extra):
             theta.bind_reserved_row(n, n_q + k)
@@ -127,7 +127,7 @@ class BaseVAE(nn.Module):
         # params.fused_iwae_backward: Training.cost may leave the IWAE loss to this step's theta-adjoint launch
         defer = bool(default_get_value(cfg.params, "fused_iwae_backward", True)) and self.shard is None
         sol = O.LazySolution(logp, O.ForwardRecord(O.DECODER_STEP_FUSED, logp.grad_fn, defer_iwae=defer),
-                             lambda: ode.solve(cfg, data.times, theta, data.inputs, data.dev_1hot, obs))
+                             lambda: ode.solve(cfg, data.times, theta, ode.row_inputs(data), data.dev_1hot, obs))
         ode._last = sol
         return on_demand_result(ode, theta, data.times, sol), theta
 
@@ -149,9 +149,9 @@ class BaseVAE(nn.Module):
             if blackbox:  # the integrator reads the device-conditioned rows (condition_theta re-binds y1.. to them)
                 for i in range(ode.n_y):
                     row_of["y%d" % (i + 1)] = n_q + i
-            return ode._spec(cfg, row_of, len(names) + len(extra))
+            return ode._spec(cfg, row_of, len(names) + len(extra), len(data.times))
 
-        theta, traj, logp = q.theta_ode_fused(u, p, 4, len(extra), spec_of, data.inputs, data.times.to(obs.device), obs,
+        theta, traj, logp = q.theta_ode_fused(u, p, 4, len(extra), spec_of, ode.row_inputs(data), data.times.to(obs.device), obs,
                                               data.dev_1hot, ode.neural_weights(), offset)
         if blackbox:
             for i in range(ode.n_y):  # (what condition_theta does: the attribute now names the conditioned row)
