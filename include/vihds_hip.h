@@ -73,7 +73,12 @@ enum vihds_solver {
   VIHDS_SOLVER_ADAPTIVE_HEUN = 7, /* Heun-Euler 2(1) */
   VIHDS_SOLVER_DOPRI8 = 8,        /* `solver: dopri8`: an 8th-order Dormand-Prince pair -- Hairer's DOP853 (12 stages), NOT
                                      torchdiffeq's 8(7) 13-stage tableau (unavailable offline); same controller */
-  VIHDS_SOLVER_COUNT = 9
+  /* `solver: beuler`: backward Euler on the observation grid, y' = y + h f(t1, y'), by a fixed number of Newton iterations
+     from y (no convergence test), the linear solves by unpivoted elimination in registers; the adjoint is the
+     implicit-function theorem's at the stored y'.  For generated models with `implicit = True` only (their struct has the
+     Jacobian, vihds/modelgen.py); every other model answers VIHDS_E_UNSUPPORTED. */
+  VIHDS_SOLVER_BEULER = 9,
+  VIHDS_SOLVER_COUNT = 10
 };
 
 #define VIHDS_MAX_SLOTS 64

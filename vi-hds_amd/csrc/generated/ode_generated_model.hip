@@ -1,6 +1,6 @@
 // One model generated from a Python definition (vihds/modelgen.py; see ../vihds_gen_model.hpp) as a side library, built with
 //   -DVIHDS_GEN_HEADER="<generated header>"
-// as ten objects compiled in parallel (Makefile, target `generated`): one per solver (-DVIHDS_ONLY_SOLVER=<id>: the
+// as eleven objects compiled in parallel (Makefile, target `generated`): one per solver (-DVIHDS_ONLY_SOLVER=<id>: the
 // kernels of that solver behind vihds_gen_launch_<id>) and the table object (no VIHDS_ONLY_SOLVER: the GenModelRecord
 // that dispatches to them).  The generated header defines VIHDS_GEN_CORE (the struct) and VIHDS_GEN_NEURAL (0 / 1).
 #include "../vihds_ode_kernels.hpp"
@@ -24,6 +24,8 @@ static_assert(!(VIHDS_GEN_NEURAL != 0 && own_prec<VIHDS_GEN_CORE>::value),
               "a model with a precision map of its own does not take NeuralPrecisions");
 static_assert(!(VIHDS_GEN_NEURAL != 0 && own_lik<VIHDS_GEN_CORE>::value),
               "a model with an observation log density of its own does not take NeuralPrecisions");
+static_assert(!(VIHDS_GEN_NEURAL != 0 && has_jacobian<VIHDS_GEN_CORE>::value),
+              "an implicit model does not take NeuralPrecisions: the precision ODE has no Jacobian");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
@@ -40,8 +42,9 @@ extern "C" int VIHDS_GEN_CAT(vihds_gen_launch_, VIHDS_ONLY_SOLVER)(bool backward
 #define VIHDS_GEN_DECL(k) \
   extern "C" int vihds_gen_launch_##k(bool, int, const vihds::OdeArgs&, hipStream_t, const vihds::LaunchMode&);
 VIHDS_GEN_DECL(0) VIHDS_GEN_DECL(1) VIHDS_GEN_DECL(2) VIHDS_GEN_DECL(3) VIHDS_GEN_DECL(4) VIHDS_GEN_DECL(5)
-VIHDS_GEN_DECL(6) VIHDS_GEN_DECL(7) VIHDS_GEN_DECL(8)
-static_assert(VIHDS_SOLVER_COUNT == 9, "one object per solver: extend the table and the Makefile");
+VIHDS_GEN_DECL(6) VIHDS_GEN_DECL(7) VIHDS_GEN_DECL(8) VIHDS_GEN_DECL(9)
+// (object 9, the implicit solver: kernels for a model generated with implicit = True, a declining function for any other)
+static_assert(VIHDS_SOLVER_COUNT == 10, "one object per solver: extend the table and the Makefile");
 namespace vihds {
 // (the entry points of vihds_api.hip decline the sampling stage, the one-pass summaries and the device-resident adaptive
 // solver for registered models before any launcher is called: of the launch modes only the host-driven controller arrives here)
@@ -59,7 +62,8 @@ static const char* const* slot_names_gen() {
 static int launch_gen(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   static const gen_launch_fn table[VIHDS_SOLVER_COUNT] = {vihds_gen_launch_0, vihds_gen_launch_1, vihds_gen_launch_2,
                                                           vihds_gen_launch_3, vihds_gen_launch_4, vihds_gen_launch_5,
-                                                          vihds_gen_launch_6, vihds_gen_launch_7, vihds_gen_launch_8};
+                                                          vihds_gen_launch_6, vihds_gen_launch_7, vihds_gen_launch_8,
+                                                          vihds_gen_launch_9};
   if (solver < 0 || solver >= VIHDS_SOLVER_COUNT) return VIHDS_E_BADARG;
   return table[solver](backward, solver, a, st, mode);
 }
@@ -70,7 +74,7 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
   static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, traj_rows<GenM>::value, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
                                    slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
                                    net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
-                                   n_forcings<GenM>::value};
+                                   n_forcings<GenM>::value, has_jacobian<GenM>::value ? 1 : 0};
   return &r;
 }
 #endif

@@ -46,8 +46,11 @@ extern "C" int VIHDS_BB_CAT(vihds_bb_launch_, VIHDS_ONLY_SOLVER)(bool backward, 
   extern "C" int vihds_bb_launch_##k(bool, int, const vihds::OdeArgs&, hipStream_t, const vihds::LaunchMode&);
 VIHDS_BB_DECL(0) VIHDS_BB_DECL(1) VIHDS_BB_DECL(2) VIHDS_BB_DECL(3) VIHDS_BB_DECL(4) VIHDS_BB_DECL(5) VIHDS_BB_DECL(6)
 VIHDS_BB_DECL(7) VIHDS_BB_DECL(8)
-static_assert(VIHDS_SOLVER_COUNT == 9, "one object per solver: extend the table and the Makefile");
+static_assert(VIHDS_SOLVER_COUNT == 10 && VIHDS_SOLVER_BEULER == 9,
+              "one object per solver 0..8, and the implicit solver, which dr_blackbox declines: extend the table and the Makefile");
 namespace vihds {
+// (dr_blackbox has no generated Jacobian: no object is built for the implicit solver)
+static int launch_declined(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&) { return VIHDS_E_UNSUPPORTED; }
 static int n_weights_sized(int n_const) { return BBV::n_weights(n_const); }
 static long long gram_floats_sized(int n) { return BBV_MFMA ? (long long)KV::gram_floats(n) : -1; }
 static void gram_reduce_sized(const OdeArgs& a, const float* aux, float* g_weights, hipStream_t st) {
@@ -56,7 +59,8 @@ static void gram_reduce_sized(const OdeArgs& a, const float* aux, float* g_weigh
 static int launch_sized(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   static const bb_launch_fn table[VIHDS_SOLVER_COUNT] = {vihds_bb_launch_0, vihds_bb_launch_1, vihds_bb_launch_2,
                                                          vihds_bb_launch_3, vihds_bb_launch_4, vihds_bb_launch_5,
-                                                         vihds_bb_launch_6, vihds_bb_launch_7, vihds_bb_launch_8};
+                                                         vihds_bb_launch_6, vihds_bb_launch_7, vihds_bb_launch_8,
+                                                         launch_declined};
   if (solver < 0 || solver >= VIHDS_SOLVER_COUNT) return VIHDS_E_BADARG;
   return table[solver](backward, solver, a, st, mode);
 }

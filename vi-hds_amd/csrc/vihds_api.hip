@@ -113,6 +113,8 @@ struct ModelEntry {
   // a registered model with forcings (GenModelRecord::n_forcings): that many series of T samples per row of cond behind the
   // treatments
   int n_forcings = 0;
+  // a registered model with a generated Jacobian (GenModelRecord::implicit): the only kind that takes an implicit solver
+  bool implicit = false;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
   bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
   int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
@@ -167,7 +169,7 @@ static ModelEntry g_gen_entries[VIHDS_GEN_MODEL_MAX];
 static std::atomic<int> g_gen_count{0};
 static ModelEntry gen_entry_of(const GenModelRecord* r) {
   return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
-          r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings};
+          r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -251,6 +253,8 @@ static long long bb_aux_floats(const BbVariant* v, const vihds_ode_problem* p) {
 static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& a, const BbVariant* v = nullptr) {
   if (p->B <= 0 || p->S <= 0 || p->T < 2) return fail(VIHDS_E_BADARG, "B, S must be > 0 and T >= 2");
   if ((long long)p->B * p->S > 0x7fffffffLL) return fail(VIHDS_E_BADARG, "B*S exceeds int range");
+  if (solver_is_implicit(p->solver) && !e->implicit)
+    return fail(VIHDS_E_UNSUPPORTED, "solver 9 (beuler) needs a generated model with implicit = True: this model has no Jacobian");
   if (p->C < e->n_cond) return fail(VIHDS_E_BADARG, "the model reads more treatments per row than C provides");
   if (e->n_forcings > 0 && (long long)p->C < (long long)e->n_cond + (long long)e->n_forcings * p->T)
     return fail(VIHDS_E_BADARG, "the model reads n_forcings series of T samples per row behind its treatments: C is too small");
@@ -361,7 +365,8 @@ int vihds_model_register(const char* library_path) {
   if (r->n_slots + ((r->neural_prec || r->own_prec) ? 0 : 4) > VIHDS_MAX_SLOTS || r->n_states < (r->own_prec ? 5 : 1) ||
       (r->neural_prec && r->own_prec) || !r->launch || !r->slot_names ||
       !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT && r->observe_kind != OBS_CUSTOM) || r->n_net_weights < 0 ||
-      r->net_fields < 0 || (r->n_net_weights > 0) != (r->net_fields > 0) || r->n_forcings < 0) {
+      r->net_fields < 0 || (r->n_net_weights > 0) != (r->net_fields > 0) || r->n_forcings < 0 ||
+      (r->implicit && (r->neural_prec || r->n_net_weights > 0))) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
   }

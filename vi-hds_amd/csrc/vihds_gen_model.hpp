@@ -45,6 +45,9 @@ struct GenModelRecord {
   // forcings of the generated struct (vihds_models.hpp n_forcings<>): a data row of cond holds n_forcings series of T samples
   // behind its treatments, so a problem needs C >= n_cond + n_forcings * T; such a model takes the fixed-grid solvers only
   int n_forcings;
+  // 1: the generated struct has a Jacobian (rhs_jac, vihds_models.hpp has_jacobian<>) and the library the kernels of the
+  // implicit solvers (VIHDS_SOLVER_BEULER); 0: it declines them
+  int implicit;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

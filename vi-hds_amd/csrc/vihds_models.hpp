@@ -971,6 +971,17 @@ struct n_forcings<M, std::void_t<decltype(M::N_FORCINGS)>> {
   static constexpr int value = M::N_FORCINGS;
 };
 
+// A core generated with `implicit = True` (vihds/modelgen.py) declares NEWTON (the Newton iterations of one implicit step),
+// JAC_NZ (the structural non-zeros of its Jacobian, bit i N + j) and one more member of the time loop:
+//   rhs_jac(t, y, p, wg, J)     J[i N + j] = d dy_i / d y_j at (t, y), the forcings read as rhs reads them
+// Such a model takes the implicit solvers (vihds_implicit.hpp: VIHDS_SOLVER_BEULER), whose kernels are instantiated for it
+// alone.  False for every hand-written model and for WithPrec<> (the precision ODE has no Jacobian here; it declares none of
+// the three and does not forward its core's).
+template <class M, class = void>
+struct has_jacobian : std::false_type {};
+template <class M>
+struct has_jacobian<M, std::void_t<decltype(M::NEWTON), decltype(M::JAC_NZ)>> : std::true_type {};
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};

@@ -20,6 +20,7 @@
 #include "vihds_args.hpp"
 #include "vihds_models.hpp"
 #include "vihds_rk_adaptive.hpp"
+#include "vihds_implicit.hpp"
 #include "vihds_blackbox.hpp"
 #include "vihds_iwae_inline.hpp"
 
@@ -106,10 +107,14 @@ struct GenDumpCtx {
 struct NetSkipCtx {
   static constexpr bool DUMP = false;
 };
-__host__ __device__ inline int ode_stages(int solver) {
+// RHS evaluations the adjoint of one step dumps, explicit schemes (the dump contexts below ask on the device: a model with
+// weights of any kind has no implicit scheme, so their code is what it was)
+__host__ __device__ inline int explicit_stages(int solver) {
   if (solver_is_adaptive(solver)) return adaptive_stages(solver);
   return solver == VIHDS_SOLVER_EULER ? 1 : (solver == VIHDS_SOLVER_RK4 ? 4 : 2);
 }
+// ... of every solver: the adjoint of an implicit step has one vector-Jacobian product, at (t1, y_k+1)
+__host__ __device__ inline int ode_stages(int solver) { return solver_is_implicit(solver) ? 1 : explicit_stages(solver); }
 template <class M, bool BB = is_blackbox<M>::value, bool HAS_W = (M::NW > 0)>
 struct bwd_ctx {  // white-box
   using type = NoCtx;
@@ -151,7 +156,7 @@ struct bwd_ctx_sel<M, true, true> {
     using type = GenDumpCtx;
     __device__ static void init(type& c, const OdeArgs& a, int i) {
       c.n = (size_t)a.n;
-      c.fstride = (size_t)(a.T - 1) * ode_stages(a.solver) * a.n;
+      c.fstride = (size_t)(a.T - 1) * explicit_stages(a.solver) * a.n;
       c.net_dump = a.aux + i;
       c.dump = a.aux + (size_t)net_fields<M>::value * c.fstride + i;
       c.e = 0;
@@ -167,7 +172,7 @@ struct bwd_ctx_sel<M, true, false> {
     __device__ static void init(type& c, const OdeArgs& a, int i) {
       c.dump = a.aux + i;
       c.n = (size_t)a.n;
-      c.fstride = (size_t)(a.T - 1) * ode_stages(a.solver) * a.n;
+      c.fstride = (size_t)(a.T - 1) * explicit_stages(a.solver) * a.n;
       c.e = 0;
       VIHDS_UNROLL for (int k = 0; k < 8; ++k) c.bsum[k] = 0.f;
     }
@@ -178,6 +183,13 @@ struct bwd_ctx_sel<M, true, false> {
 template <class M, int SOLVER>
 __device__ __forceinline__ void ode_step(float t0, float t1, float h0, float* y, const float* p, const float* wts) {
   constexpr int N = M::N;
+  if constexpr (solver_is_implicit(SOLVER)) {  // backward Euler by M::NEWTON Newton iterations from y (vihds_implicit.hpp)
+    static_assert(has_jacobian<M>::value, "an implicit solver needs a model generated with implicit = True");
+    beuler_step<N, M::NEWTON, M::JAC_NZ>(
+        t1 - t0, y, [&](const float* z, float* fz) { M::rhs(t1, z, p, wts, fz); },
+        [&](const float* z, float* J) { M::rhs_jac(t1, z, p, wts, J); });
+    return;
+  }
   if constexpr (solver_is_adaptive(SOLVER)) {  // the accepted grid of an adaptive pair, its higher-order tableau
     rk_step_generic<M, Tableau<SOLVER>>(t0, t1 - t0, y, p, wts, nullptr);
     return;
@@ -304,6 +316,20 @@ __device__ __forceinline__ void ode_step_vjp(float t0, float t1, float h0, const
   }
 }
 
+// reverse of one implicit step, at the stored y_next = y_k+1 (no Newton iteration runs here): lam <- A^-T lam with
+// A = I - h J(t1, y_next), then pb += (h lam)^T df/dp by one rhs_vjp whose state output is discarded
+template <class M, class Ctx>
+__device__ __forceinline__ void ode_step_vjp_implicit(float t0, float t1, const float* y_next, const float* p,
+                                                      const float* wts, float* lam, float* pb, Ctx& wtsb) {
+  constexpr int N = M::N;
+  static_assert(has_jacobian<M>::value, "an implicit solver needs a model generated with implicit = True");
+  const float h = t1 - t0;
+  beuler_step_vjp<N, M::JAC_NZ>(h, y_next, lam, [&](const float* z, float* J) { M::rhs_jac(t1, z, p, wts, J); });
+  float v[N], unused[N];
+  VIHDS_UNROLL for (int j = 0; j < N; ++j) { v[j] = h * lam[j]; unused[j] = 0.f; }
+  call_vjp<M>(t1, y_next, p, wts, v, unused, pb, wtsb);
+}
+
 template <class M>
 __device__ __forceinline__ void load_theta(const OdeArgs& a, int i, int b, float* th, float* prec, float* c) {
   VIHDS_UNROLL for (int q = 0; q < M::NSLOT; ++q) th[q] = a.theta[(size_t)a.slot_row[q] * a.n + i];
@@ -346,6 +372,14 @@ struct ForcingFeed {
 };
 template <>
 struct ForcingFeed<0> {};
+// what the adjoint's time loop keeps for an implicit solver beside its forcing feed: the state of the previous iteration,
+// y_k+1 (N registers).  An explicit solver's loop declares the feed alone, as it did (bwd_feed_t), so its code is what it was.
+template <class Feed, int N>
+struct WithNextState : Feed {
+  float y_next[N];
+};
+template <int NF, int N, bool IMPLICIT>
+using bwd_feed_t = std::conditional_t<IMPLICIT, WithNextState<ForcingFeed<NF>, N>, ForcingFeed<NF>>;
 // ---- forward -------------------------------------------------------------------------------------
 // LDS_IN: the time grid and the observation rows of the data rows this block spans are staged in LDS once, so the
 // time loop holds no vector-memory loads and its trajectory / x_predict stores are never waited on (see
@@ -719,7 +753,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   float tHi = a.times[a.T - 1], tLo = tHi;
   // forcing samples travel with the times: ff.hi at tHi, ff.lo at tK, the next lower point's (ff.ahead) requested one
   // iteration ahead like tLo
-  ForcingFeed<NF> ff;
+  bwd_feed_t<NF, N, solver_is_implicit(SOLVER)> ff;  // (ForcingFeed<NF>; an implicit solver's also keeps y_k+1)
   if constexpr (NF > 0) {
     ff.src = a.cond + (size_t)b * a.C + (a.C - NF * a.T);
     VIHDS_UNROLL for (int j = 0; j < NF; ++j) { ff.ahead[j] = ff.src[j * a.T + a.T - 1]; ff.hi[j] = ff.ahead[j]; }
@@ -743,7 +777,12 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     if constexpr (NF > 0) {  // the interval (k, k + 1) ...
       if (k < a.T - 1) M::set_interval(p, tK, 1.f / (tHi - tK), ff.lo, ff.hi);
     }
-    if (k < a.T - 1) ode_step_vjp<M, SOLVER>(tK, tHi, h0, y, p, wts, lam, pb, wtsb);
+    if constexpr (solver_is_implicit(SOLVER)) {
+      if (k < a.T - 1) ode_step_vjp_implicit<M>(tK, tHi, ff.y_next, p, wts, lam, pb, wtsb);
+      VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
+    } else {
+      if (k < a.T - 1) ode_step_vjp<M, SOLVER>(tK, tHi, h0, y, p, wts, lam, pb, wtsb);
+    }
     tHi = tK;
     if constexpr (NF > 0) {  // ... then the point k, whose hook adjoints follow
       VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.hi[j] = ff.lo[j];
@@ -929,8 +968,28 @@ namespace vihds {
 
 template <class M, int ONLY>
 inline int launch_ode_any(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode);
+// An implicit solver: its forward and adjoint kernels exist for a model with a generated Jacobian only -- every other
+// launcher holds exactly the kernels it held without them and answers VIHDS_E_UNSUPPORTED.  The step-size controllers and the
+// one-pass summaries are declined: an implicit step is taken on the observation grid.
+template <class M, int ONLY>
+inline int launch_ode_implicit(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+  if constexpr (has_jacobian<M>::value) {
+    if (mode.summ || mode.dev || mode.grid) return VIHDS_E_UNSUPPORTED;
+    if constexpr (solver_built_in<ONLY>(VIHDS_SOLVER_BEULER)) {
+      if (solver == VIHDS_SOLVER_BEULER) {
+        if (backward) launch_bwd_s<M, VIHDS_SOLVER_BEULER>(a, st);
+        else launch_fwd_s<M, VIHDS_SOLVER_BEULER>(a, st);
+        return VIHDS_OK;
+      }
+    }
+    return VIHDS_E_BADARG;
+  } else {
+    return VIHDS_E_UNSUPPORTED;
+  }
+}
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+  if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
   if constexpr (n_forcings<M>::value > 0) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
@@ -959,6 +1018,7 @@ inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t s
 }
 template <class M, int ONLY>
 inline int launch_ode_any(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
+  if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
   if constexpr (net_fields<M>::value > 0 || M::OBS == OBS_CUSTOM || own_prec<M>::value || own_lik<M>::value) {
     // (a generated core with networks: neither family is instantiated -- their adjoints keep weight gradients in registers;
     // a model with an observation map of its own: the one-pass summaries know the fixed maps only; a model with a precision

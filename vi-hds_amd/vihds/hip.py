@@ -34,12 +34,17 @@ MODELS = {
 GENERATED_NETWORKS = {}
 # keys of registered models with a precision map of their own: four precision rows behind the species, no precision network
 GENERATED_OWN_PRECISION = set()
+# keys of registered models generated with `implicit = True` (a Jacobian in their struct): the only models an implicit solver takes
+GENERATED_IMPLICIT = set()
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
-           "adaptive_heun": 7, "dopri8": 8}
+           "adaptive_heun": 7, "dopri8": 8, "beuler": 9}
 # torchdiffeq's adaptive pairs (vihds_rk_adaptive.hpp); "dopri8" runs an 8th-order Dormand-Prince pair with Hairer's
 # DOP853 coefficients, not torchdiffeq's own 8(7) tableau (vihds_dop853_tableau.hpp)
 ADAPTIVE_SOLVERS = ("dopri5", "bosh3", "adaptive_heun", "dopri8")
+# implicit schemes on the observation grid (vihds_implicit.hpp): backward Euler by a fixed number of Newton iterations, for
+# generated models with `implicit = True` (vihds/modelgen.py).  Not adaptive: the captured training step takes them
+IMPLICIT_SOLVERS = ("beuler",)
 
 _c_float_p = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 

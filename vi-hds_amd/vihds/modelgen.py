@@ -128,6 +128,30 @@ p[t0]) p[s].  The adaptive solvers integrate on a grid that is not the observati
 (solve raises before anything is queued, the library answers VIHDS_E_UNSUPPORTED), as it declines the one-pass summaries.
 torch_problem takes the wide cond and `times`, the torch hooks cut the samples from the wide cond.
 
+Implicit models.  A kinetic model with one fast reaction is stiff, and the wide priors draw stiff samples even where the
+posterior mean is not: beyond h |lambda| of about 2.8 rk4 blows up on the observation grid, the loss goes non-finite and the
+step is skipped.  A class that sets
+
+        implicit = True                              # default False
+        newton_iterations = 4                        # 1 .. MAX_NEWTON_ITERATIONS, read by an implicit class only
+
+gets the Jacobian of rhs generated beside its adjoint -- the DAG differentiated row by row with constant one-hot seeds
+(jacobian_nodes; vjp itself is unchanged), emitted as the member rhs_jac(t, y, p, wg, J), J[i N + j] = d dy_i / d y_j, with the
+forcing reads of rhs, a structural zero as the literal 0.f, and the constants NEWTON and JAC_NZ (the structural pattern: the
+elimination leaves out every operation on a structural zero at compile time) -- and takes the solver "beuler" (hip.IMPLICIT_SOLVERS):
+backward Euler on the observation grid, y' = y + h f(t1, y'), by exactly NEWTON Newton iterations from y (no convergence test),
+each linear solve by Gaussian elimination without a pivot search in registers (a zero pivot gives inf / NaN, which reaches the
+non-finite-loss exit like any blow-up); the adjoint is the implicit-function theorem's at the stored y' and needs first
+derivatives only.  A step evaluates rhs at t1, where a forcing's interpolant is the sample u_k+1.  What it cannot do: Newton
+from y solves the step of a GROWING mode only while h times its rate stays well below 1 (I - h J is singular at 1) -- backward
+Euler is for fast DECAY; too few iterations leave a step that is not the converged one, and the adjoint is then not the
+gradient of what was computed (FastBinding of the tests needs 6).  It composes with observe, precision, log_likelihood, piecewise
+terms and forcings.  Refused in this version: together with networks (the Jacobian of a network with respect to its inputs is
+not generated), with NeuralPrecisions (the precision ODE has no Jacobian), with more than MAX_IMPLICIT_STATES = 8 species
+(the matrix lives in registers).  Any other model given "beuler" raises before anything is queued; the implicit model keeps
+every explicit solver.  A class without `implicit` generates byte for byte the text it generated before.  torch_jacobian
+evaluates the same DAG nodes with torch ops, to check the generator against autograd.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -164,6 +188,11 @@ OBSERVE_CUSTOM = "custom"  # observe_kind of a class that defines observe(y, p, 
 MAX_NETWORKS, MAX_NET_INPUTS, MAX_NET_HIDDEN, MAX_NET_OUTPUTS = 2, 16, 32, 8
 MAX_FORCINGS = 4  # time-varying inputs of a generated model (each costs the kernels two registers and a sample in flight)
 NET_ACTIVATIONS = ("relu", "tanh")
+# species of a model with `implicit = True`: the N x N matrix of a Newton step lives in registers beside the states, and its
+# structural pattern is one 64-bit constant.  Eight is what compiles without scratch when every species is in every
+# derivative (tests/test_modelgen_implicit_host.py builds that worst case)
+MAX_IMPLICIT_STATES = 8
+MAX_NEWTON_ITERATIONS = 8
 
 
 class ModelDefinitionError(TypeError):
@@ -1173,6 +1202,23 @@ def _network_functions(networks):
     return out
 
 
+def jacobian_nodes(cls):
+    """The Jacobian of rhs as DAG nodes, row by row: J[i][j] = d dy_i / d y_j, by reverse mode with constant one-hot seeds
+    (one vjp per row; nothing of vjp is special to it).  A structural zero is the constant 0."""
+    tr = cls._trace
+    g, N = tr.g, len(cls.species)
+    rows = []
+    for i in range(N):
+        adj = vjp(g, tr.dy, [1.0 if k == i else 0.0 for k in range(N)])
+        rows.append([adj.get(g.leaf("y", j).id, g.const(0.0)) for j in range(N)])
+    return rows
+
+
+def jacobian_pattern(cls):
+    """[N][N] bools: the entries of the Jacobian that are not structurally zero."""
+    return [[not _is_const(e, 0.0) for e in row] for row in jacobian_nodes(cls)]
+
+
 def _leaf_free(node, allowed):
     return all(n.op not in _LEAVES or n.op == "const" or n.op in allowed for n in _topo([node]))
 
@@ -1186,6 +1232,9 @@ def generate_source(cls, neural=False):
         if neural and h.excludes_neural and getattr(tr, h.traced) is not None:
             raise ModelDefinitionError("%s defines %s: a model with a %s of its own does not take NeuralPrecisions"
                                        % (cls.__name__, h.signature, h.excludes_neural))
+    if neural and cls.implicit:
+        raise ModelDefinitionError("%s has implicit = True: the precision ODE of NeuralPrecisions has no generated Jacobian, so an "
+                                   "implicit model takes constant precisions or a precision map of its own" % cls.__name__)
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -1294,6 +1343,22 @@ def generate_source(cls, neural=False):
             "    p[%d] = 0.f;" % (F0 + K + k) for k in range(K)] + [
             "  }",
         ]
+    # implicit = True: the Jacobian of rhs for the Newton step of the implicit solvers and for their adjoint (after everything
+    # above, so that the text of rhs and rhs_vjp is what the class generates without it)
+    implicit_decl, jac_decl = [], []
+    if cls.implicit:
+        J = jacobian_nodes(cls)
+        nz = [(i, j) for i in range(N) for j in range(N) if not _is_const(J[i][j], 0.0)]
+        mask = sum(1 << (i * N + j) for i, j in nz)
+        implicit_decl = [
+            "  static constexpr int NEWTON = %d;" % int(cls.newton_iterations),
+            "  static constexpr unsigned long long JAC_NZ = 0x%xull;  // structural non-zeros of rhs_jac, bit i * N + j: %d of %d" % (
+                mask, len(nz), N * N)]
+        jac_decl = ["  // J[i * N + j] = d dy[i] / d y[j]; a structural zero is the literal 0.f",
+                    "  __device__ static void rhs_jac(float t, const float* y, const float* p, const float*, float* J) {",
+                    body([("J[%d]" % (i * N + j), "=", J[i][j]) for i, j in nz], True, "v", tr.c_slot, f_at_t)]
+        jac_decl += ["    J[%d] = 0.f;" % (i * N + j) for i in range(N) for j in range(N) if (i, j) not in nz]
+        jac_decl += ["  }"]
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -1309,7 +1374,7 @@ def generate_source(cls, neural=False):
         "  static constexpr int OBS = %s;" % obs_enum,
         "  static constexpr int NSLOT = %d;" % len(P),
         "  static constexpr int NP = %d;" % (max(tr.NP, 1) if not K else tr.NP + 2 * K + 1),
-    ] + forcing_decl + net_decl + [
+    ] + implicit_decl + forcing_decl + net_decl + [
         "  __host__ static const char* slot_name(int s) {",
         "    static const char* n[] = {%s};" % names,
         "    return n[s];",
@@ -1332,7 +1397,7 @@ def generate_source(cls, neural=False):
     ] + vjp_sig + [
         body(rhs_vjp, True, "v", tr.c_slot, f_at_t),
         "  }",
-    ] + hook_decl + [
+    ] + jac_decl + hook_decl + [
         "};",
         "}  // namespace vihds",
         "#define VIHDS_GEN_CORE %s" % sname,
@@ -1434,6 +1499,8 @@ def register_kernel(cls, neural=False):
     hip.GENERATED_NETWORKS[key] = [net.sizes for net in _class_networks(cls).values()]
     if cls._trace.prec is not None:  # (four precision rows behind the species that are no NeuralPrecisions states)
         hip.GENERATED_OWN_PRECISION.add(key)
+    if cls.implicit:  # (the library holds the kernels of the implicit solvers)
+        hip.GENERATED_IMPLICIT.add(key)
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -1452,6 +1519,8 @@ class GeneratedOdeModel(OdeModel):
     _observe_def = _precision_def = _likelihood_def = None  # the definitions of the hooks the class has (HOOKS: attr)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
+    implicit = False  # True: the Jacobian of rhs is generated and the implicit solvers take the model (module docstring)
+    newton_iterations = 4  # Newton iterations of one implicit step, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -1533,6 +1602,9 @@ class GeneratedOdeModel(OdeModel):
         return self.n_treatments + (K * int(n_times) if K else 0)
 
     def solve(self, config, times, theta, conditions, dev_1hot, observations=None, request=None):
+        if config.params.solver in hip.IMPLICIT_SOLVERS and not type(self).implicit:  # (before anything is built or queued)
+            raise NotImplementedError("solver '%s' needs a generated model with implicit = True (%s generates no Jacobian)"
+                                      % (config.params.solver, type(self).__name__))
         K = len(_class_forcings(type(self)))
         if K:  # (checked before anything is built or queued)
             if config.params.solver in hip.ADAPTIVE_SOLVERS:
@@ -1680,6 +1752,38 @@ class GeneratedOdeModel(OdeModel):
             return torch.stack([full(v) for v in inst.rhs(t, y, p, _Conditions(cs))], dim=2)
 
         return rhs, x0
+
+    @classmethod
+    def torch_jacobian(cls, y, theta, cond, t=0.0, times=None):
+        """The generated Jacobian of rhs evaluated with torch ops in y's dtype -- the SAME DAG nodes rhs_jac is emitted from
+        (jacobian_nodes), not autograd: it exists to check the generator against autograd of torch_problem's rhs.  y [B,S,N]
+        species, theta {parameter name: [B,S]} -- prepare is applied to it first --, cond [B,C] as the data holds it (the wide
+        rows of a class with forcings, with `times` [T]: the interpolant at t) -> [B,S,N,N], entry [i][j] = d dy_i / d y_j."""
+        tr = cls._trace
+        N, NPU = len(cls.species), len(tr.p_names)
+        ref = y[:, :, 0]
+        th = {n: theta[n].to(ref.dtype) for n in cls.parameter_names}
+        cs = _treatments_torch(cls, cond, ref, ref.shape[1])
+        env = {("th", s): th[n] for s, n in enumerate(cls.parameter_names)}
+        env.update({("c", q): v for q, v in enumerate(cs)})
+        prepared = evaluate(tr.p_exprs, env)
+        env.update({("p", k): v.to(ref.dtype) for k, v in enumerate(prepared)})
+        env.update({("p", NPU + q): v for q, v in enumerate(cs)})  # (the treatments rhs reads sit behind the named parameters)
+        env.update({("y", j): y[:, :, j] for j in range(N)})
+        env[("t", 0)] = torch.as_tensor(t, dtype=ref.dtype, device=ref.device)
+        names = _class_forcings(cls)
+        if names:
+            if times is None:
+                raise ValueError("%s.torch_jacobian needs times=: the class declares forcings %s" % (cls.__name__, names))
+            tg = torch.as_tensor(times).to(ref.dtype).to(ref.device)
+            series = _forcing_series(cls, cond, ref, tg.shape[0])
+            k = int(torch.searchsorted(tg, env[("t", 0)].reshape(1), right=True)[0]) - 1
+            k = min(max(k, 0), tg.shape[0] - 2)
+            u = series[:, :, k] + (env[("t", 0)] - tg[k]) * (series[:, :, k + 1] - series[:, :, k]) / (tg[k + 1] - tg[k])
+            env.update({("f", j): u[:, j, None].expand_as(ref) for j in range(len(names))})
+        rows = jacobian_nodes(cls)
+        flat = evaluate([e for row in rows for e in row], env)
+        return torch.stack([v.to(ref.dtype).expand_as(ref) for v in flat], dim=2).reshape(ref.shape + (N, N))
 
     @classmethod
     def torch_observe(cls, y, theta, cond):
@@ -1831,6 +1935,19 @@ def _validate(cls):
         raise ModelDefinitionError("%s: %d forcings; a generated model reads at most %d (MAX_FORCINGS)"
                                    % (name, len(forc), MAX_FORCINGS))
     nets = getattr(cls, "networks", None)
+    if not isinstance(cls.implicit, (bool, np.bool_)):
+        raise ModelDefinitionError("%s.implicit must be True or False" % name)
+    if cls.implicit:
+        it = cls.newton_iterations
+        if isinstance(it, bool) or not isinstance(it, (int, np.integer)) or not 1 <= it <= MAX_NEWTON_ITERATIONS:
+            raise ModelDefinitionError("%s.newton_iterations = %r; an implicit step runs a fixed number of Newton iterations, "
+                                       "1 .. %d" % (name, it, MAX_NEWTON_ITERATIONS))
+        if nets:
+            raise ModelDefinitionError("%s has implicit = True and networks: the Jacobian of a network with respect to its inputs "
+                                       "is not generated (second derivatives would follow in the adjoint)" % name)
+        if len(cls.species) > MAX_IMPLICIT_STATES:
+            raise ModelDefinitionError("%s has implicit = True and %d species; the matrix of a Newton step lives in registers: at "
+                                       "most %d (MAX_IMPLICIT_STATES)" % (name, len(cls.species), MAX_IMPLICIT_STATES))
     if nets is None:
         return
     if not isinstance(nets, dict) or not all(isinstance(k, str) and k.isidentifier() and isinstance(v, Network)

@@ -88,6 +88,9 @@ class OdeProblemSpec:
         if solver not in hip.SOLVERS:
             raise NotImplementedError(
                 "solver '%s' is not implemented by the HIP path (available: %s)" % (solver, ", ".join(sorted(hip.SOLVERS))))
+        if solver in hip.IMPLICIT_SOLVERS and model not in hip.GENERATED_IMPLICIT:  # (before anything is asked of the library)
+            raise NotImplementedError("solver '%s' needs a generated model with implicit = True (model '%s' has no Jacobian)"
+                                      % (solver, model))
         self.model, self.solver = model, solver
         sized = False
         if model == "dr_blackbox":
