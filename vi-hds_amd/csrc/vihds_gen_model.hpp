@@ -48,6 +48,9 @@ struct GenModelRecord {
   // 1: the generated struct has a Jacobian (rhs_jac, vihds_models.hpp has_jacobian<>) and the library the kernels of the
   // implicit solvers (VIHDS_SOLVER_BEULER); 0: it declines them
   int implicit;
+  // steps a fixed-grid scheme takes over each observation interval (vihds_models.hpp substeps<>, >= 1); above 1 the model
+  // takes the fixed-grid solvers only and the library holds no kernel of an adaptive pair
+  int substeps;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

@@ -982,6 +982,19 @@ struct has_jacobian : std::false_type {};
 template <class M>
 struct has_jacobian<M, std::void_t<decltype(M::NEWTON), decltype(M::JAC_NZ)>> : std::true_type {};
 
+// A core generated with `substeps = m > 1` (vihds/modelgen.py) declares SUBSTEPS = m: every fixed-grid scheme takes m steps of
+// its own over each observation interval (vihds_substeps.hpp defines the sub-step times), the adjoint recomputes the
+// interval's intermediate states.  Such a model takes the fixed-grid solvers only.  1 for every hand-written model and for
+// WithPrec<> (a sub-stepped model does not take NeuralPrecisions; it does not forward its core's).
+template <class M, class = void>
+struct substeps {
+  static constexpr int value = 1;
+};
+template <class M>
+struct substeps<M, std::void_t<decltype(M::SUBSTEPS)>> {
+  static constexpr int value = M::SUBSTEPS;
+};
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};

@@ -21,6 +21,7 @@
 #include "vihds_models.hpp"
 #include "vihds_rk_adaptive.hpp"
 #include "vihds_implicit.hpp"
+#include "vihds_substeps.hpp"
 #include "vihds_blackbox.hpp"
 #include "vihds_iwae_inline.hpp"
 
@@ -330,6 +331,72 @@ __device__ __forceinline__ void ode_step_vjp_implicit(float t0, float t1, const 
   call_vjp<M>(t1, y_next, p, wts, v, unused, pb, wtsb);
 }
 
+// ---- sub-steps per observation interval (substeps<M> = MS > 1, vihds_substeps.hpp) -----------------------------------
+// Everything below is instantiated for a generated model with `substeps` above 1 only: the time loops reach it behind
+// `if constexpr (substeps<M>::value > 1)`, so every other model's kernels are what they were.
+
+// the forward's interval: MS steps of the scheme, a rolled loop (the code does not grow with MS)
+template <class M, int SOLVER>
+__device__ __forceinline__ void ode_substeps(float t0, float t1, float h0, float* y, const float* p, const float* wts) {
+  constexpr int MS = substeps<M>::value;
+  const SubGrid<MS> sg(t0, t1);
+  const float hm = SubGrid<MS>::fixed_step(h0);
+#pragma unroll 1
+  for (int j = 0; j < MS; ++j) ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, y, p, wts);
+}
+
+// Where the adjoint keeps an interval's intermediate states u_1 .. u_MS-1: ROWS = (MS - 1) * N rows of 256 floats in LDS.
+// Thread t reads and writes column t alone: no barrier, and the lanes of a wavefront touch consecutive banks.  Declared by
+// the kernels that call column() only (a launcher of any other model asks for no shared memory of this kind).
+template <int ROWS>
+struct SubstateLds {
+  static_assert(ROWS >= 1 && ROWS * 256 * sizeof(float) < 64 * 1024, "(substeps - 1) * N rows of 256 floats: under 64 KB");
+  __device__ static __forceinline__ float* column() {
+    __shared__ float rows[ROWS * 256];
+    return rows + threadIdx.x;
+  }
+};
+
+// reverse of one observation interval of MS sub-steps.  y is the stored y_k = u_0; y_next the stored y_k+1 = u_MS (read by an
+// implicit scheme only).  The intermediate states are stored nowhere: MS - 1 forward sub-steps from u_0 recompute them --
+// ode_step with SubGrid's times, exactly the forward's calls -- into LDS, then the step adjoints run for j = MS-1 down to 0.
+// An explicit scheme's adjoint starts from u_j, the implicit one's from u_j+1.  Both loops stay rolled.
+template <class M, int SOLVER, class Ctx>
+__device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, const float* y, const float* y_next,
+                                                 const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb) {
+  constexpr int N = M::N, MS = substeps<M>::value;
+  float* col = SubstateLds<(MS - 1) * N>::column();
+  const SubGrid<MS> sg(t0, t1);
+  const float hm = SubGrid<MS>::fixed_step(h0);
+  float u[N];
+  VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y[q];
+#pragma unroll 1
+  for (int j = 0; j < MS - 1; ++j) {  // u_j -> u_j+1, kept as row block j
+    ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, u, p, wts);
+    VIHDS_UNROLL for (int q = 0; q < N; ++q) col[(j * N + q) * 256] = u[q];
+  }
+  if constexpr (solver_is_implicit(SOLVER)) {
+    VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y_next[q];  // u_MS
+#pragma unroll 1
+    for (int j = MS - 1; j >= 0; --j) {
+      ode_step_vjp_implicit<M>(sg.at(j), sg.at(j + 1), u, p, wts, lam, pb, wtsb);
+      if (j > 0) {  // u_j for the sub-step below
+        VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 1) * N + q) * 256];
+      }
+    }
+  } else {  // (u holds u_MS-1)
+#pragma unroll 1
+    for (int j = MS - 1; j >= 0; --j) {
+      ode_step_vjp<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, u, p, wts, lam, pb, wtsb);
+      if (j > 1) {  // u_j-1 for the sub-step below
+        VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 2) * N + q) * 256];
+      } else {
+        VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y[q];
+      }
+    }
+  }
+}
+
 template <class M>
 __device__ __forceinline__ void load_theta(const OdeArgs& a, int i, int b, float* th, float* prec, float* c) {
   VIHDS_UNROLL for (int q = 0; q < M::NSLOT; ++q) th[q] = a.theta[(size_t)a.slot_row[q] * a.n + i];
@@ -469,7 +536,8 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     }
     if (k > 0) {
       if constexpr (NF > 0) M::set_interval(p, tA, 1.f / (tB - tA), ff.lo, ff.hi);
-      ode_step<M, SOLVER>(tA, tB, h0, y, p, wts);
+      if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts);  // (one interval, several steps)
+      else ode_step<M, SOLVER>(tA, tB, h0, y, p, wts);
       tA = tB;
       if constexpr (NF > 0) {
         VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.lo[j] = ff.hi[j];
@@ -777,7 +845,14 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     if constexpr (NF > 0) {  // the interval (k, k + 1) ...
       if (k < a.T - 1) M::set_interval(p, tK, 1.f / (tHi - tK), ff.lo, ff.hi);
     }
-    if constexpr (solver_is_implicit(SOLVER)) {
+    if constexpr (substeps<M>::value > 1) {  // (the interval's sub-states are recomputed from y = y_k: ode_substeps_vjp)
+      if constexpr (solver_is_implicit(SOLVER)) {
+        if (k < a.T - 1) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, y, ff.y_next, p, wts, lam, pb, wtsb);
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
+      } else {
+        if (k < a.T - 1) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, y, nullptr, p, wts, lam, pb, wtsb);
+      }
+    } else if constexpr (solver_is_implicit(SOLVER)) {
       if (k < a.T - 1) ode_step_vjp_implicit<M>(tK, tHi, ff.y_next, p, wts, lam, pb, wtsb);
       VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
     } else {
@@ -990,10 +1065,11 @@ inline int launch_ode_implicit(bool backward, int solver, const OdeArgs& a, hipS
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
-  if constexpr (n_forcings<M>::value > 0) {
+  if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
-    // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it
+    // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it.  A model with sub-steps
+    // likewise: they divide the intervals of a fixed-grid scheme, an adaptive pair chooses its own steps
     if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
 #define VIHDS_CASE(SV)                                           \
   case SV:                                                       \

@@ -36,6 +36,9 @@ GENERATED_NETWORKS = {}
 GENERATED_OWN_PRECISION = set()
 # keys of registered models generated with `implicit = True` (a Jacobian in their struct): the only models an implicit solver takes
 GENERATED_IMPLICIT = set()
+# registered generated models: key -> `substeps`, the steps a fixed-grid solver takes over each observation interval.  Above 1
+# the model declines the adaptive solvers (they choose their own steps)
+GENERATED_SUBSTEPS = {}
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8, "beuler": 9}

@@ -152,6 +152,25 @@ not generated), with NeuralPrecisions (the precision ODE has no Jacobian), with 
 every explicit solver.  A class without `implicit` generates byte for byte the text it generated before.  torch_jacobian
 evaluates the same DAG nodes with torch ops, to check the generator against autograd.
 
+Sub-steps.  The observation grid is the plate reader's, not the model's: a fixed-grid solver takes one step per interval of it.
+A class that sets
+
+        substeps = 4                                 # 1 .. MAX_SUBSTEPS = 8, an int; default 1
+
+has every fixed-grid solver (modeuler, modeulerwhile, euler, midpoint, rk4, beuler) take that many steps of its own scheme
+over each observation interval [t_k, t_k+1]: with hs = (t_k+1 - t_k) * (1.f / m), sub-step j runs from s_j to s_j+1, where
+s_j = fmaf((float)j, hs, t_k) for j < m and s_m = t_k+1 exactly; modeuler's fixed step h0 becomes h0 * (1.f / m); beuler starts
+each sub-step's Newton iteration from the previous sub-state, so a growing mode needs h * rate / m well below 1, not h * rate.
+Only the states at the observation points are stored, observed and scored: traj, x_predict and logp keep their shapes, and the
+float64 meaning is exactly the m = 1 scheme on the refined grid read at every m-th point.  A forcing's set_interval stays one
+call per observation interval: a sub-step reads the linear interpolant of the samples inside it.  The generated struct gains the
+one line SUBSTEPS = m (none at m = 1: such a class generates byte for byte the text it generated before); the kernels' time
+loops run a rolled loop of m steps, and the adjoint, which finds only y_k stored, recomputes the interval's m - 1 intermediate
+states into LDS ((m - 1) * species rows of 256 floats per block, at most MAX_SUBSTEP_ROWS = 56) before it runs the m step
+adjoints last to first.  Such a model takes the fixed-grid solvers only: an adaptive solver chooses its own steps and is
+declined (solve raises before anything is queued, the library answers VIHDS_E_UNSUPPORTED).  Refused in this version: together
+with networks and with NeuralPrecisions (the adjoint's dump holds one evaluation per stage and observation interval).
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -193,6 +212,11 @@ NET_ACTIVATIONS = ("relu", "tanh")
 # derivative (tests/test_modelgen_implicit_host.py builds that worst case)
 MAX_IMPLICIT_STATES = 8
 MAX_NEWTON_ITERATIONS = 8
+# steps of a fixed-grid scheme per observation interval (`substeps`).  The adjoint keeps the interval's intermediate states in
+# LDS, (substeps - 1) * species rows of 256 floats per block: eight species at 8 need 56 KB, which is what builds
+# (tests/test_modelgen_substeps_host.py compiles that worst case without scratch)
+MAX_SUBSTEPS = 8
+MAX_SUBSTEP_ROWS = 56  # (substeps - 1) * species: a block's static LDS ends at 64 KB
 
 
 class ModelDefinitionError(TypeError):
@@ -1235,6 +1259,10 @@ def generate_source(cls, neural=False):
     if neural and cls.implicit:
         raise ModelDefinitionError("%s has implicit = True: the precision ODE of NeuralPrecisions has no generated Jacobian, so an "
                                    "implicit model takes constant precisions or a precision map of its own" % cls.__name__)
+    if neural and cls.substeps > 1:
+        raise ModelDefinitionError("%s has substeps = %d: the adjoint's dump of the precision network holds one evaluation per "
+                                   "stage and observation interval, so a sub-stepped model takes constant precisions or a "
+                                   "precision map of its own" % (cls.__name__, cls.substeps))
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -1359,6 +1387,9 @@ def generate_source(cls, neural=False):
                     body([("J[%d]" % (i * N + j), "=", J[i][j]) for i, j in nz], True, "v", tr.c_slot, f_at_t)]
         jac_decl += ["    J[%d] = 0.f;" % (i * N + j) for i in range(N) for j in range(N) if (i, j) not in nz]
         jac_decl += ["  }"]
+    # substeps = m > 1: the one line the kernels' time loops read (vihds_models.hpp substeps<>); a class without it generates
+    # the text it generated before
+    substeps_decl = ["  static constexpr int SUBSTEPS = %d;" % int(cls.substeps)] if cls.substeps > 1 else []
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -1374,7 +1405,7 @@ def generate_source(cls, neural=False):
         "  static constexpr int OBS = %s;" % obs_enum,
         "  static constexpr int NSLOT = %d;" % len(P),
         "  static constexpr int NP = %d;" % (max(tr.NP, 1) if not K else tr.NP + 2 * K + 1),
-    ] + implicit_decl + forcing_decl + net_decl + [
+    ] + substeps_decl + implicit_decl + forcing_decl + net_decl + [
         "  __host__ static const char* slot_name(int s) {",
         "    static const char* n[] = {%s};" % names,
         "    return n[s];",
@@ -1501,6 +1532,7 @@ def register_kernel(cls, neural=False):
         hip.GENERATED_OWN_PRECISION.add(key)
     if cls.implicit:  # (the library holds the kernels of the implicit solvers)
         hip.GENERATED_IMPLICIT.add(key)
+    hip.GENERATED_SUBSTEPS[key] = int(cls.substeps)  # (above 1: the library holds the fixed-grid schemes only)
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -1521,6 +1553,7 @@ class GeneratedOdeModel(OdeModel):
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
     implicit = False  # True: the Jacobian of rhs is generated and the implicit solvers take the model (module docstring)
     newton_iterations = 4  # Newton iterations of one implicit step, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
+    substeps = 1  # steps a fixed-grid solver takes over each observation interval, 1 .. MAX_SUBSTEPS (module docstring)
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -1605,6 +1638,12 @@ class GeneratedOdeModel(OdeModel):
         if config.params.solver in hip.IMPLICIT_SOLVERS and not type(self).implicit:  # (before anything is built or queued)
             raise NotImplementedError("solver '%s' needs a generated model with implicit = True (%s generates no Jacobian)"
                                       % (config.params.solver, type(self).__name__))
+        if type(self).substeps > 1 and config.params.solver in hip.ADAPTIVE_SOLVERS:  # (before anything is built or queued)
+            raise NotImplementedError(
+                "%s has substeps = %d, which divide the observation intervals of a fixed-grid scheme: the adaptive solver '%s' "
+                "chooses its own steps and is not available to it (fixed-grid solvers: %s)" % (
+                    type(self).__name__, type(self).substeps, config.params.solver,
+                    ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         K = len(_class_forcings(type(self)))
         if K:  # (checked before anything is built or queued)
             if config.params.solver in hip.ADAPTIVE_SOLVERS:
@@ -1948,6 +1987,17 @@ def _validate(cls):
         if len(cls.species) > MAX_IMPLICIT_STATES:
             raise ModelDefinitionError("%s has implicit = True and %d species; the matrix of a Newton step lives in registers: at "
                                        "most %d (MAX_IMPLICIT_STATES)" % (name, len(cls.species), MAX_IMPLICIT_STATES))
+    m = cls.substeps
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or not 1 <= m <= MAX_SUBSTEPS:
+        raise ModelDefinitionError("%s.substeps = %r; a fixed-grid solver takes a whole number of steps over each observation "
+                                   "interval, 1 .. %d (MAX_SUBSTEPS)" % (name, m, MAX_SUBSTEPS))
+    if (m - 1) * len(cls.species) > MAX_SUBSTEP_ROWS:
+        raise ModelDefinitionError("%s has substeps = %d and %d species: the adjoint keeps (substeps - 1) * species rows of an "
+                                   "interval's intermediate states in LDS, at most %d (MAX_SUBSTEP_ROWS)"
+                                   % (name, m, len(cls.species), MAX_SUBSTEP_ROWS))
+    if m > 1 and nets:
+        raise ModelDefinitionError("%s has substeps = %d and networks: the adjoint's dump of a network holds one evaluation per "
+                                   "stage and observation interval (substeps > 1 is for models without networks)" % (name, m))
     if nets is None:
         return
     if not isinstance(nets, dict) or not all(isinstance(k, str) and k.isidentifier() and isinstance(v, Network)

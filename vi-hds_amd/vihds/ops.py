@@ -91,6 +91,11 @@ class OdeProblemSpec:
         if solver in hip.IMPLICIT_SOLVERS and model not in hip.GENERATED_IMPLICIT:  # (before anything is asked of the library)
             raise NotImplementedError("solver '%s' needs a generated model with implicit = True (model '%s' has no Jacobian)"
                                       % (solver, model))
+        if solver in hip.ADAPTIVE_SOLVERS and hip.GENERATED_SUBSTEPS.get(model, 1) > 1:  # (likewise)
+            raise NotImplementedError(
+                "model '%s' has substeps = %d, which divide the observation intervals of a fixed-grid scheme: the adaptive solver "
+                "'%s' chooses its own steps and is not available to it (fixed-grid solvers: %s)" % (
+                    model, hip.GENERATED_SUBSTEPS[model], solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         self.model, self.solver = model, solver
         sized = False
         if model == "dr_blackbox":
