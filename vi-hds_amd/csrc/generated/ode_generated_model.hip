@@ -30,6 +30,8 @@ static_assert(!(substeps<VIHDS_GEN_CORE>::value > 1 && (VIHDS_GEN_NEURAL != 0 ||
               "a model with sub-steps takes no networks and no NeuralPrecisions: the adjoint's dump holds (T-1) x stages evaluations");
 static_assert(substeps<VIHDS_GEN_CORE>::value >= 1 && substeps<VIHDS_GEN_CORE>::value <= kMaxSubsteps,
               "substeps: 1 .. 8 (vihds_substeps.hpp)");
+static_assert(!(VIHDS_GEN_NEURAL != 0 && has_jump<VIHDS_GEN_CORE>::value),
+              "a model with a state jump does not take NeuralPrecisions: WithPrec<> does not forward jump / jump_vjp");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
@@ -78,7 +80,8 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
   static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, traj_rows<GenM>::value, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
                                    slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
                                    net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
-                                   n_forcings<GenM>::value, has_jacobian<GenM>::value ? 1 : 0, substeps<GenM>::value};
+                                   n_forcings<GenM>::value, has_jacobian<GenM>::value ? 1 : 0, substeps<GenM>::value,
+                                   has_jump<GenM>::value ? 1 : 0};
   return &r;
 }
 #endif

@@ -117,6 +117,8 @@ struct ModelEntry {
   bool implicit = false;
   // a registered model's sub-steps per observation interval (GenModelRecord::substeps); above 1 it takes no adaptive solver
   int substeps = 1;
+  // a registered model with a state jump at the observation points (GenModelRecord::jump): it takes no adaptive solver
+  bool jump = false;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
   bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
   int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
@@ -171,7 +173,7 @@ static ModelEntry g_gen_entries[VIHDS_GEN_MODEL_MAX];
 static std::atomic<int> g_gen_count{0};
 static ModelEntry gen_entry_of(const GenModelRecord* r) {
   return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
-          r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps};
+          r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps, r->jump != 0};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -260,6 +262,9 @@ static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& 
   if (e->substeps > 1 && solver_is_adaptive(p->solver))
     return fail(VIHDS_E_UNSUPPORTED, "the model has substeps > 1, which divide the observation intervals of a fixed-grid scheme: "
                                      "an adaptive solver chooses its own steps and is not available to it");
+  if (e->jump && solver_is_adaptive(p->solver))
+    return fail(VIHDS_E_UNSUPPORTED, "the model has a state jump at the observation points, applied between two steps of a fixed-grid "
+                                     "scheme: an adaptive solver integrates on a grid of its own and is not available to it");
   if (p->C < e->n_cond) return fail(VIHDS_E_BADARG, "the model reads more treatments per row than C provides");
   if (e->n_forcings > 0 && (long long)p->C < (long long)e->n_cond + (long long)e->n_forcings * p->T)
     return fail(VIHDS_E_BADARG, "the model reads n_forcings series of T samples per row behind its treatments: C is too small");
@@ -372,7 +377,8 @@ int vihds_model_register(const char* library_path) {
       !r->n_weights || (r->observe_kind != OBS_DEFAULT && r->observe_kind != OBS_DIRECT && r->observe_kind != OBS_CUSTOM) || r->n_net_weights < 0 ||
       r->net_fields < 0 || (r->n_net_weights > 0) != (r->net_fields > 0) || r->n_forcings < 0 ||
       (r->implicit && (r->neural_prec || r->n_net_weights > 0)) || r->substeps < 1 || r->substeps > kMaxSubsteps ||
-      (r->substeps > 1 && (r->neural_prec || r->n_net_weights > 0))) {
+      (r->substeps > 1 && (r->neural_prec || r->n_net_weights > 0)) || (r->jump != 0 && r->jump != 1) ||
+      (r->jump && r->neural_prec)) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
   }

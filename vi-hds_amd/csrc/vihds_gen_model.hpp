@@ -51,6 +51,9 @@ struct GenModelRecord {
   // steps a fixed-grid scheme takes over each observation interval (vihds_models.hpp substeps<>, >= 1); above 1 the model
   // takes the fixed-grid solvers only and the library holds no kernel of an adaptive pair
   int substeps;
+  // 1: the generated struct has a state jump at the observation points (jump / jump_vjp, vihds_models.hpp has_jump<>); the
+  // model then takes the fixed-grid solvers only and the library holds no kernel of an adaptive pair
+  int jump;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

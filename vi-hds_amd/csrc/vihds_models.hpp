@@ -995,6 +995,19 @@ struct substeps<M, std::void_t<decltype(M::SUBSTEPS)>> {
   static constexpr int value = M::SUBSTEPS;
 };
 
+// A core generated with a state jump (vihds/modelgen.py: jump(self, y, p, c)) declares OWN_JUMP = true and two members that run
+// once per time point but the last, after the point's state is stored, observed and scored:
+//   jump(y, p, yj)                       yj[N] = the state right after the time point (y is the left limit; never in place)
+//   jump_vjp(y, p, yjb, yb, pb)          yb += (d yj/d y)^T yjb ; pb += (d yj/d p)^T yjb   (forward values recomputed)
+// The step over [t_k, t_k+1] starts from yj; the stored trajectory holds the left limits.  p holds the forcing samples of the
+// point (set_point in the forward, the value entries of set_interval(k, k+1) in the adjoint: the same numbers).  Such a model
+// takes the fixed-grid solvers only.  False for every hand-written model and for WithPrec<> (which declares no OWN_JUMP and
+// does not forward its core's members).
+template <class M, class = void>
+struct has_jump : std::false_type {};
+template <class M>
+struct has_jump<M, std::void_t<decltype(M::OWN_JUMP)>> : std::bool_constant<M::OWN_JUMP> {};
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};

@@ -618,6 +618,16 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
         obc[j] = obn[j];
       }
     }
+    if constexpr (has_jump<M>::value) {
+      // a state jump of the model's own (a branch of its own: every other model's code stays what it was): what was stored,
+      // observed and scored above is the left limit y_k; the step of the next iteration starts from jump(y_k), evaluated
+      // while p still holds the point's forcing samples (set_point).  A jump at the last point has no effect: not evaluated
+      if (k + 1 < a.T) {
+        float yj[N];
+        M::jump(y, p, yj);
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) y[j] = yj[j];
+      }
+    }
   }
   if (a.logp) {
     VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.logp[(size_t)j * n + i] = lp[j];
@@ -845,7 +855,32 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     if constexpr (NF > 0) {  // the interval (k, k + 1) ...
       if (k < a.T - 1) M::set_interval(p, tK, 1.f / (tHi - tK), ff.lo, ff.hi);
     }
-    if constexpr (substeps<M>::value > 1) {  // (the interval's sub-states are recomputed from y = y_k: ode_substeps_vjp)
+    if constexpr (has_jump<M>::value) {
+      // a state jump of the model's own (a branch of its own: every other model's code stays what it was).  The stored y is the
+      // left limit y_k and the interval started from yj = jump(y_k): recomputed here by the forward's call on the forward's
+      // operands (the value entries of p are u_k after set_interval), so the same bits.  The step adjoint runs from yj -- an
+      // implicit step's at the stored y_k+1, which needs no start state --, then jump_vjp takes lam (the adjoint of yj) to the
+      // adjoint of y_k and adds its parameter part to pb, ahead of the hook adjoints of the point, which add into that lam
+      if (k < a.T - 1) {
+        float yj[N], lamk[N];
+        if constexpr (substeps<M>::value > 1) {
+          M::jump(y, p, yj);
+          if constexpr (solver_is_implicit(SOLVER)) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, yj, ff.y_next, p, wts, lam, pb, wtsb);
+          else ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, yj, nullptr, p, wts, lam, pb, wtsb);
+        } else if constexpr (solver_is_implicit(SOLVER)) {
+          ode_step_vjp_implicit<M>(tK, tHi, ff.y_next, p, wts, lam, pb, wtsb);
+        } else {
+          M::jump(y, p, yj);
+          ode_step_vjp<M, SOLVER>(tK, tHi, h0, yj, p, wts, lam, pb, wtsb);
+        }
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) lamk[j] = 0.f;
+        M::jump_vjp(y, p, lam, lamk, pb);
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] = lamk[j];
+      }
+      if constexpr (solver_is_implicit(SOLVER)) {  // (the interval below ends on the stored left limit y_k)
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
+      }
+    } else if constexpr (substeps<M>::value > 1) {  // (the interval's sub-states are recomputed from y = y_k: ode_substeps_vjp)
       if constexpr (solver_is_implicit(SOLVER)) {
         if (k < a.T - 1) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, y, ff.y_next, p, wts, lam, pb, wtsb);
         VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
@@ -1065,11 +1100,12 @@ inline int launch_ode_implicit(bool backward, int solver, const OdeArgs& a, hipS
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
-  if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1) {
+  if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
     // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it.  A model with sub-steps
-    // likewise: they divide the intervals of a fixed-grid scheme, an adaptive pair chooses its own steps
+    // likewise: they divide the intervals of a fixed-grid scheme, an adaptive pair chooses its own steps.  A model with a state
+    // jump likewise: the jump is applied between two intervals of the observation grid, which only these time loops walk
     if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
 #define VIHDS_CASE(SV)                                           \
   case SV:                                                       \

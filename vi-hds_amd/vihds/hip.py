@@ -39,6 +39,9 @@ GENERATED_IMPLICIT = set()
 # registered generated models: key -> `substeps`, the steps a fixed-grid solver takes over each observation interval.  Above 1
 # the model declines the adaptive solvers (they choose their own steps)
 GENERATED_SUBSTEPS = {}
+# keys of registered generated models with a state jump at the observation points (`jump(self, y, p, c)`): they decline the
+# adaptive solvers (the jump is applied between two steps of a fixed-grid scheme)
+GENERATED_JUMP = set()
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8, "beuler": 9}

@@ -171,6 +171,29 @@ adjoints last to first.  Such a model takes the fixed-grid solvers only: an adap
 declined (solve raises before anything is queued, the library answers VIHDS_E_UNSUPPORTED).  Refused in this version: together
 with networks and with NeuralPrecisions (the adjoint's dump holds one evaluation per stage and observation interval).
 
+State jumps.  A discontinuity of the state at an observation point -- a culture diluted at a read, a bolus pipetted into a
+well, a turbidostat that dilutes above a threshold, a dose -- is neither a term of rhs nor a forcing (both change the
+derivative, not the state).  A class may define
+
+        def jump(self, y, p, c):                     # -> list of len(species): the state right after the time point
+            keep = self.forcing.keep                 # per well, per time point; 1.0 where nothing happens
+            return [y[0] * keep, y[1] * keep + p.bolus * self.forcing.dose, ...]
+
+With Phi the chosen fixed-grid scheme over one observation interval (sub-steps included): y_0 is the initial state; for k = 0 ..
+T-1 the state y_k is stored, observed and scored (traj, x_predict and logp hold the LEFT limit at t_k), and for k < T-1 the next
+interval starts from the jump, y_k+1 = Phi(t_k, t_k+1, jump(y_k; p, c, u_k)), u_k the forcing samples of the point as the other
+hooks read them.  A jump at the last point has no effect and is not evaluated.  The hook has no t: an event schedule travels as
+a forcing (which may differ from well to well), a state-triggered event is a where on y -- its condition carries no adjoint, as
+for every where: there is no gradient with respect to an event time or a trigger threshold.  Like log_likelihood it takes
+exactly its arguments, `jump = None` in a subclass removes it, and a treatment it reads becomes one more effective parameter.
+The struct gains OWN_JUMP, jump(y, p, yj) and jump_vjp(y, p, yjb, yb, pb) (reverse mode, forward values recomputed, it adds);
+the forward kernel calls jump last in a time point's iteration, the adjoint recomputes it from the stored left limit, runs the
+step adjoint from there and chains jump_vjp into the trajectory adjoint ahead of the point's hook adjoints.  modeuler's fixed
+h0 and the sub-step grid are untouched.  Networks in rhs, forcings, implicit, substeps and the other hooks all combine with it.
+Such a model takes the fixed-grid solvers only (an adaptive solver is declined: solve raises before anything is queued, the
+library answers VIHDS_E_UNSUPPORTED) and no NeuralPrecisions (generate_source(cls, neural=True) raises).  A class without the hook
+generates byte for byte the text it generated before.  torch_jump restates the hook with torch ops.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -944,7 +967,7 @@ _GROUP_ADJOINT = {"y": "yb", "x": "xpb", "pr": "prb", "p": "pb"}  # leaf kind ->
 
 class Hook(object):
     """One optional function of a model that the kernels call once per time point, inside the time loop; it returns four
-    values, is traced into the model's DAG (the operations of rhs: no t, no network calls) and is emitted with its
+    values (n_outputs says otherwise), is traced into the model's DAG (the operations of rhs: no t, no network calls) and is emitted with its
     reverse-mode adjoint as two members of the struct.  TO ADD A HOOK, ADD ONE RECORD to HOOKS (in the order in which the
     forward kernel calls them) and its call site in the kernels; tracing, code generation, the capture of the definition
     when a class is defined and the torch restatement walk this table.
@@ -954,6 +977,7 @@ class Hook(object):
                          adds into the adjoint array of each group that has one (_GROUP_ADJOINT), in this order, and last
                          into pb of the named effective parameters (a treatment has no adjoint)
       outputs            what the four returned values are, in error messages
+      n_outputs          how many values it returns: 4, or "species" (one per species: the state jump)
       attr, traced       the class attribute that holds the definition; the Trace attribute that holds its four nodes
       c_out, seed        the C arrays of the values and of their adjoints
       c_forward, c_adjoint   the members' signatures
@@ -971,6 +995,7 @@ class Hook(object):
 
     switch_note = excludes_neural = settle = None
     note = ""
+    n_outputs = 4
     hides_method = none_resets = checks_arguments = False
 
     def __init__(self, name, **fields):
@@ -980,6 +1005,10 @@ class Hook(object):
     @property
     def targets(self):
         return [(k, _GROUP_ADJOINT[k]) for k in self.groups + ("p",) if k in _GROUP_ADJOINT]
+
+    def count(self, n_species):
+        """The number of values the hook returns for a model of n_species species."""
+        return n_species if self.n_outputs == "species" else self.n_outputs
 
 
 HOOKS = (
@@ -1009,13 +1038,24 @@ HOOKS = (
          excludes_neural="likelihood", none_resets=True, checks_arguments=True,
          note=": it sees the predicted signals, the observations and the precisions of one time point, the effective parameters "
               "and the treatments -- no t and no species (or None in a subclass, for the Gaussian)"),
+    # the state jump: called last, after the point's state is stored, observed and scored; sees the species (the left limit),
+    # the effective parameters and the treatments -- no t: an event schedule travels as a forcing, a state-triggered event is a
+    # where on y.  It returns the state right after the time point, one value per species; the next interval starts there
+    Hook("jump", signature="jump(self, y, p, c)", groups=("y",), outputs="the state right after the time point, one value per species",
+         n_outputs="species", attr="_jump_def", traced="jmp", c_out="yj", seed="yjb",
+         switch="OWN_JUMP", switch_note="the state jumps at the observation points: jump / jump_vjp",
+         c_forward=["  __device__ static void jump(const float* y, const float* p, float* yj) {"],
+         c_adjoint=["  __device__ static void jump_vjp(const float* y, const float* p, const float* yjb, float* yb, float* pb) {"],
+         excludes_neural="state jump", none_resets=True, checks_arguments=True,
+         note=": it sees the species at one time point (the left limit), the effective parameters and the treatments -- no t "
+              "(or None in a subclass, for no jump)"),
 )
 HOOK = {h.name: h for h in HOOKS}
 
 
 class Trace(object):
-    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe, precision and log_likelihood)
-    traced into one Graph."""
+    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe, precision, log_likelihood and
+    jump) traced into one Graph."""
 
     def __init__(self, cls):
         inst = cls.__new__(cls)  # (the functions are methods; nothing of nn.Module is touched by them)
@@ -1027,7 +1067,7 @@ class Trace(object):
         def call(k, name, net, inputs):
             if self._phase != "rhs":
                 raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only (not in "
-                                           "prepare, initial_state, observe or precision, nor in log_likelihood)" % (name, self._phase))
+                                           "prepare, initial_state, observe or precision, nor in log_likelihood or jump)" % (name, self._phase))
             if name in self._called:
                 raise ModelDefinitionError("network '%s' is called twice: a network may be called at most once per rhs "
                                            "evaluation (its adjoint dump has one slot per evaluation)" % name)
@@ -1041,8 +1081,8 @@ class Trace(object):
             if self._phase in ("prepare", "initial_state"):
                 raise ModelDefinitionError(
                     "forcing '%s' read in %s: a forcing changes over the experiment, and %s is evaluated once, before the "
-                    "first time point -- forcings are read in rhs (the interpolant at the stage time), observe, precision and "
-                    "log_likelihood (the sample of the time point)" % (name, self._phase, self._phase))
+                    "first time point -- forcings are read in rhs (the interpolant at the stage time), observe, precision, "
+                    "log_likelihood and jump (the sample of the time point)" % (name, self._phase, self._phase))
             return g.leaf("f", k)
 
         object.__setattr__(inst, "forcing", _Forcings(cls, read))
@@ -1078,8 +1118,9 @@ class Trace(object):
                 self._phase = h.name
                 out = definition(inst, *[[g.leaf(k, j) for j in range(N if k == "y" else 4)] for k in h.groups], p,
                                  _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
-                if not isinstance(out, (list, tuple)) or len(out) != 4:
-                    raise ModelDefinitionError("%s.%s must return a list of 4 entries (%s)" % (cls.__name__, h.name, h.outputs))
+                if not isinstance(out, (list, tuple)) or len(out) != h.count(N):
+                    raise ModelDefinitionError("%s.%s must return a list of %d entries (%s)"
+                                               % (cls.__name__, h.name, h.count(N), h.outputs))
                 setattr(self, h.traced, [g._arg(x) for x in out])
         used = {n.val for n in _topo(self.dy + [x for h in HOOKS for x in getattr(self, h.traced) or []]) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
@@ -1350,7 +1391,7 @@ def generate_source(cls, neural=False):
         outs = getattr(tr, h.traced)
         if outs is None:
             continue
-        adj = vjp(g, outs, [g.leaf("seed", j) for j in range(4)])
+        adj = vjp(g, outs, [g.leaf("seed", j) for j in range(h.count(N))])
         if h.switch_note:
             hook_decl.append("  static constexpr bool %s = true;  // %s" % (h.switch, h.switch_note))
         hook_decl += h.c_forward + [body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in enumerate(outs)], True, h.seed, tr.c_slot,
@@ -1533,6 +1574,8 @@ def register_kernel(cls, neural=False):
     if cls.implicit:  # (the library holds the kernels of the implicit solvers)
         hip.GENERATED_IMPLICIT.add(key)
     hip.GENERATED_SUBSTEPS[key] = int(cls.substeps)  # (above 1: the library holds the fixed-grid schemes only)
+    if cls._trace.jmp is not None:  # (a state jump at the observation points: the fixed-grid schemes only, likewise)
+        hip.GENERATED_JUMP.add(key)
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -1548,7 +1591,7 @@ class GeneratedOdeModel(OdeModel):
     parameter_names = None
     n_conditions = 0
     observe_kind = "default"
-    _observe_def = _precision_def = _likelihood_def = None  # the definitions of the hooks the class has (HOOKS: attr)
+    _observe_def = _precision_def = _likelihood_def = _jump_def = None  # the definitions of the hooks the class has (HOOKS: attr)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
     implicit = False  # True: the Jacobian of rhs is generated and the implicit solvers take the model (module docstring)
@@ -1644,6 +1687,12 @@ class GeneratedOdeModel(OdeModel):
                 "chooses its own steps and is not available to it (fixed-grid solvers: %s)" % (
                     type(self).__name__, type(self).substeps, config.params.solver,
                     ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if type(self)._jump_def is not None and config.params.solver in hip.ADAPTIVE_SOLVERS:  # (likewise)
+            raise NotImplementedError(
+                "%s defines jump(self, y, p, c), a state jump applied between two steps of a fixed-grid scheme: the adaptive "
+                "solver '%s' integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
+                    type(self).__name__, config.params.solver,
+                    ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         K = len(_class_forcings(type(self)))
         if K:  # (checked before anything is built or queued)
             if config.params.solver in hip.ADAPTIVE_SOLVERS:
@@ -1668,6 +1717,11 @@ class GeneratedOdeModel(OdeModel):
     def precision_kind(self):
         """'custom' for a model with a precision map of its own (module docstring), else 'fixed'."""
         return "custom" if type(self)._precision_def is not None else "fixed"
+
+    @property
+    def has_jump(self):
+        """True for a model with a state jump at the observation points (module docstring)."""
+        return type(self)._jump_def is not None
 
     @property
     def likelihood_kind(self):
@@ -1866,6 +1920,18 @@ class GeneratedOdeModel(OdeModel):
         obs, prec = obs.to(x.dtype)[:, None].expand(x.shape), prec.to(x.dtype).expand(x.shape)
         return _hook_torch(cls, HOOK["log_likelihood"], cls.__new__(cls), [x, obs, prec], theta, cond)
 
+    @classmethod
+    def torch_jump(cls, y, theta, cond):
+        """The model's own state jump with torch ops in y's dtype (the float64 reference of the generated jump / jump_vjp, as
+        torch_observe is for the map): y [B,S,N,T] species at the time points (the left limits; rows stored behind them are
+        ignored), theta {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as the data holds it (the
+        wide rows of a class with forcings: the jump of point k reads sample k) -> the states right after the points [B,S,N,T].
+        The kernels do not evaluate the jump of the last point."""
+        if cls._jump_def is None:
+            raise ModelDefinitionError("%s defines no jump(self, y, p, c): its state is continuous at the observation points"
+                                       % cls.__name__)
+        return _hook_torch(cls, HOOK["jump"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond)
+
     def _log_likelihood_map(self, x_predict, observations, precisions):
         """The model's own log density on tensors of the host paths (the host-driven adaptive route, the plugin fallback of
         Training.cost), with theta and the treatments of the last solve, as _observe_map: x_predict [B,S,4,T], observations
@@ -1917,7 +1983,8 @@ def _forcing_series(cls, cond, like, n_times):
 
 def _hook_torch(cls, h, inst, groups, th, cond):
     """The class's definition of hook h with torch ops in the dtype of its first group: groups of [B,S,.,T] tensors (in
-    the hook's order), th {parameter name: [B,S]} -- prepare is applied to it -- and cond [B,C] -> [B,S,4,T]."""
+    the hook's order), th {parameter name: [B,S]} -- prepare is applied to it -- and cond [B,C] -> [B,S,4,T] (the hook's
+    n_outputs: [B,S,N,T] for the state jump)."""
     ref = groups[0][:, :, 0, :]
     cs = _treatments_torch(cls, cond, ref, ref.shape[1])
     thn = _Named([(n, th[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")

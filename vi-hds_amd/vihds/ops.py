@@ -96,6 +96,11 @@ class OdeProblemSpec:
                 "model '%s' has substeps = %d, which divide the observation intervals of a fixed-grid scheme: the adaptive solver "
                 "'%s' chooses its own steps and is not available to it (fixed-grid solvers: %s)" % (
                     model, hip.GENERATED_SUBSTEPS[model], solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if solver in hip.ADAPTIVE_SOLVERS and model in hip.GENERATED_JUMP:  # (likewise)
+            raise NotImplementedError(
+                "model '%s' has a state jump at the observation points, applied between two steps of a fixed-grid scheme: the "
+                "adaptive solver '%s' integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
+                    model, solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         self.model, self.solver = model, solver
         sized = False
         if model == "dr_blackbox":
