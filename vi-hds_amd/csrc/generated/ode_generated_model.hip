@@ -32,6 +32,12 @@ static_assert(substeps<VIHDS_GEN_CORE>::value >= 1 && substeps<VIHDS_GEN_CORE>::
               "substeps: 1 .. 8 (vihds_substeps.hpp)");
 static_assert(!(VIHDS_GEN_NEURAL != 0 && has_jump<VIHDS_GEN_CORE>::value),
               "a model with a state jump does not take NeuralPrecisions: WithPrec<> does not forward jump / jump_vjp");
+static_assert(!(VIHDS_GEN_NEURAL != 0 && (has_start<VIHDS_GEN_CORE>::value || lead_in<VIHDS_GEN_CORE>::value > 0)),
+              "a model with a start map or a lead-in phase does not take NeuralPrecisions: WithPrec<> does not forward them");
+static_assert(!(lead_in<VIHDS_GEN_CORE>::value > 0 && net_fields<VIHDS_GEN_CORE>::value > 0),
+              "a model with a lead-in phase takes no networks: the adjoint's dump holds (T-1) x stages evaluations");
+static_assert(lead_in<VIHDS_GEN_CORE>::value >= 0 && lead_in<VIHDS_GEN_CORE>::value <= kMaxLeadInSteps,
+              "lead_in_steps: 1 .. 8 (vihds_substeps.hpp)");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
@@ -81,7 +87,7 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
                                    slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
                                    net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
                                    n_forcings<GenM>::value, has_jacobian<GenM>::value ? 1 : 0, substeps<GenM>::value,
-                                   has_jump<GenM>::value ? 1 : 0};
+                                   has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value};
   return &r;
 }
 #endif

@@ -119,6 +119,10 @@ struct ModelEntry {
   int substeps = 1;
   // a registered model with a state jump at the observation points (GenModelRecord::jump): it takes no adaptive solver
   bool jump = false;
+  // a registered model with a start map (GenModelRecord::start) / the steps of its lead-in phase (GenModelRecord::lead_in_steps,
+  // 0: none): either takes no adaptive solver
+  bool start = false;
+  int lead_in_steps = 0;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
   bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
   int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
@@ -173,7 +177,8 @@ static ModelEntry g_gen_entries[VIHDS_GEN_MODEL_MAX];
 static std::atomic<int> g_gen_count{0};
 static ModelEntry gen_entry_of(const GenModelRecord* r) {
   return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
-          r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps, r->jump != 0};
+          r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps, r->jump != 0,
+          r->start != 0, r->lead_in_steps};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -265,6 +270,12 @@ static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& 
   if (e->jump && solver_is_adaptive(p->solver))
     return fail(VIHDS_E_UNSUPPORTED, "the model has a state jump at the observation points, applied between two steps of a fixed-grid "
                                      "scheme: an adaptive solver integrates on a grid of its own and is not available to it");
+  if (e->start && solver_is_adaptive(p->solver))
+    return fail(VIHDS_E_UNSUPPORTED, "the model has a start map (start), which the kernels of the fixed-grid schemes call before "
+                                     "the first step: an adaptive solver is not available to it");
+  if (e->lead_in_steps > 0 && solver_is_adaptive(p->solver))
+    return fail(VIHDS_E_UNSUPPORTED, "the model has a lead-in phase (lead_in), steps of a fixed-grid scheme before the first "
+                                     "observation point: an adaptive solver chooses its own steps and is not available to it");
   if (p->C < e->n_cond) return fail(VIHDS_E_BADARG, "the model reads more treatments per row than C provides");
   if (e->n_forcings > 0 && (long long)p->C < (long long)e->n_cond + (long long)e->n_forcings * p->T)
     return fail(VIHDS_E_BADARG, "the model reads n_forcings series of T samples per row behind its treatments: C is too small");
@@ -378,7 +389,9 @@ int vihds_model_register(const char* library_path) {
       r->net_fields < 0 || (r->n_net_weights > 0) != (r->net_fields > 0) || r->n_forcings < 0 ||
       (r->implicit && (r->neural_prec || r->n_net_weights > 0)) || r->substeps < 1 || r->substeps > kMaxSubsteps ||
       (r->substeps > 1 && (r->neural_prec || r->n_net_weights > 0)) || (r->jump != 0 && r->jump != 1) ||
-      (r->jump && r->neural_prec)) {
+      (r->jump && r->neural_prec) || (r->start != 0 && r->start != 1) || r->lead_in_steps < 0 ||
+      r->lead_in_steps > kMaxLeadInSteps || ((r->start || r->lead_in_steps) && r->neural_prec) ||
+      (r->lead_in_steps && r->n_net_weights > 0)) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
   }

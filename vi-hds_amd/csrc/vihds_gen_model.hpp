@@ -54,6 +54,12 @@ struct GenModelRecord {
   // 1: the generated struct has a state jump at the observation points (jump / jump_vjp, vihds_models.hpp has_jump<>); the
   // model then takes the fixed-grid solvers only and the library holds no kernel of an adaptive pair
   int jump;
+  // 1: the generated struct maps its initial state to the state the integration starts from (start / start_vjp,
+  // vihds_models.hpp has_start<>); the fixed-grid solvers only, likewise
+  int start;
+  // steps of the lead-in phase before the first observation point (vihds_models.hpp lead_in<>: 0 for none, else 1 ..
+  // kMaxLeadInSteps); above 0 the fixed-grid solvers only, likewise
+  int lead_in_steps;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

@@ -1008,6 +1008,29 @@ struct has_jump : std::false_type {};
 template <class M>
 struct has_jump<M, std::void_t<decltype(M::OWN_JUMP)>> : std::bool_constant<M::OWN_JUMP> {};
 
+// A core generated with a start map (vihds/modelgen.py: start(self, y, p, c)) declares OWN_START = true and two members that run
+// once per trajectory, after init (which stays affine in theta: init_vjp sees no theta):
+//   start(y, p, ys)                      ys[N] = the state the integration starts from (y is what init returned; never in place)
+//   start_vjp(y, p, ysb, yb, pb)         yb += (d ys/d y)^T ysb ; pb += (d ys/d p)^T ysb   (forward values recomputed)
+// p holds the first forcing samples (set_point(p, u_0)).  The adjoint kernel recomputes init, runs start_vjp ahead of prepare_vjp
+// and hands yb to init_vjp.  Such a model takes the fixed-grid solvers only.  False for every hand-written model and WithPrec<>.
+template <class M, class = void>
+struct has_start : std::false_type {};
+template <class M>
+struct has_start<M, std::void_t<decltype(M::OWN_START)>> : std::bool_constant<M::OWN_START> {};
+
+// A core generated with `lead_in = L > 0` (vihds/modelgen.py) declares LEAD_STEPS = n (1 .. kMaxLeadInSteps) and LEAD_TIME = L:
+// before the first observation point the fixed-grid scheme takes n steps on SubGrid<n>(t_0 - L, t_0) (vihds_substeps.hpp), of
+// which nothing is stored, observed or scored.  value is n, 0 for every other model.  The fixed-grid solvers only.
+template <class M, class = void>
+struct lead_in {
+  static constexpr int value = 0;
+};
+template <class M>
+struct lead_in<M, std::void_t<decltype(M::LEAD_STEPS), decltype(M::LEAD_TIME)>> {
+  static constexpr int value = M::LEAD_STEPS;
+};
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};

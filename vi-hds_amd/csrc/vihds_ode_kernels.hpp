@@ -356,6 +356,13 @@ struct SubstateLds {
     return rows + threadIdx.x;
   }
 };
+// the rows a model's adjoint asks for: the sub-states of an interval and those of the lead-in phase (lead_in<M>, below) are
+// never live at once, so they share one block of max(substeps - 1, lead-in steps - 1) * N rows
+template <class M>
+constexpr int substate_rows() {
+  constexpr int ms = substeps<M>::value - 1, nl = lead_in<M>::value - 1;
+  return (ms > nl ? ms : nl) * M::N;
+}
 
 // reverse of one observation interval of MS sub-steps.  y is the stored y_k = u_0; y_next the stored y_k+1 = u_MS (read by an
 // implicit scheme only).  The intermediate states are stored nowhere: MS - 1 forward sub-steps from u_0 recompute them --
@@ -365,7 +372,7 @@ template <class M, int SOLVER, class Ctx>
 __device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, const float* y, const float* y_next,
                                                  const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb) {
   constexpr int N = M::N, MS = substeps<M>::value;
-  float* col = SubstateLds<(MS - 1) * N>::column();
+  float* col = SubstateLds<substate_rows<M>()>::column();
   const SubGrid<MS> sg(t0, t1);
   const float hm = SubGrid<MS>::fixed_step(h0);
   float u[N];
@@ -394,6 +401,64 @@ __device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, c
         VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y[q];
       }
     }
+  }
+}
+
+// ---- the lead-in phase (lead_in<M> = NL > 0: LEAD_STEPS steps over LEAD_TIME before the first observation point) -------
+// Instantiated for a generated model with `lead_in` only (behind `if constexpr (lead_in<M>::value > 0)`).  The grid is
+// SubGrid<NL>(t_0 - L, t_0): s_j = fmaf(j, hl, tl), s_NL = t_0 exactly; modeuler's fixed step is hl there; sub-steps do not
+// divide these steps and no jump is applied.  The caller has put the first forcing samples in place with slope 0
+// (set_interval(p, tl, 0, u_0, u_0)).  Nothing is stored: y goes from y_start to y_0.
+template <class M, int SOLVER>
+__device__ __forceinline__ void ode_lead_in(float t_first, float* y, const float* p, const float* wts) {
+  constexpr int NL = lead_in<M>::value;
+  const SubGrid<NL> sg(t_first - M::LEAD_TIME, t_first);
+#pragma unroll 1
+  for (int j = 0; j < NL; ++j) ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), sg.hs, y, p, wts);
+}
+
+// reverse of the lead-in phase: lam (the adjoint of y_0 = u_NL) -> the adjoint of y_start = u_0; pb += the parameter part.
+// u_1 .. u_NL-1 are recomputed from y_start with exactly the forward's calls into LDS (the rows of SubstateLds, which no
+// interval's sub-states occupy any more), then the step adjoints run last to first; an implicit step's at u_j+1, with
+// u_NL = y_first, the stored y_0 (read by an implicit scheme only).  NL = 1 keeps nothing and declares no LDS.
+template <class M, int SOLVER, class Ctx>
+__device__ __forceinline__ void ode_lead_in_vjp(float t_first, const float* y_start, const float* y_first, const float* p,
+                                                const float* wts, float* lam, float* pb, Ctx& wtsb) {
+  constexpr int N = M::N, NL = lead_in<M>::value;
+  const SubGrid<NL> sg(t_first - M::LEAD_TIME, t_first);
+  float u[N];
+  VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y_start[q];
+  if constexpr (NL > 1) {
+    float* col = SubstateLds<substate_rows<M>()>::column();
+#pragma unroll 1
+    for (int j = 0; j < NL - 1; ++j) {  // u_j -> u_j+1, kept as row block j
+      ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), sg.hs, u, p, wts);
+      VIHDS_UNROLL for (int q = 0; q < N; ++q) col[(j * N + q) * 256] = u[q];
+    }
+    if constexpr (solver_is_implicit(SOLVER)) {
+      VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y_first[q];  // u_NL
+#pragma unroll 1
+      for (int j = NL - 1; j >= 0; --j) {
+        ode_step_vjp_implicit<M>(sg.at(j), sg.at(j + 1), u, p, wts, lam, pb, wtsb);
+        if (j > 0) {  // u_j for the step below
+          VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 1) * N + q) * 256];
+        }
+      }
+    } else {  // (u holds u_NL-1)
+#pragma unroll 1
+      for (int j = NL - 1; j >= 0; --j) {
+        ode_step_vjp<M, SOLVER>(sg.at(j), sg.at(j + 1), sg.hs, u, p, wts, lam, pb, wtsb);
+        if (j > 1) {  // u_j-1 for the step below
+          VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 2) * N + q) * 256];
+        } else {
+          VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y_start[q];
+        }
+      }
+    }
+  } else if constexpr (solver_is_implicit(SOLVER)) {
+    ode_step_vjp_implicit<M>(sg.at(0), sg.at(1), y_first, p, wts, lam, pb, wtsb);
+  } else {
+    ode_step_vjp<M, SOLVER>(sg.at(0), sg.at(1), sg.hs, u, p, wts, lam, pb, wtsb);
   }
 }
 
@@ -521,6 +586,22 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     VIHDS_UNROLL for (int j = 0; j < NF; ++j) {
       ff.lo[j] = LDS_IN ? in_lds[ff.lds + j * a.T] : ff.src[j * a.T];
       ff.hi[j] = LDS_IN ? in_lds[ff.lds + j * a.T + 1] : ff.src[j * a.T + 1];
+    }
+  }
+  if constexpr (has_start<M>::value || lead_in<M>::value > 0) {
+    // where the trajectory starts, for a generated model that says so (a branch of its own: every other model's code stays what
+    // it was).  start maps what init returned, with the first forcing samples in p (set_point); the lead-in phase then takes
+    // the scheme from t_0 - L to t_0 with those samples held (slope 0) and rhs seeing the true t < t_0.  Nothing of it is
+    // stored, observed or scored: the time loop below begins at y_0
+    if constexpr (NF > 0) M::set_point(p, ff.lo);
+    if constexpr (has_start<M>::value) {
+      float ys[N];
+      M::start(y, p, ys);
+      VIHDS_UNROLL for (int j = 0; j < N; ++j) y[j] = ys[j];
+    }
+    if constexpr (lead_in<M>::value > 0) {
+      if constexpr (NF > 0) M::set_interval(p, tA - M::LEAD_TIME, 0.f, ff.lo, ff.lo);
+      ode_lead_in<M, SOLVER>(tA, y, p, wts);
     }
   }
   for (int k = 0; k < a.T; ++k) {
@@ -967,6 +1048,33 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
       VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] += a.g_traj[((size_t)k * NT + j) * n + i];
     }
   }
+  if constexpr (has_start<M>::value || lead_in<M>::value > 0) {
+    // where the trajectory started (a branch of its own: every other model's code stays what it was).  lam is the adjoint of
+    // y_0 and tHi is t_0; ff.lo holds the first forcing samples.  init and start are recomputed by the forward's calls on the
+    // forward's operands; the lead-in's step adjoints run last to first (an implicit scheme's last one at the stored y_0,
+    // which ff.y_next holds), then start_vjp takes lam to the adjoint of what init returned and adds its parameter part to pb
+    // ahead of prepare_vjp; init_vjp below is handed that state adjoint
+    float yi[N];
+    M::init(th, c, yi);
+    if constexpr (NF > 0) M::set_point(p, ff.lo);
+    if constexpr (lead_in<M>::value > 0) {
+      float ys[N];
+      if constexpr (has_start<M>::value) {
+        M::start(yi, p, ys);
+      } else {
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) ys[j] = yi[j];
+      }
+      if constexpr (NF > 0) M::set_interval(p, tHi - M::LEAD_TIME, 0.f, ff.lo, ff.lo);  // (the value entries stay u_0)
+      if constexpr (solver_is_implicit(SOLVER)) ode_lead_in_vjp<M, SOLVER>(tHi, ys, ff.y_next, p, wts, lam, pb, wtsb);
+      else ode_lead_in_vjp<M, SOLVER>(tHi, ys, nullptr, p, wts, lam, pb, wtsb);
+    }
+    if constexpr (has_start<M>::value) {
+      float lami[N];
+      VIHDS_UNROLL for (int j = 0; j < N; ++j) lami[j] = 0.f;
+      M::start_vjp(yi, p, lam, lami, pb);
+      VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] = lami[j];
+    }
+  }
   float thb[M::NSLOT];
   VIHDS_UNROLL for (int q = 0; q < M::NSLOT; ++q) thb[q] = 0.f;
   if constexpr (is_blackbox<M>::value) {
@@ -1100,12 +1208,14 @@ inline int launch_ode_implicit(bool backward, int solver, const OdeArgs& a, hipS
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
-  if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value) {
+  if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value || has_start<M>::value ||
+                lead_in<M>::value > 0) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
     // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it.  A model with sub-steps
     // likewise: they divide the intervals of a fixed-grid scheme, an adaptive pair chooses its own steps.  A model with a state
-    // jump likewise: the jump is applied between two intervals of the observation grid, which only these time loops walk
+    // jump likewise: the jump is applied between two intervals of the observation grid, which only these time loops walk.  A
+    // model with a start map or a lead-in phase likewise: only these kernels call start and run the steps before t_0
     if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
 #define VIHDS_CASE(SV)                                           \
   case SV:                                                       \

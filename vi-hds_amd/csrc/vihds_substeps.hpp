@@ -22,6 +22,9 @@ namespace vihds {
 
 // the sub-steps a generated model may ask for (vihds.modelgen.MAX_SUBSTEPS)
 constexpr int kMaxSubsteps = 8;
+// the steps of a lead-in phase before the first observation point (vihds.modelgen.MAX_LEAD_IN_STEPS): SubGrid<n>(t_0 - L, t_0)
+constexpr int kMaxLeadInSteps = 8;
+static_assert(kMaxLeadInSteps <= kMaxSubsteps, "the lead-in grid is a SubGrid");
 
 template <int MS>
 struct SubGrid {

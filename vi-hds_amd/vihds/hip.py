@@ -42,6 +42,11 @@ GENERATED_SUBSTEPS = {}
 # keys of registered generated models with a state jump at the observation points (`jump(self, y, p, c)`): they decline the
 # adaptive solvers (the jump is applied between two steps of a fixed-grid scheme)
 GENERATED_JUMP = set()
+# keys of registered generated models with a start map (`start(self, y, p, c)`), and key -> (lead_in, lead_in_steps) of those
+# with a lead-in phase before the first observation point: both decline the adaptive solvers (only the kernels of the
+# fixed-grid schemes call start and run the steps before t_0)
+GENERATED_START = set()
+GENERATED_LEAD_IN = {}
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8, "beuler": 9}

@@ -194,6 +194,30 @@ Such a model takes the fixed-grid solvers only (an adaptive solver is declined: 
 library answers VIHDS_E_UNSUPPORTED) and no NeuralPrecisions (generate_source(cls, neural=True) raises).  A class without the hook
 generates byte for byte the text it generated before.  torch_jump restates the hook with torch ops.
 
+Where the trajectory starts.  initial_state stays affine in theta (init_vjp sees no theta) and the time loop begins at the first
+read.  Two optional attributes lift both limits:
+
+        def start(self, y, p, c):                    # -> list of len(species): the state the integration starts from
+            rfp0 = p.rc / (p.drfp + p.r)             # y is what initial_state returned; p, c as in jump; self.forcing.<name>
+            return [y[0], where(c[0] > 0.5, rfp0, y[1]), ...]              # reads the first sample u_0
+        lead_in = 6.0                                # L > 0, in the units of `times`: an unscored phase before t_0
+        lead_in_steps = 4                            # n, 1 .. MAX_LEAD_IN_STEPS = 8, an int; default 1
+
+y_start = start(initial_state(th, c); p, c, u_0); with no lead-in y_0 = y_start.  start has the rules of jump (all operations of
+the model language, no t, no network call, exactly its arguments, `start = None` in a subclass removes it, a treatment it reads
+becomes one more effective parameter, a parameter may be read by it alone).  With a lead-in, tl = t_0 - L (formed in float32),
+hl = (t_0 - tl) * (1.f / n), s_j = fmaf(j, hl, tl) for j < n and s_n = t_0 exactly (lead_in_times returns them); u_0 = y_start,
+u_j+1 = Phi(s_j, s_j+1, u_j) with Phi one step of the chosen fixed-grid scheme, y_0 = u_n.  Nothing of the lead-in is stored,
+observed or scored: traj[0], x_predict[0] and logp begin at y_0.  rhs sees the true t < t_0 there -- where(t < 0.0, 0.0, c[0]) is
+an inducer absent before the first read --, a forcing holds its first sample, modeuler's fixed step is hl, beuler starts each
+step's Newton iteration from u_j, substeps do not divide these steps and jump is not applied.  The struct gains OWN_START, start
+and start_vjp, LEAD_STEPS and LEAD_TIME; the adjoint kernel, after its time loop, recomputes init, start and the lead-in's
+intermediate states (into the LDS rows of the sub-steps: (n - 1) * species at most MAX_SUBSTEP_ROWS), runs the n step adjoints
+last to first, then start_vjp ahead of prepare_vjp, and hands the state part to the unchanged init_vjp.  Fixed-grid solvers only
+(an adaptive solver is declined: solve raises before anything is queued, the library answers VIHDS_E_UNSUPPORTED), no
+NeuralPrecisions; a lead-in takes no networks (the dump is sized (T-1) x stages), start combines with networks in rhs.  A class
+with neither generates byte for byte the text it generated before.  torch_start restates the hook with torch ops.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -240,6 +264,9 @@ MAX_NEWTON_ITERATIONS = 8
 # (tests/test_modelgen_substeps_host.py compiles that worst case without scratch)
 MAX_SUBSTEPS = 8
 MAX_SUBSTEP_ROWS = 56  # (substeps - 1) * species: a block's static LDS ends at 64 KB
+# steps of the lead-in phase before the first observation point (`lead_in_steps`).  The adjoint keeps its intermediate states in
+# the LDS rows the sub-steps use (never both at once): (lead_in_steps - 1) * species rows, at most MAX_SUBSTEP_ROWS
+MAX_LEAD_IN_STEPS = 8
 
 
 class ModelDefinitionError(TypeError):
@@ -1011,6 +1038,20 @@ class Hook(object):
         return n_species if self.n_outputs == "species" else self.n_outputs
 
 
+# the start map: called once per trajectory, after init and before the first step -- not inside the time loop, so it is a record
+# of its own beside HOOKS (ALL_HOOKS, below, is what tracing, code generation and the capture of the definitions walk); sees what
+# initial_state returned, the effective parameters and the treatments -- no t; a forcing reads its first sample.  It returns the
+# state the integration starts from, one value per species
+START_HOOK = \
+    Hook("start", signature="start(self, y, p, c)", groups=("y",), outputs="the state the integration starts from, one value per species",
+         n_outputs="species", attr="_start_def", traced="start", c_out="ys", seed="ysb",
+         switch="OWN_START", switch_note="the integration starts from start(init): start / start_vjp",
+         c_forward=["  __device__ static void start(const float* y, const float* p, float* ys) {"],
+         c_adjoint=["  __device__ static void start_vjp(const float* y, const float* p, const float* ysb, float* yb, float* pb) {"],
+         excludes_neural="start map", none_resets=True, checks_arguments=True,
+         note=": it sees what initial_state returned, the effective parameters and the treatments -- no t "
+              "(or None in a subclass, for no start map)")
+
 HOOKS = (
     # the observation map: sees the species, the effective parameters and the treatments, like rhs without t
     Hook("observe", signature="observe(self, y, p, c)", groups=("y",), outputs="the OD, RFP, YFP and CFP signals",
@@ -1050,12 +1091,13 @@ HOOKS = (
          note=": it sees the species at one time point (the left limit), the effective parameters and the treatments -- no t "
               "(or None in a subclass, for no jump)"),
 )
-HOOK = {h.name: h for h in HOOKS}
+ALL_HOOKS = (START_HOOK,) + HOOKS  # in the order in which the forward kernel calls them
+HOOK = {h.name: h for h in ALL_HOOKS}
 
 
 class Trace(object):
-    """The functions of a model class (prepare, initial_state, rhs and, when defined, observe, precision, log_likelihood and
-    jump) traced into one Graph."""
+    """The functions of a model class (prepare, initial_state, rhs and, when defined, start, observe, precision, log_likelihood
+    and jump) traced into one Graph."""
 
     def __init__(self, cls):
         inst = cls.__new__(cls)  # (the functions are methods; nothing of nn.Module is touched by them)
@@ -1067,7 +1109,7 @@ class Trace(object):
         def call(k, name, net, inputs):
             if self._phase != "rhs":
                 raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only (not in "
-                                           "prepare, initial_state, observe or precision, nor in log_likelihood or jump)" % (name, self._phase))
+                                           "prepare, initial_state, observe or precision, nor in log_likelihood, jump or start)" % (name, self._phase))
             if name in self._called:
                 raise ModelDefinitionError("network '%s' is called twice: a network may be called at most once per rhs "
                                            "evaluation (its adjoint dump has one slot per evaluation)" % name)
@@ -1082,7 +1124,8 @@ class Trace(object):
                 raise ModelDefinitionError(
                     "forcing '%s' read in %s: a forcing changes over the experiment, and %s is evaluated once, before the "
                     "first time point -- forcings are read in rhs (the interpolant at the stage time), observe, precision, "
-                    "log_likelihood and jump (the sample of the time point)" % (name, self._phase, self._phase))
+                    "log_likelihood and jump (the sample of the time point) and in start (the first sample)"
+                    % (name, self._phase, self._phase))
             return g.leaf("f", k)
 
         object.__setattr__(inst, "forcing", _Forcings(cls, read))
@@ -1111,7 +1154,7 @@ class Trace(object):
                     cls.__name__, name, "no derivative depends on its outputs" if name in self._called
                     else "never called in rhs"))
         # the hooks (optional) see their groups of leaves, the effective parameters and the treatments
-        for h in HOOKS:
+        for h in ALL_HOOKS:
             setattr(self, h.traced, None)
             definition = getattr(cls, h.attr, None)
             if definition is not None:
@@ -1122,7 +1165,7 @@ class Trace(object):
                     raise ModelDefinitionError("%s.%s must return a list of %d entries (%s)"
                                                % (cls.__name__, h.name, h.count(N), h.outputs))
                 setattr(self, h.traced, [g._arg(x) for x in out])
-        used = {n.val for n in _topo(self.dy + [x for h in HOOKS for x in getattr(self, h.traced) or []]) if n.op == "p"}
+        used = {n.val for n in _topo(self.dy + [x for h in ALL_HOOKS for x in getattr(self, h.traced) or []]) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
@@ -1293,7 +1336,7 @@ def generate_source(cls, neural=False):
     recomputed inside them) and the switches csrc/generated/ode_generated_model.hip reads.  Deterministic: the same
     definition gives byte-identical text; its hash (with the kernel headers') names the library."""
     tr = cls._trace
-    for h in HOOKS:
+    for h in ALL_HOOKS:
         if neural and h.excludes_neural and getattr(tr, h.traced) is not None:
             raise ModelDefinitionError("%s defines %s: a model with a %s of its own does not take NeuralPrecisions"
                                        % (cls.__name__, h.signature, h.excludes_neural))
@@ -1304,6 +1347,11 @@ def generate_source(cls, neural=False):
         raise ModelDefinitionError("%s has substeps = %d: the adjoint's dump of the precision network holds one evaluation per "
                                    "stage and observation interval, so a sub-stepped model takes constant precisions or a "
                                    "precision map of its own" % (cls.__name__, cls.substeps))
+    if neural and cls.lead_in > 0:
+        raise ModelDefinitionError("%s has lead_in = %r: the adjoint's dump of the precision network holds one evaluation per "
+                                   "stage and observation interval, so a model with a lead-in phase does not take "
+                                   "NeuralPrecisions (constant precisions, or a precision map of its own)"
+                                   % (cls.__name__, cls.lead_in))
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -1338,7 +1386,9 @@ def generate_source(cls, neural=False):
                 "%s.initial_state: the derivative with respect to '%s' depends on theta or the treatments; the kernels' "
                 "init_vjp sees the state adjoint only, so the initial state must be affine in the parameters with constant "
                 "coefficients (move nonlinear maps into prepare... or into a parameter of its own; where, minimum, maximum, "
-                "abs and sqrt of a parameter or a treatment are such maps: a condition on theta is refused here too)"
+                "abs and sqrt of a parameter or a treatment are such maps: a condition on theta is refused here too); a "
+                "nonlinear start -- a steady state, a ratio of rates, a where on a treatment -- goes into start(self, y, p, c), "
+                "which maps what initial_state returns and reads the effective parameters"
                 % (cls.__name__, P[s]))
         init_vjp.append(("thb[%d]" % s, "+=", e))
     # rhs / rhs_vjp
@@ -1387,7 +1437,7 @@ def generate_source(cls, neural=False):
         net_decl = []
     # the hooks a model defines: value and adjoint run once per time point inside the time loop
     hook_decl = []
-    for h in HOOKS:
+    for h in ALL_HOOKS:
         outs = getattr(tr, h.traced)
         if outs is None:
             continue
@@ -1431,6 +1481,11 @@ def generate_source(cls, neural=False):
     # substeps = m > 1: the one line the kernels' time loops read (vihds_models.hpp substeps<>); a class without it generates
     # the text it generated before
     substeps_decl = ["  static constexpr int SUBSTEPS = %d;" % int(cls.substeps)] if cls.substeps > 1 else []
+    # lead_in = L > 0: the two lines the kernels read (vihds_models.hpp lead_in<>); none without it, likewise
+    if cls.lead_in > 0:
+        substeps_decl += ["  static constexpr int LEAD_STEPS = %d;  // steps of the scheme over [t_0 - LEAD_TIME, t_0], nothing stored"
+                          % int(cls.lead_in_steps),
+                          "  static constexpr float LEAD_TIME = %s;" % _lit(cls.lead_in)]
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -1576,6 +1631,10 @@ def register_kernel(cls, neural=False):
     hip.GENERATED_SUBSTEPS[key] = int(cls.substeps)  # (above 1: the library holds the fixed-grid schemes only)
     if cls._trace.jmp is not None:  # (a state jump at the observation points: the fixed-grid schemes only, likewise)
         hip.GENERATED_JUMP.add(key)
+    if cls._trace.start is not None:  # (a start map: the fixed-grid schemes only, likewise)
+        hip.GENERATED_START.add(key)
+    if cls.lead_in > 0:  # (a lead-in phase: the fixed-grid schemes only, likewise)
+        hip.GENERATED_LEAD_IN[key] = (float(cls.lead_in), int(cls.lead_in_steps))
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -1592,11 +1651,14 @@ class GeneratedOdeModel(OdeModel):
     n_conditions = 0
     observe_kind = "default"
     _observe_def = _precision_def = _likelihood_def = _jump_def = None  # the definitions of the hooks the class has (HOOKS: attr)
+    _start_def = None  # ... and of its start map (START_HOOK)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
     implicit = False  # True: the Jacobian of rhs is generated and the implicit solvers take the model (module docstring)
     newton_iterations = 4  # Newton iterations of one implicit step, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
     substeps = 1  # steps a fixed-grid solver takes over each observation interval, 1 .. MAX_SUBSTEPS (module docstring)
+    lead_in = 0.0  # L > 0: the length of an unscored phase before the first observation point, in the units of `times`
+    lead_in_steps = 1  # steps a fixed-grid solver takes over the lead-in phase, 1 .. MAX_LEAD_IN_STEPS (module docstring)
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -1607,7 +1669,7 @@ class GeneratedOdeModel(OdeModel):
             cls.parameter_names = list(declared)
             del cls.parameters
         # ... and its hooks (HOOKS says how each is taken from the class body)
-        for h in HOOKS:
+        for h in ALL_HOOKS:
             definition = cls.__dict__.get(h.name)
             if definition is not None:
                 ok = callable(definition)
@@ -1693,6 +1755,14 @@ class GeneratedOdeModel(OdeModel):
                 "solver '%s' integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
                     type(self).__name__, config.params.solver,
                     ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        for has, what in ((type(self)._start_def is not None, "defines start(self, y, p, c), the state the integration starts from"),
+                          (type(self).lead_in > 0, "has lead_in = %r, steps of a fixed-grid scheme before the first observation "
+                                                   "point" % (type(self).lead_in,))):
+            if has and config.params.solver in hip.ADAPTIVE_SOLVERS:  # (likewise)
+                raise NotImplementedError(
+                    "%s %s: only the kernels of the fixed-grid schemes run it, the adaptive solver '%s' is not available to it "
+                    "(fixed-grid solvers: %s)" % (type(self).__name__, what, config.params.solver,
+                                                  ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         K = len(_class_forcings(type(self)))
         if K:  # (checked before anything is built or queued)
             if config.params.solver in hip.ADAPTIVE_SOLVERS:
@@ -1722,6 +1792,16 @@ class GeneratedOdeModel(OdeModel):
     def has_jump(self):
         """True for a model with a state jump at the observation points (module docstring)."""
         return type(self)._jump_def is not None
+
+    @property
+    def has_start(self):
+        """True for a model with a start map, start(self, y, p, c) (module docstring)."""
+        return type(self)._start_def is not None
+
+    @property
+    def has_lead_in(self):
+        """True for a model with a lead-in phase before the first observation point, lead_in > 0 (module docstring)."""
+        return type(self).lead_in > 0
 
     @property
     def likelihood_kind(self):
@@ -1798,13 +1878,15 @@ class GeneratedOdeModel(OdeModel):
         return call
 
     @classmethod
-    def torch_problem(cls, th, cond, weights=None, times=None):
+    def torch_problem(cls, th, cond, weights=None, times=None, start=True):
         """(rhs, x0) in the convention of oracle.make_*: th maps parameter names to [B, S] tensors, cond is [B, C] (log(1 +
         treatment), as the data holds it; for a class with K forcings the wide rows [n_conditions treatments | K x T samples,
         forcing-major], and `times` [T] is then required: rhs interpolates the samples linearly at its t); rhs(t, state
         [B, S, N]) -> [B, S, N] of the species (no precision states).
         weights: {network name: (W1 [H][I], b1 [H], W2 [O][H], b2 [O])} for a model with networks (an instance's
-        network_weights(), or tensors of the caller's own that require grad: autograd then gives the weight gradients)."""
+        network_weights(), or tensors of the caller's own that require grad: autograd then gives the weight gradients).
+        x0 is the state the integration starts from: a class's start map is applied to its initial state (start=False: the
+        initial state alone); the steps of a lead-in phase are the caller's to take, on lead_in_times."""
         inst = cls.__new__(cls)
         nets = _class_networks(cls)
         if nets:
@@ -1832,6 +1914,8 @@ class GeneratedOdeModel(OdeModel):
         full = lambda v: v if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
         p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
         x0 = torch.stack([full(v) for v in inst.initial_state(thn, _Conditions(cs))], dim=2)
+        if start and cls._start_def is not None:  # (the state the integration starts from)
+            x0 = cls.torch_start(x0, th, cond, **({"n_times": tg.shape[0]} if names else {}))
 
         def rhs(t, state):
             y = list(torch.unbind(state[:, :, :N], dim=2))
@@ -1932,6 +2016,22 @@ class GeneratedOdeModel(OdeModel):
                                        % cls.__name__)
         return _hook_torch(cls, HOOK["jump"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond)
 
+    @classmethod
+    def torch_start(cls, y, theta, cond, n_times=None):
+        """The model's own start map with torch ops in y's dtype (the float64 reference of the generated start / start_vjp): y
+        [B,S,N] what initial_state returned, theta {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as
+        the data holds it (the wide rows of a class with forcings: start reads the first sample of each series; n_times says
+        how many samples a series has where the rows hold more treatments than the model reads) -> the state the integration
+        starts from [B,S,N]."""
+        if cls._start_def is None:
+            raise ModelDefinitionError("%s defines no start(self, y, p, c): its integration starts from its initial state"
+                                       % cls.__name__)
+        K, T = len(_class_forcings(cls)), 1
+        if K:
+            T = int(n_times) if n_times is not None else (cond.shape[1] - int(cls.n_conditions)) // K
+        y = y[:, :, :len(cls.species)]
+        return _hook_torch(cls, HOOK["start"], cls.__new__(cls), [y.unsqueeze(-1).expand(y.shape + (T,))], theta, cond)[..., 0]
+
     def _log_likelihood_map(self, x_predict, observations, precisions):
         """The model's own log density on tensors of the host paths (the host-driven adaptive route, the plugin fallback of
         Training.cost), with theta and the treatments of the last solve, as _observe_map: x_predict [B,S,4,T], observations
@@ -1956,6 +2056,30 @@ class GeneratedOdeModel(OdeModel):
             raise RuntimeError(nothing_solved % type(self).__name__)
         packed, row_of, cond = self._last_inputs
         return {n: packed[row_of[n]].to(dev) for n in type(self).parameter_names}, cond.to(dev)
+
+
+def _fma32(a, b, c):
+    """fmaf(a, b, c) of three float32 numbers: the exact a * b + c rounded once to float32 (to nearest, ties to even)."""
+    from fractions import Fraction
+    exact = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
+    best = np.float32(float(exact))  # (rounded twice: a neighbour may be nearer, never as near -- a tie survives both roundings)
+    for other in (np.nextafter(best, np.float32(-np.inf)), np.nextafter(best, np.float32(np.inf))):
+        if np.isfinite(other) and abs(Fraction(float(other)) - exact) < abs(Fraction(float(best)) - exact):
+            best = other
+    return np.float32(best)
+
+
+def lead_in_times(cls, t0):
+    """The n + 1 float32 times of the class's lead-in phase for a first observation point t0, exactly as the kernels form them
+    (csrc/vihds_substeps.hpp, SubGrid<n>(tl, t0)): tl = t0 - L, hl = (t0 - tl) * (1.f / n), s_j = fmaf(j, hl, tl) for j < n and
+    s_n = t0.  A numpy float32 array; [t0] alone for a class without a lead-in."""
+    t0 = np.float32(t0)
+    if not cls.lead_in > 0:
+        return np.array([t0], dtype=np.float32)
+    n = int(cls.lead_in_steps)
+    tl = np.float32(t0 - np.float32(cls.lead_in))
+    hl = np.float32(np.float32(t0 - tl) * np.float32(np.float32(1.0) / np.float32(n)))
+    return np.array([_fma32(np.float32(j), hl, tl) for j in range(n)] + [t0], dtype=np.float32)
 
 
 def _treatments_torch(cls, cond, like, S):
@@ -2065,6 +2189,25 @@ def _validate(cls):
     if m > 1 and nets:
         raise ModelDefinitionError("%s has substeps = %d and networks: the adjoint's dump of a network holds one evaluation per "
                                    "stage and observation interval (substeps > 1 is for models without networks)" % (name, m))
+    L, n = cls.lead_in, cls.lead_in_steps
+    if (isinstance(L, (bool, np.bool_)) or not isinstance(L, (int, float, np.integer, np.floating)) or not math.isfinite(L)
+            or L < 0 or (L > 0 and not 0 < float(np.float32(L)) < float("inf"))):
+        raise ModelDefinitionError("%s.lead_in = %r; the length of the lead-in phase is a number above 0 in the units of `times` "
+                                   "(a float32 above 0; the default 0.0: no lead-in)" % (name, L))
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= n <= MAX_LEAD_IN_STEPS:
+        raise ModelDefinitionError("%s.lead_in_steps = %r; a fixed-grid solver takes a whole number of steps over the lead-in "
+                                   "phase, 1 .. %d (MAX_LEAD_IN_STEPS)" % (name, n, MAX_LEAD_IN_STEPS))
+    if not L > 0 and n != 1:
+        raise ModelDefinitionError("%s has lead_in_steps = %d without lead_in: the steps divide a lead-in phase of length "
+                                   "lead_in > 0" % (name, n))
+    if L > 0 and (n - 1) * len(cls.species) > MAX_SUBSTEP_ROWS:
+        raise ModelDefinitionError("%s has lead_in_steps = %d and %d species: the adjoint keeps (lead_in_steps - 1) * species "
+                                   "rows of the lead-in's intermediate states in LDS, at most %d (MAX_SUBSTEP_ROWS)"
+                                   % (name, n, len(cls.species), MAX_SUBSTEP_ROWS))
+    if L > 0 and nets:
+        raise ModelDefinitionError("%s has lead_in = %r and networks: the adjoint's dump of a network holds one evaluation per "
+                                   "stage and observation interval, (T-1) x stages (a lead-in phase is for models without "
+                                   "networks)" % (name, L))
     if nets is None:
         return
     if not isinstance(nets, dict) or not all(isinstance(k, str) and k.isidentifier() and isinstance(v, Network)

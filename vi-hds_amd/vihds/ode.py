@@ -144,10 +144,12 @@ def x_predict_on_demand(request, ode, config):
     A map of the model's own -- observe_kind "custom", vihds/modelgen.py -- exists in its kernels only and may read theta:
     such a model always stores x_predict, and the summaries take it from that buffer; so does a model with a precision map
     of its own -- its precision rows go to vihds_iw_summaries, which takes x_predict as a buffer -- and a model with a state
-    jump (has_jump, vihds/modelgen.py): what is read afterwards is the buffer its kernel scored, the left limits."""
+    jump (has_jump, vihds/modelgen.py): what is read afterwards is the buffer its kernel scored, the left limits.  A model
+    with a start map or a lead-in phase (has_start / has_lead_in) likewise: its evaluation stores what its kernel scored."""
     return ((not torch.is_grad_enabled() or request.general_tail)
             and bool(default_get_value(config.params, "lazy_x_predict", True)) and ode.observe_kind != "custom"
-            and ode.precision_kind != "custom" and not getattr(ode, "has_jump", False))
+            and ode.precision_kind != "custom" and not getattr(ode, "has_jump", False)
+            and not getattr(ode, "has_start", False) and not getattr(ode, "has_lead_in", False))
 
 
 class DeviceConditioner(nn.Module):

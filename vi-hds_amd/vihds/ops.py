@@ -101,6 +101,13 @@ class OdeProblemSpec:
                 "model '%s' has a state jump at the observation points, applied between two steps of a fixed-grid scheme: the "
                 "adaptive solver '%s' integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
                     model, solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if solver in hip.ADAPTIVE_SOLVERS and (model in hip.GENERATED_START or model in hip.GENERATED_LEAD_IN):  # (likewise)
+            raise NotImplementedError(
+                "model '%s' has %s, which only the kernels of the fixed-grid schemes run before the first observation point: "
+                "the adaptive solver '%s' is not available to it (fixed-grid solvers: %s)" % (
+                    model, " and ".join(["a start map (start)"] * (model in hip.GENERATED_START)
+                                        + ["a lead-in phase (lead_in)"] * (model in hip.GENERATED_LEAD_IN)),
+                    solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         self.model, self.solver = model, solver
         sized = False
         if model == "dr_blackbox":

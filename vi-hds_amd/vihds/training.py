@@ -4,7 +4,9 @@
 time (fused into the ODE kernel), log p(theta) - log q(theta) (fused into the theta kernel) and the
 importance-weight logsumexp (vihds_iwae_fwd) -- all run in HIP kernels.
 """
+import contextlib
 import functools
+import gc
 import math
 import os
 import time
@@ -34,6 +36,23 @@ def log_prob_observations(model, x_predict, x_obs, precisions, use_laplace=False
         # a generated model's own log density (vihds/modelgen.py), with theta and the treatments of its last solve
         return torch.sum(ode_model._log_likelihood_map(x_predict, x_obs, precisions), 3)
     return torch.sum(log_prob_gaussian(torch.unsqueeze(x_obs, 1), x_predict, precisions), 3)
+
+
+@contextlib.contextmanager
+def _capture_without_gc():
+    """Around a hipGraph capture: Python's cyclic collector runs once before it and not at all inside it.  A capture in the
+    default (global) error mode permits no call that frees device resources, from any thread; a dead reference cycle that still
+    holds some -- a Training of an earlier run with its captured graph and the graph's memory pool -- is freed whenever the
+    collector next runs, and if that is in the middle of a capture the runtime aborts the process.  torch.cuda.graph used
+    to collect on entry; it now does so only under torch.compiler.config.force_cudagraph_gc."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 def _delta_obs(obs):
@@ -433,7 +452,7 @@ class Training:
         g = torch.cuda.CUDAGraph()
         hostdraws.ACTIVE = draws
         try:
-            with torch.cuda.graph(g):
+            with _capture_without_gc(), torch.cuda.graph(g):
                 staged = self._evaluation_device_side(data, n_samples)
         finally:
             hostdraws.ACTIVE = None
@@ -742,7 +761,7 @@ class Training:
                 # single process -- or several ranks whose communicator records into the capture: the collectives sit in
                 # the graph between the kernels they separate, one graph launch per `len(segments)` steps
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, **({"capture_error_mode": "thread_local"} if sync is not None else {})):
+                with _capture_without_gc(), torch.cuda.graph(g, **({"capture_error_mode": "thread_local"} if sync is not None else {})):
                     loss = []
                     for k, (static, prologue) in enumerate(segments):
                         if prologue is not None:
