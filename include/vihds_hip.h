@@ -76,7 +76,11 @@ enum vihds_solver {
   /* `solver: beuler`: backward Euler on the observation grid, y' = y + h f(t1, y'), by a fixed number of Newton iterations
      from y (no convergence test), the linear solves by unpivoted elimination in registers; the adjoint is the
      implicit-function theorem's at the stored y'.  For generated models with `implicit = True` only (their struct has the
-     Jacobian, vihds/modelgen.py); every other model answers VIHDS_E_UNSUPPORTED. */
+     Jacobian, vihds/modelgen.py); every other model answers VIHDS_E_UNSUPPORTED.  The id means "the implicit scheme of the
+     model": a model generated with `implicit_order = 2` runs Alexander's two-stage SDIRK (order 2, L-stable) under it, with
+     a = gamma h, gamma = 1 - sqrt(2)/2: stage 1 solves z1 = y + a f(t0 + gamma h, z1) from y, stage 2 solves
+     y' = w + a f(t1, y') from z1 with w = y + (1 + sqrt(2)) (z1 - y), the same fixed count per stage; its adjoint is the
+     converged step's, with z1 recomputed (vihds_implicit.hpp). */
   VIHDS_SOLVER_BEULER = 9,
   VIHDS_SOLVER_COUNT = 10
 };

@@ -86,7 +86,7 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
   static const GenModelRecord r = {VIHDS_ABI_VERSION, (int)sizeof(OdeArgs), VIHDS_HDR_HASH, traj_rows<GenM>::value, GenM::NSLOT, GenM::NC, GenM::OBS, GenM::NEURAL_PREC ? 1 : 0,
                                    slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
                                    net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
-                                   n_forcings<GenM>::value, has_jacobian<GenM>::value ? 1 : 0, substeps<GenM>::value,
+                                   n_forcings<GenM>::value, implicit_order<GenM>::value, substeps<GenM>::value,
                                    has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value};
   return &r;
 }

@@ -45,8 +45,9 @@ struct GenModelRecord {
   // forcings of the generated struct (vihds_models.hpp n_forcings<>): a data row of cond holds n_forcings series of T samples
   // behind its treatments, so a problem needs C >= n_cond + n_forcings * T; such a model takes the fixed-grid solvers only
   int n_forcings;
-  // 1: the generated struct has a Jacobian (rhs_jac, vihds_models.hpp has_jacobian<>) and the library the kernels of the
-  // implicit solvers (VIHDS_SOLVER_BEULER); 0: it declines them
+  // above 0: the generated struct has a Jacobian (rhs_jac, vihds_models.hpp has_jacobian<>) and the library the kernels of the
+  // implicit solver (VIHDS_SOLVER_BEULER); the value is the order of the model's implicit scheme (implicit_order<>: 1 backward
+  // Euler, 2 the two-stage SDIRK).  0: it declines the implicit solver
   int implicit;
   // steps a fixed-grid scheme takes over each observation interval (vihds_models.hpp substeps<>, >= 1); above 1 the model
   // takes the fixed-grid solvers only and the library holds no kernel of an adaptive pair

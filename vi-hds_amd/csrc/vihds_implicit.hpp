@@ -1,6 +1,7 @@
 // Implicit fixed-grid schemes for generated models with a Jacobian (vihds/modelgen.py: implicit = True; vihds_models.hpp:
-// has_jacobian<M>).  One scheme: backward Euler (VIHDS_SOLVER_BEULER), defined exactly -- with h = t1 - t0 and z = y_k,
-// NEWTON times:
+// has_jacobian<M>).  Solver VIHDS_SOLVER_BEULER is the implicit scheme of the model: backward Euler, or Alexander's two-stage
+// SDIRK for a model generated with implicit_order = 2 (below, sdirk2_step).  Backward Euler, defined exactly -- with
+// h = t1 - t0 and z = y_k, NEWTON times:
 //     F = z - y_k - h f(t1, z);   A = I - h J(t1, z);   solve A d = -F;   z <- z + d
 // then y_k+1 = z.  The count is fixed: no convergence test, no data-dependent branch.  The adjoint is the implicit-function
 // theorem's at the stored y_k+1 (the exact derivative of the converged step; first derivatives only, no Newton in the
@@ -120,6 +121,82 @@ VIHDS_HD void beuler_step_vjp(float h, const float* y_next, float* lam, JF&& jac
   float J[N * N];
   jac(y_next, J);
   implicit_solve<N, JAC_NZ, true>(h, J, lam);
+}
+
+// ---- Alexander's two-stage SDIRK (implicit_order = 2: order 2, L-stable, stiffly accurate) ------------------------------------
+// gamma = 1 - sqrt(2)/2 and c = 1 + sqrt(2) = (1 - gamma) / gamma, each the nearest float.  With h = t1 - t0, a = gamma h and
+// tg = fmaf(gamma, h, t0):
+//     stage 1   z = y_k;  NEWTON times  F = z - y_k - a f(tg, z);  A = I - a J(tg, z);  solve A d = -F;  z <- z + d   -> z1
+//     base      w = fmaf(c, z1 - y_k, y_k)      (= y_k + (1 - gamma) h f(tg, z1) without evaluating a stiff f again)
+//     stage 2   z = z1;   NEWTON times  F = z - w - a f(t1, z);     A = I - a J(t1, z);   solve A d = -F;  z <- z + d   -> y_k+1
+// The count is fixed as for backward Euler.  The adjoint is the converged step's (first derivatives, no Newton iteration on the
+// adjoint): with z1 recomputed by the forward's stage-1 call,  A2 = I - a J(t1, y_k+1), A2^T mu2 = lambda;
+// A1 = I - a J(tg, z1), A1^T mu1 = c mu2;  parameter adjoint += (a mu2)^T df/dp at (t1, y_k+1) + (a mu1)^T df/dp at (tg, z1);
+// lambda <- (1 - c) mu2 + mu1.
+constexpr float kSdirk2Gamma = 0.29289323f;
+constexpr float kSdirk2C = 2.4142137f;
+
+// NEWTON iterations of z = base + a f(z) from z (= the start on entry, the stage value on return).  f(z, out[N]) and
+// jac(z, J[N N]) are the right-hand side and its Jacobian at the stage's time.
+template <int N, int NEWTON, unsigned long long JAC_NZ, class F, class JF>
+VIHDS_HD void sdirk_stage(float a, const float* base, float* z, F&& f, JF&& jac) {
+  static_assert(NEWTON >= 1, "at least one Newton iteration");
+  for (int it = 0; it < NEWTON; ++it) {
+    float fz[N], J[N * N], d[N];
+    f(z, fz);
+    jac(z, J);
+    VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) d[j] = __builtin_fmaf(a, fz[j], base[j] - z[j]);  // -F
+    implicit_solve<N, JAC_NZ, false>(a, J, d);
+    VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) z[j] += d[j];
+  }
+}
+
+// the stage-1 value z1 of the step from y over [t0, t0 + h]; f(t, z, out) and jac(t, z, J) take the stage time
+template <int N, int NEWTON, unsigned long long JAC_NZ, class F, class JF>
+VIHDS_HD void sdirk2_stage1(float t0, float h, const float* y, float* z1, F&& f, JF&& jac) {
+  const float a = kSdirk2Gamma * h;
+  const float tg = __builtin_fmaf(kSdirk2Gamma, h, t0);
+  VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) z1[j] = y[j];
+  sdirk_stage<N, NEWTON, JAC_NZ>(
+      a, y, z1, [&](const float* z, float* fz) { f(tg, z, fz); }, [&](const float* z, float* J) { jac(tg, z, J); });
+}
+
+// One step y (= y_k) -> y_k+1 from t0 to t1.
+template <int N, int NEWTON, unsigned long long JAC_NZ, class F, class JF>
+VIHDS_HD void sdirk2_step(float t0, float t1, float* y, F&& f, JF&& jac) {
+  const float h = t1 - t0;
+  const float a = kSdirk2Gamma * h;
+  float z[N], w[N];
+  sdirk2_stage1<N, NEWTON, JAC_NZ>(t0, h, y, z, f, jac);
+  VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) w[j] = __builtin_fmaf(kSdirk2C, z[j] - y[j], y[j]);
+  sdirk_stage<N, NEWTON, JAC_NZ>(
+      a, w, z, [&](const float* u, float* fz) { f(t1, u, fz); }, [&](const float* u, float* J) { jac(t1, u, J); });
+  VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) y[j] = z[j];
+}
+
+// The step's adjoint at the start state y (= y_k) and the stored y_next (= y_k+1): lam (adjoint of y_k+1) <- adjoint of y_k.
+// z1 (the recomputed stage value), mu1 and mu2 are returned for the caller's two parameter products: rhs_vjp at (t1, y_next)
+// seeded with a mu2 and at (tg, z1) seeded with a mu1.
+template <int N, int NEWTON, unsigned long long JAC_NZ, class F, class JF>
+VIHDS_HD void sdirk2_step_vjp(float t0, float t1, const float* y, const float* y_next, float* lam, float* z1, float* mu1,
+                              float* mu2, F&& f, JF&& jac) {
+  const float h = t1 - t0;
+  const float a = kSdirk2Gamma * h;
+  const float tg = __builtin_fmaf(kSdirk2Gamma, h, t0);
+  sdirk2_stage1<N, NEWTON, JAC_NZ>(t0, h, y, z1, f, jac);
+  {
+    float J[N * N];
+    jac(t1, y_next, J);
+    VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) mu2[j] = lam[j];
+    implicit_solve<N, JAC_NZ, true>(a, J, mu2);
+  }
+  {
+    float J[N * N];
+    jac(tg, z1, J);
+    VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) mu1[j] = kSdirk2C * mu2[j];
+    implicit_solve<N, JAC_NZ, true>(a, J, mu1);
+  }
+  VIHDS_IMPLICIT_UNROLL for (int j = 0; j < N; ++j) lam[j] = __builtin_fmaf(1.f - kSdirk2C, mu2[j], mu1[j]);
 }
 
 }  // namespace vihds

@@ -981,6 +981,18 @@ template <class M, class = void>
 struct has_jacobian : std::false_type {};
 template <class M>
 struct has_jacobian<M, std::void_t<decltype(M::NEWTON), decltype(M::JAC_NZ)>> : std::true_type {};
+// The order of such a model's implicit scheme: 2 for a core generated with `implicit_order = 2` (it declares IMPLICIT_ORDER = 2:
+// Alexander's two-stage SDIRK, vihds_implicit.hpp), 1 for any other model with a Jacobian (backward Euler), 0 without one.
+// WithPrec<> does not forward it.
+template <class M, class = void>
+struct implicit_order {
+  static constexpr int value = has_jacobian<M>::value ? 1 : 0;
+};
+template <class M>
+struct implicit_order<M, std::void_t<decltype(M::IMPLICIT_ORDER)>> {
+  static_assert(has_jacobian<M>::value && M::IMPLICIT_ORDER == 2, "IMPLICIT_ORDER is 2, on a model with a Jacobian");
+  static constexpr int value = 2;
+};
 
 // A core generated with `substeps = m > 1` (vihds/modelgen.py) declares SUBSTEPS = m: every fixed-grid scheme takes m steps of
 // its own over each observation interval (vihds_substeps.hpp defines the sub-step times), the adjoint recomputes the

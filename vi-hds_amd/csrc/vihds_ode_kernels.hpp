@@ -186,6 +186,12 @@ __device__ __forceinline__ void ode_step(float t0, float t1, float h0, float* y,
   constexpr int N = M::N;
   if constexpr (solver_is_implicit(SOLVER)) {  // backward Euler by M::NEWTON Newton iterations from y (vihds_implicit.hpp)
     static_assert(has_jacobian<M>::value, "an implicit solver needs a model generated with implicit = True");
+    if constexpr (implicit_order<M>::value == 2) {  // ... or the model's two-stage SDIRK, M::NEWTON iterations per stage
+      sdirk2_step<N, M::NEWTON, M::JAC_NZ>(
+          t0, t1, y, [&](float t, const float* z, float* fz) { M::rhs(t, z, p, wts, fz); },
+          [&](float t, const float* z, float* J) { M::rhs_jac(t, z, p, wts, J); });
+      return;
+    }
     beuler_step<N, M::NEWTON, M::JAC_NZ>(
         t1 - t0, y, [&](const float* z, float* fz) { M::rhs(t1, z, p, wts, fz); },
         [&](const float* z, float* J) { M::rhs_jac(t1, z, p, wts, J); });
@@ -331,6 +337,36 @@ __device__ __forceinline__ void ode_step_vjp_implicit(float t0, float t1, const 
   call_vjp<M>(t1, y_next, p, wts, v, unused, pb, wtsb);
 }
 
+// reverse of one step of the two-stage SDIRK (implicit_order<M> = 2), from the step's start state y = y_k and the stored
+// y_next = y_k+1: the stage value z1 is recomputed by the forward's stage-1 call into registers (no Newton iteration runs on the
+// adjoint itself), lam <- (1 - c) mu2 + mu1, then pb += (a mu2)^T df/dp at (t1, y_next) + (a mu1)^T df/dp at (tg, z1) by two
+// rhs_vjp calls whose state output is discarded.  Instantiated for such a model only.
+template <class M, class Ctx>
+__device__ __forceinline__ void ode_step_vjp_sdirk2(float t0, float t1, const float* y, const float* y_next, const float* p,
+                                                    const float* wts, float* lam, float* pb, Ctx& wtsb) {
+  constexpr int N = M::N;
+  static_assert(implicit_order<M>::value == 2, "the two-stage scheme needs a model generated with implicit_order = 2");
+  const float h = t1 - t0;
+  const float a = kSdirk2Gamma * h;
+  const float tg = __builtin_fmaf(kSdirk2Gamma, h, t0);
+  float z1[N], mu1[N], mu2[N], unused[N];
+  sdirk2_step_vjp<N, M::NEWTON, M::JAC_NZ>(
+      t0, t1, y, y_next, lam, z1, mu1, mu2, [&](float t, const float* z, float* fz) { M::rhs(t, z, p, wts, fz); },
+      [&](float t, const float* z, float* J) { M::rhs_jac(t, z, p, wts, J); });
+  VIHDS_UNROLL for (int j = 0; j < N; ++j) { mu2[j] = a * mu2[j]; unused[j] = 0.f; }
+  call_vjp<M>(t1, y_next, p, wts, mu2, unused, pb, wtsb);
+  VIHDS_UNROLL for (int j = 0; j < N; ++j) { mu1[j] = a * mu1[j]; unused[j] = 0.f; }
+  call_vjp<M>(tg, z1, p, wts, mu1, unused, pb, wtsb);
+}
+// ... of one step of the model's implicit scheme, whichever it is: y (the step's start state) is read by the two-stage scheme
+// only (backward Euler's adjoint needs no start state: a caller may pass nullptr for such a model)
+template <class M, class Ctx>
+__device__ __forceinline__ void ode_step_vjp_implicit_any(float t0, float t1, const float* y, const float* y_next,
+                                                          const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb) {
+  if constexpr (implicit_order<M>::value == 2) ode_step_vjp_sdirk2<M>(t0, t1, y, y_next, p, wts, lam, pb, wtsb);
+  else ode_step_vjp_implicit<M>(t0, t1, y_next, p, wts, lam, pb, wtsb);
+}
+
 // ---- sub-steps per observation interval (substeps<M> = MS > 1, vihds_substeps.hpp) -----------------------------------
 // Everything below is instantiated for a generated model with `substeps` above 1 only: the time loops reach it behind
 // `if constexpr (substeps<M>::value > 1)`, so every other model's kernels are what they were.
@@ -386,9 +422,20 @@ __device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, c
     VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y_next[q];  // u_MS
 #pragma unroll 1
     for (int j = MS - 1; j >= 0; --j) {
-      ode_step_vjp_implicit<M>(sg.at(j), sg.at(j + 1), u, p, wts, lam, pb, wtsb);
-      if (j > 0) {  // u_j for the sub-step below
-        VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 1) * N + q) * 256];
+      if constexpr (implicit_order<M>::value == 2) {  // (the two-stage scheme's adjoint also reads the sub-step's start u_j)
+        float us[N];
+        if (j > 0) {
+          VIHDS_UNROLL for (int q = 0; q < N; ++q) us[q] = col[((j - 1) * N + q) * 256];
+        } else {
+          VIHDS_UNROLL for (int q = 0; q < N; ++q) us[q] = y[q];
+        }
+        ode_step_vjp_sdirk2<M>(sg.at(j), sg.at(j + 1), us, u, p, wts, lam, pb, wtsb);
+        VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = us[q];
+      } else {
+        ode_step_vjp_implicit<M>(sg.at(j), sg.at(j + 1), u, p, wts, lam, pb, wtsb);
+        if (j > 0) {  // u_j for the sub-step below
+          VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 1) * N + q) * 256];
+        }
       }
     }
   } else {  // (u holds u_MS-1)
@@ -439,9 +486,20 @@ __device__ __forceinline__ void ode_lead_in_vjp(float t_first, const float* y_st
       VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y_first[q];  // u_NL
 #pragma unroll 1
       for (int j = NL - 1; j >= 0; --j) {
-        ode_step_vjp_implicit<M>(sg.at(j), sg.at(j + 1), u, p, wts, lam, pb, wtsb);
-        if (j > 0) {  // u_j for the step below
-          VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 1) * N + q) * 256];
+        if constexpr (implicit_order<M>::value == 2) {  // (the two-stage scheme's adjoint also reads the step's start u_j)
+          float us[N];
+          if (j > 0) {
+            VIHDS_UNROLL for (int q = 0; q < N; ++q) us[q] = col[((j - 1) * N + q) * 256];
+          } else {
+            VIHDS_UNROLL for (int q = 0; q < N; ++q) us[q] = y_start[q];
+          }
+          ode_step_vjp_sdirk2<M>(sg.at(j), sg.at(j + 1), us, u, p, wts, lam, pb, wtsb);
+          VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = us[q];
+        } else {
+          ode_step_vjp_implicit<M>(sg.at(j), sg.at(j + 1), u, p, wts, lam, pb, wtsb);
+          if (j > 0) {  // u_j for the step below
+            VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 1) * N + q) * 256];
+          }
         }
       }
     } else {  // (u holds u_NL-1)
@@ -456,7 +514,7 @@ __device__ __forceinline__ void ode_lead_in_vjp(float t_first, const float* y_st
       }
     }
   } else if constexpr (solver_is_implicit(SOLVER)) {
-    ode_step_vjp_implicit<M>(sg.at(0), sg.at(1), y_first, p, wts, lam, pb, wtsb);
+    ode_step_vjp_implicit_any<M>(sg.at(0), sg.at(1), u, y_first, p, wts, lam, pb, wtsb);
   } else {
     ode_step_vjp<M, SOLVER>(sg.at(0), sg.at(1), sg.hs, u, p, wts, lam, pb, wtsb);
   }
@@ -949,7 +1007,12 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
           if constexpr (solver_is_implicit(SOLVER)) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, yj, ff.y_next, p, wts, lam, pb, wtsb);
           else ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, yj, nullptr, p, wts, lam, pb, wtsb);
         } else if constexpr (solver_is_implicit(SOLVER)) {
-          ode_step_vjp_implicit<M>(tK, tHi, ff.y_next, p, wts, lam, pb, wtsb);
+          if constexpr (implicit_order<M>::value == 2) {  // (the two-stage scheme's adjoint starts from yj as well)
+            M::jump(y, p, yj);
+            ode_step_vjp_sdirk2<M>(tK, tHi, yj, ff.y_next, p, wts, lam, pb, wtsb);
+          } else {
+            ode_step_vjp_implicit<M>(tK, tHi, ff.y_next, p, wts, lam, pb, wtsb);
+          }
         } else {
           M::jump(y, p, yj);
           ode_step_vjp<M, SOLVER>(tK, tHi, h0, yj, p, wts, lam, pb, wtsb);
@@ -969,7 +1032,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
         if (k < a.T - 1) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, y, nullptr, p, wts, lam, pb, wtsb);
       }
     } else if constexpr (solver_is_implicit(SOLVER)) {
-      if (k < a.T - 1) ode_step_vjp_implicit<M>(tK, tHi, ff.y_next, p, wts, lam, pb, wtsb);
+      if (k < a.T - 1) ode_step_vjp_implicit_any<M>(tK, tHi, y, ff.y_next, p, wts, lam, pb, wtsb);
       VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
     } else {
       if (k < a.T - 1) ode_step_vjp<M, SOLVER>(tK, tHi, h0, y, p, wts, lam, pb, wtsb);

@@ -36,6 +36,8 @@ GENERATED_NETWORKS = {}
 GENERATED_OWN_PRECISION = set()
 # keys of registered models generated with `implicit = True` (a Jacobian in their struct): the only models an implicit solver takes
 GENERATED_IMPLICIT = set()
+# ... key -> `implicit_order` of those models: what solver "beuler" runs for the model, 1 backward Euler, 2 the two-stage SDIRK
+GENERATED_IMPLICIT_ORDER = {}
 # registered generated models: key -> `substeps`, the steps a fixed-grid solver takes over each observation interval.  Above 1
 # the model declines the adaptive solvers (they choose their own steps)
 GENERATED_SUBSTEPS = {}
@@ -53,8 +55,9 @@ SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 
 # torchdiffeq's adaptive pairs (vihds_rk_adaptive.hpp); "dopri8" runs an 8th-order Dormand-Prince pair with Hairer's
 # DOP853 coefficients, not torchdiffeq's own 8(7) tableau (vihds_dop853_tableau.hpp)
 ADAPTIVE_SOLVERS = ("dopri5", "bosh3", "adaptive_heun", "dopri8")
-# implicit schemes on the observation grid (vihds_implicit.hpp): backward Euler by a fixed number of Newton iterations, for
-# generated models with `implicit = True` (vihds/modelgen.py).  Not adaptive: the captured training step takes them
+# implicit schemes on the observation grid (vihds_implicit.hpp): "beuler" is the implicit scheme of the model -- backward Euler,
+# or the two-stage SDIRK of a class with `implicit_order = 2` -- by a fixed number of Newton iterations, for generated models
+# with `implicit = True` (vihds/modelgen.py).  Not adaptive: the captured training step takes them
 IMPLICIT_SOLVERS = ("beuler",)
 
 _c_float_p = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())

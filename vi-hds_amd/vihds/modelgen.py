@@ -152,6 +152,26 @@ not generated), with NeuralPrecisions (the precision ODE has no Jacobian), with 
 every explicit solver.  A class without `implicit` generates byte for byte the text it generated before.  torch_jacobian
 evaluates the same DAG nodes with torch ops, to check the generator against autograd.
 
+Backward Euler is first order: `substeps` buys accuracy linearly.  An implicit class that also sets
+
+        implicit_order = 2                           # the int 1 (default) or 2; 2 needs implicit = True
+
+runs Alexander's two-stage SDIRK under the same solver name -- "beuler" is the implicit scheme of the model; there is no new
+solver id, hip.GENERATED_IMPLICIT_ORDER[key] tells which scheme a registered model runs.  It is order 2, L-stable and stiffly
+accurate (stability function (1 + (1 - 2 gamma) z) / (1 - gamma z)^2).  With gamma the float nearest 1 - sqrt(2)/2, c the
+float nearest 1 + sqrt(2), h = t1 - t0, a = gamma * h and tg = fmaf(gamma, h, t0), in float32: stage 1 starts at z = y_k and
+runs NEWTON times  F = z - y_k - a f(tg, z), A = I - a J(tg, z), solve A d = -F, z += d  to z1; the base of stage 2 is
+w = fmaf(c, z1 - y_k, y_k), which is y_k + (1 - gamma) h f(tg, z1) without another evaluation of a stiff f; stage 2 starts at
+z = z1 and runs NEWTON times  F = z - w - a f(t1, z), A = I - a J(t1, z), solve A d = -F, z += d  to y_k+1.
+newton_iterations is the count per stage; no convergence test, as above.  A forcing is read at tg and at t1 from the
+interval's interpolant.  The adjoint is the converged step's, first derivatives only: z1 is recomputed by the forward's
+stage-1 call (registers, no LDS), A2 = I - a J(t1, y_k+1), A2^T mu2 = lambda;  A1 = I - a J(tg, z1), A1^T mu1 = c mu2;  the
+parameter adjoint gains (a mu2)^T df/dp at (t1, y_k+1) and (a mu1)^T df/dp at (tg, z1);  lambda <- (1 - c) mu2 + mu1.  The
+stage matrix is I - gamma h J: Newton from y_k on a growing mode reaches steps about 3.4 times longer than backward Euler's.
+The order combines with everything `implicit` combines with (forcings, substeps, jump, start, lead_in, the hooks), whose
+definitions are written over the one-step map; what `implicit` refuses stays refused.  The generated struct gains the one
+line IMPLICIT_ORDER = 2 (none at order 1: such a class generates byte for byte the text it generated before).
+
 Sub-steps.  The observation grid is the plate reader's, not the model's: a fixed-grid solver takes one step per interval of it.
 A class that sets
 
@@ -1473,6 +1493,9 @@ def generate_source(cls, neural=False):
             "  static constexpr int NEWTON = %d;" % int(cls.newton_iterations),
             "  static constexpr unsigned long long JAC_NZ = 0x%xull;  // structural non-zeros of rhs_jac, bit i * N + j: %d of %d" % (
                 mask, len(nz), N * N)]
+        # implicit_order = 2: the one line the kernels read (vihds_models.hpp implicit_order<>); none at order 1
+        if cls.implicit_order == 2:
+            implicit_decl += ["  static constexpr int IMPLICIT_ORDER = 2;  // the two-stage SDIRK of vihds_implicit.hpp"]
         jac_decl = ["  // J[i * N + j] = d dy[i] / d y[j]; a structural zero is the literal 0.f",
                     "  __device__ static void rhs_jac(float t, const float* y, const float* p, const float*, float* J) {",
                     body([("J[%d]" % (i * N + j), "=", J[i][j]) for i, j in nz], True, "v", tr.c_slot, f_at_t)]
@@ -1628,6 +1651,7 @@ def register_kernel(cls, neural=False):
         hip.GENERATED_OWN_PRECISION.add(key)
     if cls.implicit:  # (the library holds the kernels of the implicit solvers)
         hip.GENERATED_IMPLICIT.add(key)
+        hip.GENERATED_IMPLICIT_ORDER[key] = int(cls.implicit_order)
     hip.GENERATED_SUBSTEPS[key] = int(cls.substeps)  # (above 1: the library holds the fixed-grid schemes only)
     if cls._trace.jmp is not None:  # (a state jump at the observation points: the fixed-grid schemes only, likewise)
         hip.GENERATED_JUMP.add(key)
@@ -1656,6 +1680,7 @@ class GeneratedOdeModel(OdeModel):
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
     implicit = False  # True: the Jacobian of rhs is generated and the implicit solvers take the model (module docstring)
     newton_iterations = 4  # Newton iterations of one implicit step, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
+    implicit_order = 1  # the order of the implicit scheme: 1 backward Euler, 2 the two-stage SDIRK (needs implicit = True)
     substeps = 1  # steps a fixed-grid solver takes over each observation interval, 1 .. MAX_SUBSTEPS (module docstring)
     lead_in = 0.0  # L > 0: the length of an unscored phase before the first observation point, in the units of `times`
     lead_in_steps = 1  # steps a fixed-grid solver takes over the lead-in phase, 1 .. MAX_LEAD_IN_STEPS (module docstring)
@@ -2167,6 +2192,13 @@ def _validate(cls):
     nets = getattr(cls, "networks", None)
     if not isinstance(cls.implicit, (bool, np.bool_)):
         raise ModelDefinitionError("%s.implicit must be True or False" % name)
+    order = cls.implicit_order
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or order not in (1, 2):
+        raise ModelDefinitionError("%s.implicit_order = %r; the order of the implicit scheme is the int 1 (backward Euler) or 2 "
+                                   "(the two-stage SDIRK)" % (name, order))
+    if order == 2 and not cls.implicit:
+        raise ModelDefinitionError("%s has implicit_order = 2 without implicit = True: the order is that of the implicit "
+                                   "scheme, which needs the generated Jacobian" % name)
     if cls.implicit:
         it = cls.newton_iterations
         if isinstance(it, bool) or not isinstance(it, (int, np.integer)) or not 1 <= it <= MAX_NEWTON_ITERATIONS:
