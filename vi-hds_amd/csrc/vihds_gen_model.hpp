@@ -7,11 +7,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "vihds_algebraic.hpp"  // a generated struct with algebraic variables calls its templates from rhs and observe
 #include "vihds_args.hpp"
 
 // registered models take ids from here on (far above the built-in enum vihds_model)
 #define VIHDS_GEN_MODEL_BASE 1024
-#define VIHDS_GEN_MODEL_MAX 64
+#define VIHDS_GEN_MODEL_MAX 128  // (models one process may register: the GPU suite alone registers more than 64)
 
 // hash of the kernel headers a library was compiled from (the Makefile passes it to every object that needs it)
 #ifndef VIHDS_HDR_HASH

@@ -49,6 +49,9 @@ GENERATED_JUMP = set()
 # fixed-grid schemes call start and run the steps before t_0)
 GENERATED_START = set()
 GENERATED_LEAD_IN = {}
+# registered generated models with algebraic variables (`algebraic`, `constraint`): key -> the number of unknowns their struct
+# solves for inside rhs and observe (nothing else differs: every explicit solver takes them)
+GENERATED_ALGEBRAIC = {}
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8, "beuler": 9}

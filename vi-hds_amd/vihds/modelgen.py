@@ -238,6 +238,40 @@ last to first, then start_vjp ahead of prepare_vjp, and hands the state part to 
 NeuralPrecisions; a lead-in takes no networks (the dump is sized (T-1) x stages), start combines with networks in rhs.  A class
 with neither generates byte for byte the text it generated before.  torch_start restates the hook with torch ops.
 
+Algebraic variables.  A fast reaction held at its equilibrium -- binding and unbinding of a repressor, an inducer, a dimer, orders
+of magnitude faster than expression and dilution -- is the reduction modellers reach for before a stiff solver: the TOTALS stay
+ODE states and the complex is defined by a constraint g(y, z, p) = 0 (quasi-steady state, rapid equilibrium).  A class declares
+
+        algebraic = ["C"]                            # 1 .. MAX_ALGEBRAIC = 4 unknowns z; identifiers of their own
+        algebraic_iterations = 6                     # 1 .. MAX_NEWTON_ITERATIONS, an int: a fixed Newton count
+        def algebraic_start(self, y, p, c):          # -> the iteration's starting value, one entry per unknown
+            return [y[0] * y[1] / (y[0] + y[1] + p.Kd)]
+        def constraint(self, y, z, p, c):            # -> one residual per unknown; z solves constraint(...) == 0
+            return [(y[0] - z[0]) * (y[1] - z[0]) - p.Kd * z[0]]
+
+and reads self.algebraic.C in rhs and in observe (reading it in prepare, initial_state, start, precision, log_likelihood or jump
+raises and says so).  constraint and algebraic_start have no t and call no network; they read the species, the effective
+parameters, the treatments and the forcings -- in rhs a forcing is the interpolant at the stage time, in observe the sample of
+the time point.  The value, exactly: z = algebraic_start(y, p); algebraic_iterations times G = g(y, z, p), A = dg/dz (y, z, p),
+solve A d = -G, z += d; then rhs / observe are evaluated with that z.  No convergence test, no data-dependent branch; the solve
+is Gaussian elimination without a pivot search on the structural pattern of dg/dz (ALG_NZ; csrc/vihds_algebraic.hpp), so
+residual i must depend on unknown i (a structurally zero pivot, column or row is refused when the class is defined; a pivot
+that vanishes numerically gives inf / NaN, which reaches the non-finite-loss exit).  The adjoint repeats the value pass (the
+same bits), takes the adjoint zb of z from reverse mode over rhs / observe, solves A^T mu = zb with A at the final z and
+subtracts (dg/dy)^T mu from the state adjoint and (dg/dp)^T mu from the parameter adjoint -- one vjp of the constraint seeded
+with -mu.  That is the implicit-function derivative of the CONVERGED solution: nothing is differentiated through the iteration
+or through algebraic_start, so too few iterations (or a start near a double root, where Newton converges slowly) leave an
+adjoint that is not the gradient of what was computed.  A treatment or forcing read by the constraint has no adjoint.  The
+closure lives inside the struct's rhs / rhs_vjp and observe / observe_vjp (the members algebraic_start, constraint,
+constraint_jac, constraint_vjp, algebraic, algebraic_vjp and the constants N_ALGEBRAIC, ALG_ITER, ALG_NZ): every explicit
+solver runs such a model with unchanged kernels, and substeps, jump, start, lead_in, forcings, an own precision and an own
+log_likelihood combine with it.  Refused in this version: together with implicit = True (the reduced Jacobian f_y - f_z
+g_z^-1 g_y is not generated), with networks, with NeuralPrecisions, more than MAX_ALGEBRAIC unknowns.  A class without
+`algebraic` generates byte for byte the text it generated before.  torch_algebraic(y, theta, cond) returns z by the same
+iteration with torch ops (autograd Jacobians, a pivoted solve); it keeps the iterate's value and carries the implicit-function
+gradient, and torch_problem's right-hand side and torch_observe use it, so autograd through the host paths stays correct;
+torch_constraint_jacobian evaluates the generated dg/dz, to check the generator against autograd.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -287,6 +321,9 @@ MAX_SUBSTEP_ROWS = 56  # (substeps - 1) * species: a block's static LDS ends at 
 # steps of the lead-in phase before the first observation point (`lead_in_steps`).  The adjoint keeps its intermediate states in
 # the LDS rows the sub-steps use (never both at once): (lead_in_steps - 1) * species rows, at most MAX_SUBSTEP_ROWS
 MAX_LEAD_IN_STEPS = 8
+# unknowns of a model with `algebraic` variables: the matrix of a Newton step on the constraint lives in registers beside the
+# states, its structural pattern is one 16-bit constant (tests/test_modelgen_algebraic_host.py compiles four without scratch)
+MAX_ALGEBRAIC = 4
 
 
 class ModelDefinitionError(TypeError):
@@ -335,6 +372,8 @@ _LEAVES = ("const", "th", "c", "y", "p", "t", "seed", "x")  # (x: the predicted 
 _LEAVES += ("ob", "pr")
 # ... and the forcings (rhs and the hooks): per-row time series, data like the observations
 _LEAVES += ("f",)
+# ... and the algebraic variables (rhs and observe): the unknowns z of the class's constraint, solved for where they are read
+_LEAVES += ("z",)
 _NO_ADJOINT = ("ob", "f")
 
 
@@ -991,6 +1030,47 @@ class _Forcings(object):
         raise ModelDefinitionError("forcings are read-only")
 
 
+def _class_algebraic(cls):
+    return list(getattr(cls, "algebraic", None) or ())
+
+
+class _Algebraic(object):
+    """`self.algebraic` of the instance the functions run on: `self.algebraic.<name>` is that unknown of the constraint at the
+    state where the function is evaluated.  read(i, name) does the work (symbolic or torch)."""
+
+    def __init__(self, cls, read):
+        object.__setattr__(self, "_names", _class_algebraic(cls))
+        object.__setattr__(self, "_read", read)
+        object.__setattr__(self, "_cls", cls.__name__)
+
+    def __getattr__(self, name):
+        if name not in self._names:
+            raise ModelDefinitionError("unknown algebraic variable '%s' (%s.algebraic declares: %s)"
+                                       % (name, self._cls, ", ".join(self._names) or "none"))
+        return self._read(self._names.index(name), name)
+
+    __getitem__ = __getattr__
+
+    def __setattr__(self, name, value):
+        raise ModelDefinitionError("algebraic variables are read-only")
+
+    def __len__(self):
+        return len(self._names)
+
+    def __iter__(self):
+        return iter(self._names)
+
+
+_ALGEBRAIC_READERS = ("rhs", "observe")  # the functions that may read self.algebraic.<name>
+
+
+def _algebraic_misread(name, where):
+    raise ModelDefinitionError(
+        "algebraic variable '%s' read in %s: the constraint is solved where rhs and observe are evaluated -- an algebraic "
+        "variable is read in rhs(self, t, y, p, c) and in observe(self, y, p, c) only (constraint receives the unknowns as its "
+        "argument z)" % (name, where))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the hook table
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1149,6 +1229,14 @@ class Trace(object):
             return g.leaf("f", k)
 
         object.__setattr__(inst, "forcing", _Forcings(cls, read))
+        self.algebraic = _class_algebraic(cls)
+
+        def read_z(i, name):
+            if self._phase not in _ALGEBRAIC_READERS:
+                _algebraic_misread(name, self._phase)
+            return g.leaf("z", i)
+
+        object.__setattr__(inst, "algebraic", _Algebraic(cls, read_z))
         N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
         th = _Named([(n, g.leaf("th", s)) for s, n in enumerate(P)], "parameter")
         cs = [g.leaf("c", q) for q in range(C)]
@@ -1165,6 +1253,17 @@ class Trace(object):
         # one more effective parameter (copied by prepare, no adjoint)
         NPU = len(self.p_names)
         p = _Named([(n, g.leaf("p", k)) for k, n in enumerate(self.p_names)], "effective parameter")
+        # the algebraic variables: the start of the iteration and the constraint, which see the species, the effective
+        # parameters, the treatments and the forcings -- no t (a class without them traces nothing here)
+        self.z0 = self.con = None
+        M = len(self.algebraic)
+        if M:
+            ys, cz = [g.leaf("y", j) for j in range(N)], _Conditions([g.leaf("p", NPU + q) for q in range(C)])
+            self._phase = "algebraic_start"
+            self.z0 = self._unknown_list(inst.algebraic_start(ys, p, cz), "algebraic_start", M)
+            self._phase = "constraint"
+            self.con = self._unknown_list(inst.constraint(ys, [g.leaf("z", i) for i in range(M)], p, cz), "constraint", M)
+            self._phase = "rhs"
         self.dy = self._state_list(inst.rhs(g.leaf("t", 0), [g.leaf("y", j) for j in range(N)], p,
                                             _Conditions([g.leaf("p", NPU + q) for q in range(C)])), "rhs", N)
         reached = {n.val for n in _topo(self.dy) if n.op == "net"}
@@ -1185,13 +1284,20 @@ class Trace(object):
                     raise ModelDefinitionError("%s.%s must return a list of %d entries (%s)"
                                                % (cls.__name__, h.name, h.count(N), h.outputs))
                 setattr(self, h.traced, [g._arg(x) for x in out])
-        used = {n.val for n in _topo(self.dy + [x for h in ALL_HOOKS for x in getattr(self, h.traced) or []]) if n.op == "p"}
+        used = {n.val for n in _topo(self.dy + [x for h in ALL_HOOKS for x in getattr(self, h.traced) or []]
+                                     + (self.z0 or []) + (self.con or [])) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
         self.c_slot = {NPU + q: NPU + k for k, q in enumerate(self.c_in_rhs)}
         # the forcings' entries of p follow: K values, K slopes, one interval start (the struct's set_interval / set_point)
         self.F0 = self.NP
+
+    def _unknown_list(self, v, what, M):
+        if not isinstance(v, (list, tuple)) or len(v) != M:
+            raise ModelDefinitionError("%s.%s must return a list of %d entries (one per algebraic variable: %s)"
+                                       % (self.cls.__name__, what, M, ", ".join(self.algebraic)))
+        return [self.g._arg(x) for x in v]
 
     def _state_list(self, v, what, N):
         if not isinstance(v, (list, tuple)) or len(v) != N:
@@ -1347,6 +1453,48 @@ def jacobian_pattern(cls):
     return [[not _is_const(e, 0.0) for e in row] for row in jacobian_nodes(cls)]
 
 
+def constraint_jacobian_nodes(cls):
+    """dg/dz of the class's constraint as DAG nodes, row by row: A[i][j] = d g_i / d z_j, by reverse mode with constant one-hot
+    seeds (as jacobian_nodes does for rhs).  A structural zero is the constant 0."""
+    tr = cls._trace
+    g, M = tr.g, len(tr.algebraic)
+    rows = []
+    for i in range(M):
+        adj = vjp(g, tr.con, [1.0 if k == i else 0.0 for k in range(M)])
+        rows.append([adj.get(g.leaf("z", j).id, g.const(0.0)) for j in range(M)])
+    return rows
+
+
+def constraint_pattern(cls):
+    """[M][M] bools: the entries of dg/dz that are not structurally zero."""
+    return [[not _is_const(e, 0.0) for e in row] for row in constraint_jacobian_nodes(cls)]
+
+
+def _check_constraint_pattern(cls):
+    """A structurally singular dg/dz is refused when the class is defined: an unknown no residual depends on, a residual that
+    depends on no unknown, and -- the elimination has no pivot search -- a pivot that is a structural zero after fill-in."""
+    names, pat = _class_algebraic(cls), [list(r) for r in constraint_pattern(cls)]
+    M = len(names)
+    for j in range(M):
+        if not any(pat[i][j] for i in range(M)):
+            raise ModelDefinitionError("%s.constraint: no residual depends on the algebraic variable '%s' -- dg/dz has a zero "
+                                       "column and is structurally singular" % (cls.__name__, names[j]))
+    for i in range(M):
+        if not any(pat[i]):
+            raise ModelDefinitionError("%s.constraint: residual %d depends on no algebraic variable -- dg/dz has a zero row and "
+                                       "is structurally singular" % (cls.__name__, i))
+    for k in range(M):
+        if not pat[k][k]:
+            raise ModelDefinitionError(
+                "%s.constraint: residual %d does not depend on the algebraic variable '%s' (not even after the elimination's "
+                "fill-in) -- the solve eliminates without a pivot search, so pivot %d would be a structural zero: order the "
+                "residuals so that residual i depends on unknown i" % (cls.__name__, k, names[k], k))
+        for i in range(k + 1, M):
+            if pat[i][k]:
+                for j in range(k + 1, M):
+                    pat[i][j] = pat[i][j] or pat[k][j]
+
+
 def _leaf_free(node, allowed):
     return all(n.op not in _LEAVES or n.op == "const" or n.op in allowed for n in _topo([node]))
 
@@ -1372,6 +1520,10 @@ def generate_source(cls, neural=False):
                                    "stage and observation interval, so a model with a lead-in phase does not take "
                                    "NeuralPrecisions (constant precisions, or a precision map of its own)"
                                    % (cls.__name__, cls.lead_in))
+    if neural and tr.algebraic:
+        raise ModelDefinitionError("%s declares algebraic variables: WithPrec<> evaluates the precision ODE beside a rhs that has no "
+                                   "unknowns, so a model with algebraic variables does not take NeuralPrecisions (constant "
+                                   "precisions, or a precision map of its own)" % cls.__name__)
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -1425,8 +1577,22 @@ def generate_source(cls, neural=False):
 
     def body(assign, fast, seed, p_map=None, forcing=None):
         names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp", "ob": "ob", "pr": "pr",
-                 "f": forcing}
+                 "f": forcing, "z": "z"}
         return "\n".join(_Emitter(fast, names, p_map).emit(assign))
+
+    # algebraic variables: a member that reads them opens with the solve, its adjoint repeats the solve and closes with the mu
+    # step (csrc/vihds_algebraic.hpp).  `u` holds the forcings' values where the member is evaluated
+    M = len(tr.algebraic)
+
+    def reads_z(outs):
+        return M > 0 and any(n.op == "z" for n in _topo([o for o in outs if isinstance(o, Sym)]))
+
+    def solve_z(forcing):
+        head = ["    const float u[%d] = {%s};" % (K, ", ".join(forcing))] if K else ["    const float* u = nullptr;"]
+        return head + ["    float z[%d];" % M, "    algebraic(y, p, u, z);"]
+
+    def pull_z(adj):
+        return [("zb[%d]" % i, "=", adj.get(g.leaf("z", i).id, g.const(0.0))) for i in range(M)]
 
     names = ", ".join('"%s"' % n for n in P)
     key = cls.model_key
@@ -1464,9 +1630,12 @@ def generate_source(cls, neural=False):
         adj = vjp(g, outs, [g.leaf("seed", j) for j in range(h.count(N))])
         if h.switch_note:
             hook_decl.append("  static constexpr bool %s = true;  // %s" % (h.switch, h.switch_note))
-        hook_decl += h.c_forward + [body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in enumerate(outs)], True, h.seed, tr.c_slot,
-                                         f_at_point), "  }"]
-        hook_decl += h.c_adjoint + [body(pull(adj, h.targets), True, h.seed, tr.c_slot, f_at_point), "  }"]
+        with_z = reads_z(outs)  # (observe alone may: a class without algebraic variables emits what it emitted before)
+        hook_decl += h.c_forward + (solve_z(f_at_point) if with_z else []) + [
+            body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in enumerate(outs)], True, h.seed, tr.c_slot, f_at_point), "  }"]
+        hook_decl += h.c_adjoint + (solve_z(f_at_point) + ["    float zb[%d];" % M] if with_z else []) + [
+            body(pull(adj, h.targets) + (pull_z(adj) if with_z else []), True, h.seed, tr.c_slot, f_at_point)] + (
+            ["    algebraic_vjp(y, z, p, u, zb, yb, pb);"] if with_z else []) + ["  }"]
     forcing_decl = []
     if K:
         forcing_decl = [
@@ -1501,6 +1670,53 @@ def generate_source(cls, neural=False):
                     body([("J[%d]" % (i * N + j), "=", J[i][j]) for i, j in nz], True, "v", tr.c_slot, f_at_t)]
         jac_decl += ["    J[%d] = 0.f;" % (i * N + j) for i in range(N) for j in range(N) if (i, j) not in nz]
         jac_decl += ["  }"]
+    # algebraic variables: the constants, the three traced members (time-loop helpers, like rhs), the constraint's adjoint
+    # product and the two members every reader calls; rhs / rhs_vjp open with the solve where rhs reads an unknown
+    algebraic_decl, rhs_open, vjp_open, vjp_pull, vjp_close = [], [], [], [], []
+    if M:
+        A = constraint_jacobian_nodes(cls)
+        anz = [(i, j) for i in range(M) for j in range(M) if not _is_const(A[i][j], 0.0)]
+        u_names = ["u[%d]" % k for k in range(K)]
+        zargs = "const float* y, const float* z, const float* p, const float* u"
+        cadj = vjp(g, tr.con, [g.leaf("seed", i) for i in range(M)])
+        algebraic_decl = [
+            "  static constexpr int N_ALGEBRAIC = %d;  // %s: the unknowns z of constraint(y, z, p) = 0 (vihds_algebraic.hpp)" % (
+                M, ", ".join(tr.algebraic)),
+            "  static constexpr int ALG_ITER = %d;  // Newton iterations from algebraic_start, a fixed count" % int(cls.algebraic_iterations),
+            "  static constexpr unsigned ALG_NZ = 0x%xu;  // structural non-zeros of constraint_jac, bit i * N_ALGEBRAIC + j: %d of %d" % (
+                sum(1 << (i * M + j) for i, j in anz), len(anz), M * M),
+            "  // u: the forcings' values where the caller is evaluated (rhs: the interpolant at t; observe: the point's sample)",
+            "  __device__ static void algebraic_start(const float* y, const float* p, const float* u, float* z) {",
+            body([("z[%d]" % i, "=", e) for i, e in enumerate(tr.z0)], True, "v", tr.c_slot, u_names),
+            "  }",
+            "  __device__ static void constraint(%s, float* G) {" % zargs,
+            body([("G[%d]" % i, "=", e) for i, e in enumerate(tr.con)], True, "v", tr.c_slot, u_names),
+            "  }",
+            "  // A[i * N_ALGEBRAIC + j] = d G[i] / d z[j]; a structural zero is not written (and not read by the solve)",
+            "  __device__ static void constraint_jac(%s, float* A) {" % zargs,
+            body([("A[%d]" % (i * M + j), "=", A[i][j]) for i, j in anz], True, "v", tr.c_slot, u_names),
+            "  }",
+            "  // yb, pb += v^T dG/dy, v^T dG/dp (the adjoint passes v = -mu)",
+            "  __device__ static void constraint_vjp(%s, const float* v, float* yb, float* pb) {" % zargs,
+            body(pull(cadj, [("y", "yb"), ("p", "pb")]), True, "v", tr.c_slot, u_names),
+            "  }",
+            "  __device__ static void algebraic(const float* y, const float* p, const float* u, float* z) {",
+            "    algebraic_start(y, p, u, z);",
+            "    algebraic_newton<N_ALGEBRAIC, ALG_ITER, ALG_NZ>(",
+            "        z, [&](const float* s, float* G) { constraint(y, s, p, u, G); },",
+            "        [&](const float* s, float* A) { constraint_jac(y, s, p, u, A); });",
+            "  }",
+            "  // zb: the adjoint of z from the reader's reverse mode; A^T mu = zb at the final z, then the constraint's product with -mu",
+            "  __device__ static void algebraic_vjp(%s, float* zb, float* yb, float* pb) {" % zargs,
+            "    algebraic_adjoint<N_ALGEBRAIC, ALG_NZ>(zb, [&](float* A) { constraint_jac(y, z, p, u, A); });",
+            "    constraint_vjp(y, z, p, u, zb, yb, pb);",
+            "  }",
+        ]
+        if reads_z(tr.dy):
+            rhs_open = solve_z(f_at_t)
+            vjp_open = rhs_open + ["    float zb[%d];" % M]
+            vjp_pull = pull_z(adj1)
+            vjp_close = ["    algebraic_vjp(y, z, p, u, zb, yb, pb);"]
     # substeps = m > 1: the one line the kernels' time loops read (vihds_models.hpp substeps<>); a class without it generates
     # the text it generated before
     substeps_decl = ["  static constexpr int SUBSTEPS = %d;" % int(cls.substeps)] if cls.substeps > 1 else []
@@ -1524,7 +1740,7 @@ def generate_source(cls, neural=False):
         "  static constexpr int OBS = %s;" % obs_enum,
         "  static constexpr int NSLOT = %d;" % len(P),
         "  static constexpr int NP = %d;" % (max(tr.NP, 1) if not K else tr.NP + 2 * K + 1),
-    ] + substeps_decl + implicit_decl + forcing_decl + net_decl + [
+    ] + substeps_decl + implicit_decl + forcing_decl + net_decl + algebraic_decl + [
         "  __host__ static const char* slot_name(int s) {",
         "    static const char* n[] = {%s};" % names,
         "    return n[s];",
@@ -1541,11 +1757,12 @@ def generate_source(cls, neural=False):
         "  __device__ static void init_vjp(const float* yb, float* thb) {",
         body(init_vjp, False, "yb"),
         "  }",
-    ] + rhs_sig + [
+    ] + rhs_sig + rhs_open + [
         body(rhs, True, "v", tr.c_slot, f_at_t),
         "  }",
-    ] + vjp_sig + [
-        body(rhs_vjp, True, "v", tr.c_slot, f_at_t),
+    ] + vjp_sig + vjp_open + [
+        body(rhs_vjp + vjp_pull, True, "v", tr.c_slot, f_at_t),
+    ] + vjp_close + [
         "  }",
     ] + jac_decl + hook_decl + [
         "};",
@@ -1652,6 +1869,8 @@ def register_kernel(cls, neural=False):
     if cls.implicit:  # (the library holds the kernels of the implicit solvers)
         hip.GENERATED_IMPLICIT.add(key)
         hip.GENERATED_IMPLICIT_ORDER[key] = int(cls.implicit_order)
+    if cls._trace.algebraic:  # (unknowns of a constraint, solved inside the struct's rhs and observe)
+        hip.GENERATED_ALGEBRAIC[key] = len(cls._trace.algebraic)
     hip.GENERATED_SUBSTEPS[key] = int(cls.substeps)  # (above 1: the library holds the fixed-grid schemes only)
     if cls._trace.jmp is not None:  # (a state jump at the observation points: the fixed-grid schemes only, likewise)
         hip.GENERATED_JUMP.add(key)
@@ -1668,7 +1887,12 @@ def register_kernel(cls, neural=False):
 # ---------------------------------------------------------------------------------------------------------------------
 class GeneratedOdeModel(OdeModel):
     """Base class of models defined in Python (module docstring).  A subclass that sets `model_key` is traced when the
-    class is defined: errors in the definition and the kernels' limits are reported there, not inside a launch."""
+    class is defined: errors in the definition and the kernels' limits are reported there, not inside a launch.
+
+    A class with `algebraic` variables keeps the totals of a fast reaction as species and defines the unknowns by
+    constraint(self, y, z, p, c) == 0, solved by algebraic_iterations Newton steps from algebraic_start(self, y, p, c) wherever
+    rhs and observe are evaluated; the adjoint is the implicit-function theorem's at the final iterate (module docstring,
+    "Algebraic variables"; torch_algebraic restates the solve on the host)."""
 
     species = None
     parameter_names = None
@@ -1684,6 +1908,10 @@ class GeneratedOdeModel(OdeModel):
     substeps = 1  # steps a fixed-grid solver takes over each observation interval, 1 .. MAX_SUBSTEPS (module docstring)
     lead_in = 0.0  # L > 0: the length of an unscored phase before the first observation point, in the units of `times`
     lead_in_steps = 1  # steps a fixed-grid solver takes over the lead-in phase, 1 .. MAX_LEAD_IN_STEPS (module docstring)
+    algebraic = ()  # names of the algebraic variables, read as self.algebraic.<name> in rhs and observe (module docstring)
+    algebraic_iterations = 6  # Newton iterations on the constraint, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
+    constraint = None  # constraint(self, y, z, p, c) -> one residual per algebraic variable; z solves constraint(...) == 0
+    algebraic_start = None  # algebraic_start(self, y, p, c) -> the iteration's starting value, one entry per algebraic variable
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -1718,6 +1946,8 @@ class GeneratedOdeModel(OdeModel):
             return
         _validate(cls)
         cls._trace = Trace(cls)
+        if cls._trace.algebraic:
+            _check_constraint_pattern(cls)
         generate_source(cls)  # (the checks that need the adjoints: an initial state the kernels can differentiate)
 
     def __init__(self, config):
@@ -1937,6 +2167,8 @@ class GeneratedOdeModel(OdeModel):
             object.__setattr__(inst, "forcing", _Forcings(cls, lambda k, name: now["u"][k] if now else no_forcing(k, name)))
         thn = _Named([(n, th[n]) for n in cls.parameter_names], "parameter")
         full = lambda v: v if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
+        unknowns = _class_algebraic(cls)
+        object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda _i, name: _algebraic_misread(name, "prepare, initial_state or start")))
         p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
         x0 = torch.stack([full(v) for v in inst.initial_state(thn, _Conditions(cs))], dim=2)
         if start and cls._start_def is not None:  # (the state the integration starts from)
@@ -1951,6 +2183,9 @@ class GeneratedOdeModel(OdeModel):
                 k = min(max(k, 0), tg.shape[0] - 2)
                 u = series[:, :, k] + (tt - tg[k]) * (series[:, :, k + 1] - series[:, :, k]) / (tg[k + 1] - tg[k])
                 now["u"] = [u[:, j, None].expand(B, S) for j in range(len(names))]
+            if unknowns:  # the constraint's solution at this stage state, carrying the implicit-function gradient
+                z, _ = _algebraic_torch(cls, inst, y, p, _Conditions(cs))
+                object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda i, _name: z[i]))
             return torch.stack([full(v) for v in inst.rhs(t, y, p, _Conditions(cs))], dim=2)
 
         return rhs, x0
@@ -1997,6 +2232,52 @@ class GeneratedOdeModel(OdeModel):
             raise ModelDefinitionError("%s defines no observe(self, y, p, c): its map is the fixed kind '%s'"
                                        % (cls.__name__, cls.observe_kind))
         return _hook_torch(cls, HOOK["observe"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond)
+
+    @classmethod
+    def torch_algebraic(cls, y, theta, cond, forcing=None, return_increment=False):
+        """The algebraic variables at the states y with torch ops in y's dtype, by the iteration the kernels run (module
+        docstring): z = algebraic_start(y, p); algebraic_iterations times G = g(y, z, p), A = dg/dz by autograd, A d = -G by
+        torch.linalg.solve (pivoted), z += d.  y [B,S,N] species, theta {parameter name: [B,S]} -- prepare is applied to it
+        first --, cond [B,C] as the data holds it, forcing: the K values the constraint reads there (tensors that broadcast to
+        [B,S]) for a class with forcings -> z [B,S,M].  The value is the iterate's; its gradient is the implicit-function
+        derivative of the converged solution, z_K.detach() - (s - s.detach()) with s = solve(A(z_K).detach(), g(y, z_K.detach(),
+        p)): nothing is differentiated through the iteration.  return_increment: (z, the largest last Newton increment relative
+        to the largest |z| of its trajectory) -- what says whether the iteration has converged."""
+        if not _class_algebraic(cls):
+            raise ModelDefinitionError("%s declares no algebraic variables" % cls.__name__)
+        inst = cls.__new__(cls)
+        ref = y[:, :, 0]
+        cs = _treatments_torch(cls, cond, ref, ref.shape[1])
+        thn = _Named([(n, theta[n].to(ref.dtype)) for n in cls.parameter_names], "parameter")
+        p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
+        names = _class_forcings(cls)
+        if names:
+            if forcing is None or len(forcing) != len(names):
+                raise ValueError("%s.torch_algebraic needs forcing=[%s]: the values of the class's forcings at the states"
+                                 % (cls.__name__, ", ".join(names)))
+            object.__setattr__(inst, "forcing", _Forcings(cls, lambda k, _name: forcing[k]))
+        z, last = _algebraic_torch(cls, inst, list(torch.unbind(y[:, :, :len(cls.species)], dim=2)), p, _Conditions(cs))
+        z = torch.stack([v.expand_as(ref) for v in z], dim=2)
+        return (z, last) if return_increment else z
+
+    @classmethod
+    def torch_constraint_jacobian(cls, y, z, theta, cond, forcing=None):
+        """The generated dg/dz evaluated with torch ops in y's dtype -- the SAME DAG nodes constraint_jac is emitted from
+        (constraint_jacobian_nodes), not autograd: it exists to check the generator against autograd of the class's constraint.
+        y [B,S,N], z [B,S,M], theta, cond and forcing as torch_algebraic takes them -> [B,S,M,M], entry [i][j] = d g_i / d z_j."""
+        tr = cls._trace
+        N, M, NPU = len(cls.species), len(tr.algebraic), len(tr.p_names)
+        ref = y[:, :, 0]
+        cs = _treatments_torch(cls, cond, ref, ref.shape[1])
+        env = {("th", s): theta[n].to(ref.dtype) for s, n in enumerate(cls.parameter_names)}
+        env.update({("c", q): v for q, v in enumerate(cs)})
+        env.update({("p", k): v.to(ref.dtype) for k, v in enumerate(evaluate(tr.p_exprs, env))})
+        env.update({("p", NPU + q): v for q, v in enumerate(cs)})
+        env.update({("y", j): y[:, :, j] for j in range(N)})
+        env.update({("z", i): z[:, :, i] for i in range(M)})
+        env.update({("f", k): v for k, v in enumerate(forcing or ())})
+        flat = evaluate([e for row in constraint_jacobian_nodes(cls) for e in row], env)
+        return torch.stack([v.to(ref.dtype).expand_as(ref) for v in flat], dim=2).reshape(ref.shape + (M, M))
 
     @classmethod
     def torch_precision(cls, y, theta, cond):
@@ -2130,6 +2411,46 @@ def _forcing_series(cls, cond, like, n_times):
     return cond[:, cond.shape[1] - K * n_times:].to(like.dtype).to(like.device).reshape(cond.shape[0], K, n_times)
 
 
+def _algebraic_torch(cls, inst, y, p, cs):
+    """(the M algebraic variables, the largest last Newton increment relative to the trajectory's largest |z|) of the class's
+    constraint at the species y (a list of N tensors that broadcast together), by the iteration as the module docstring defines
+    it; p the effective parameters, cs the treatments, inst.forcing the forcings' values there.  Each returned tensor has the
+    iterate's value and the implicit-function gradient with respect to y, p (GeneratedOdeModel.torch_algebraic)."""
+    M = len(_class_algebraic(cls))
+    like = torch.broadcast_tensors(*[v for v in y if isinstance(v, torch.Tensor)])[0]
+    full = lambda v: v if isinstance(v, torch.Tensor) else torch.full_like(like, float(v))  # noqa: E731
+    stack = lambda vs: torch.stack(torch.broadcast_tensors(*[full(v) for v in vs]), dim=-1)  # noqa: E731
+    residual = lambda zz: stack(inst.constraint(y, list(torch.unbind(zz, dim=-1)), p, cs))  # noqa: E731
+
+    def linearised(zz):
+        with torch.enable_grad():
+            zz = zz.detach().requires_grad_(True)
+            G = residual(zz)
+            G = G.expand(torch.broadcast_shapes(G.shape, zz.shape))
+            rows = []
+            for i in range(M):
+                gi = G[..., i].sum()
+                row = torch.autograd.grad(gi, zz, retain_graph=True, allow_unused=True)[0] if gi.requires_grad else None
+                rows.append(torch.zeros_like(zz) if row is None else row)
+        return torch.stack(rows, dim=-2).detach(), G.detach()
+
+    out = inst.algebraic_start(y, p, cs)
+    if not isinstance(out, (list, tuple)) or len(out) != M:
+        raise ModelDefinitionError("%s.algebraic_start must return a list of %d entries" % (cls.__name__, M))
+    z = stack(out).detach()
+    z = z.expand(torch.broadcast_shapes(z.shape, residual(z).shape)).to(like.dtype)
+    d = torch.zeros_like(z)
+    for _ in range(int(cls.algebraic_iterations)):
+        A, G = linearised(z)
+        d = torch.linalg.solve(A, -G.unsqueeze(-1)).squeeze(-1)
+        z = z + d
+    last = float((d.abs().amax(-1) / z.abs().amax(-1).clamp_min(1e-30)).max()) if bool(torch.isfinite(d).all()) else float("inf")
+    if torch.is_grad_enabled():
+        s = torch.linalg.solve(linearised(z)[0], residual(z).unsqueeze(-1)).squeeze(-1)
+        z = z - (s - s.detach())
+    return list(torch.unbind(z, dim=-1)), last
+
+
 def _hook_torch(cls, h, inst, groups, th, cond):
     """The class's definition of hook h with torch ops in the dtype of its first group: groups of [B,S,.,T] tensors (in
     the hook's order), th {parameter name: [B,S]} -- prepare is applied to it -- and cond [B,C] -> [B,S,4,T] (the hook's
@@ -2142,6 +2463,12 @@ def _hook_torch(cls, h, inst, groups, th, cond):
     if _class_forcings(cls):  # the samples of every time point, [B,1,T] each
         series = _forcing_series(cls, cond, ref, ref.shape[-1])
         object.__setattr__(inst, "forcing", _Forcings(cls, lambda k, _name: series[:, k, None, :]))
+    if _class_algebraic(cls):
+        if h.name in _ALGEBRAIC_READERS:  # (observe: the constraint's solution at every time point's state)
+            z, _ = _algebraic_torch(cls, inst, list(torch.unbind(groups[0], dim=2)), p, _Conditions([over_time(v) for v in cs]))
+            object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda i, _name: z[i]))
+        else:
+            object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda _i, name: _algebraic_misread(name, h.name)))
     out = getattr(cls, h.attr)(inst, *[list(torch.unbind(v, dim=2)) for v in groups], p, _Conditions([over_time(v) for v in cs]))
     full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
     return torch.stack([full(v) for v in out], dim=2)
@@ -2190,6 +2517,43 @@ def _validate(cls):
         raise ModelDefinitionError("%s: %d forcings; a generated model reads at most %d (MAX_FORCINGS)"
                                    % (name, len(forc), MAX_FORCINGS))
     nets = getattr(cls, "networks", None)
+    alg = getattr(cls, "algebraic", None) or ()
+    if not isinstance(alg, (list, tuple)) or not all(isinstance(a, str) and a.isidentifier() for a in alg):
+        raise ModelDefinitionError("%s.algebraic must be a list of names (valid identifiers)" % name)
+    if alg:
+        if len(set(alg)) != len(alg):
+            raise ModelDefinitionError("%s.algebraic has duplicates" % name)
+        clash = [a for a in alg if a in cls.species or a in cls.parameter_names or a in forc]
+        if clash:
+            raise ModelDefinitionError("%s.algebraic: %s %s also a species, a parameter or a forcing; an algebraic variable "
+                                       "needs a name of its own" % (name, ", ".join("'%s'" % a for a in clash),
+                                                                    "is" if len(clash) == 1 else "are"))
+        if len(alg) > MAX_ALGEBRAIC:
+            raise ModelDefinitionError("%s: %d algebraic variables; the matrix of a Newton step on the constraint lives in "
+                                       "registers: at most %d (MAX_ALGEBRAIC)" % (name, len(alg), MAX_ALGEBRAIC))
+        for what, sig, n_args in (("constraint", "constraint(self, y, z, p, c)", 5),
+                                  ("algebraic_start", "algebraic_start(self, y, p, c)", 4)):
+            fn = getattr(cls, what, None)
+            if fn is None:
+                raise ModelDefinitionError("%s declares algebraic variables without %s: the unknowns are defined by "
+                                           "constraint(self, y, z, p, c) == 0 and the iteration starts from "
+                                           "algebraic_start(self, y, p, c)" % (name, what))
+            required = [q for q in inspect.signature(fn).parameters.values()
+                        if q.default is q.empty and q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD)] if callable(fn) else []
+            if len(required) != n_args:
+                raise ModelDefinitionError("%s.%s must be a function %s: it sees the species, the effective parameters and the "
+                                           "treatments -- no t" % (name, what, sig))
+        it = cls.algebraic_iterations
+        if isinstance(it, (bool, np.bool_)) or not isinstance(it, (int, np.integer)) or not 1 <= it <= MAX_NEWTON_ITERATIONS:
+            raise ModelDefinitionError("%s.algebraic_iterations = %r; the constraint is solved by a fixed number of Newton "
+                                       "iterations, 1 .. %d" % (name, it, MAX_NEWTON_ITERATIONS))
+        if cls.implicit:
+            raise ModelDefinitionError("%s has algebraic variables and implicit = True: the Jacobian of the reduced system, "
+                                       "f_y - f_z g_z^-1 g_y, is not generated (an algebraic model takes the explicit solvers)" % name)
+        if nets:
+            raise ModelDefinitionError("%s has algebraic variables and networks: the adjoint repeats the value pass of rhs, and "
+                                       "the dump of a network holds one evaluation per stage (algebraic variables are for models "
+                                       "without networks)" % name)
     if not isinstance(cls.implicit, (bool, np.bool_)):
         raise ModelDefinitionError("%s.implicit must be True or False" % name)
     order = cls.implicit_order
