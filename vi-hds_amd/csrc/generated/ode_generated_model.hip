@@ -38,6 +38,13 @@ static_assert(!(lead_in<VIHDS_GEN_CORE>::value > 0 && net_fields<VIHDS_GEN_CORE>
               "a model with a lead-in phase takes no networks: the adjoint's dump holds (T-1) x stages evaluations");
 static_assert(lead_in<VIHDS_GEN_CORE>::value >= 0 && lead_in<VIHDS_GEN_CORE>::value <= kMaxLeadInSteps,
               "lead_in_steps: 1 .. 8 (vihds_substeps.hpp)");
+static_assert(!(VIHDS_GEN_NEURAL != 0 && n_delays<VIHDS_GEN_CORE>::value > 0),
+              "a model with delayed reads does not take NeuralPrecisions: WithPrec<> forwards neither N_DELAYS nor set_delay");
+static_assert(!(n_delays<VIHDS_GEN_CORE>::value > 0 &&
+                (has_jacobian<VIHDS_GEN_CORE>::value || substeps<VIHDS_GEN_CORE>::value > 1 || has_jump<VIHDS_GEN_CORE>::value ||
+                 lead_in<VIHDS_GEN_CORE>::value > 0 || net_fields<VIHDS_GEN_CORE>::value > 0)),
+              "delayed reads combine with the explicit fixed-grid schemes only: no implicit, substeps, jump, lead_in or networks");
+static_assert(n_delays<VIHDS_GEN_CORE>::value >= 0 && n_delays<VIHDS_GEN_CORE>::value <= 4, "delays: at most 4");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
@@ -87,7 +94,8 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
                                    slot_names_gen(), n_weights_gen, launch_gen, VIHDS_GEN_CORE::NW,
                                    net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
                                    n_forcings<GenM>::value, implicit_order<GenM>::value, substeps<GenM>::value,
-                                   has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value};
+                                   has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value,
+                                   n_delays<GenM>::value};
   return &r;
 }
 #endif

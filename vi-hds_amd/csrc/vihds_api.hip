@@ -123,6 +123,9 @@ struct ModelEntry {
   // 0: none): either takes no adaptive solver
   bool start = false;
   int lead_in_steps = 0;
+  // a registered model with delayed reads (GenModelRecord::n_delays): its forward needs the trajectory buffer, its adjoint a
+  // history workspace of n_delays * T * B * S floats in aux, and it takes no adaptive solver
+  int n_delays = 0;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
   bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
   int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
@@ -178,7 +181,7 @@ static std::atomic<int> g_gen_count{0};
 static ModelEntry gen_entry_of(const GenModelRecord* r) {
   return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
           r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps, r->jump != 0,
-          r->start != 0, r->lead_in_steps};
+          r->start != 0, r->lead_in_steps, r->n_delays};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -391,7 +394,9 @@ int vihds_model_register(const char* library_path) {
       (r->substeps > 1 && (r->neural_prec || r->n_net_weights > 0)) || (r->jump != 0 && r->jump != 1) ||
       (r->jump && r->neural_prec) || (r->start != 0 && r->start != 1) || r->lead_in_steps < 0 ||
       r->lead_in_steps > kMaxLeadInSteps || ((r->start || r->lead_in_steps) && r->neural_prec) ||
-      (r->lead_in_steps && r->n_net_weights > 0)) {
+      (r->lead_in_steps && r->n_net_weights > 0) || r->n_delays < 0 || r->n_delays > 4 ||
+      (r->n_delays > 0 && (r->neural_prec || r->n_net_weights > 0 || r->implicit || r->substeps > 1 || r->jump ||
+                           r->lead_in_steps))) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
   }
@@ -528,6 +533,8 @@ long long vihds_ode_bwd_aux_floats(const vihds_ode_problem* p) {
   }
   const ModelEntry* e = entry(p->model);
   if (!e) return VIHDS_E_UNSUPPORTED;
+  // (a registered model with delayed reads: the history adjoint A[entry][T][n], one column per trajectory -- no weights, no dump)
+  if (e->n_delays > 0) return (long long)e->n_delays * p->T * p->B * p->S;
   if (!e->has_weights()) return 0;
   if (vihds_ode_bwd_reduces_weights(p)) return relay_lanes_aux_floats(p->B * p->S, e->lane_species);  // one partial row per block
   // white-box + neural precisions: [8 + NIN][E][n], NIN = 1 + core states (optional: see vihds_ode_bwd)
@@ -591,6 +598,8 @@ int vihds_ode_fwd(const vihds_ode_problem* p, const float* theta, const float* c
   if (p->C > 0 && !cond) return fail(VIHDS_E_BADARG, "null cond");
   set_inputs(a, theta, cond, dev1hot, times, obs, weights);
   a.traj = traj; a.xpred = xpred; a.logp = logp;
+  if (e->n_delays > 0 && !traj)
+    return fail(VIHDS_E_BADARG, "a model with delayed reads looks its history up in the trajectory buffer: pass traj");
   rc = launcher_of(e, bb)(false, p->solver, a, (hipStream_t)stream, LaunchMode{});
   if (rc) return fail(rc, "unknown solver");
   return check_hip("vihds_ode_fwd launch");
@@ -828,6 +837,8 @@ static int ode_bwd(const char* launch_name, const vihds_ode_problem* p, const fl
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && !aux) return fail(VIHDS_E_BADARG, "dr_blackbox backward needs the aux buffer");
   if (e->n_net_weights > 0 && g_weights && !aux)
     return fail(VIHDS_E_BADARG, "a generated model with networks forms its weight gradient from the aux dump: pass aux (vihds_ode_bwd_aux_floats)");
+  if (e->n_delays > 0 && !aux)
+    return fail(VIHDS_E_BADARG, "a model with delayed reads keeps its history adjoint in aux: pass aux (vihds_ode_bwd_aux_floats)");
   a.traj_in = traj; a.g_traj = g.g_traj; a.g_xpred = g.g_xpred; a.g_logp = g.g_logp; a.g_theta = g_theta;
   a.iw_logp = g.iw_logp; a.iw_log_p = g.iw_log_p; a.iw_log_q = g.iw_log_q;
   if (elbo) a.logp_grad_broadcast = 1;

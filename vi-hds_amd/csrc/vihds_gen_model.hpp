@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "vihds_algebraic.hpp"  // a generated struct with algebraic variables calls its templates from rhs and observe
+#include "vihds_delay.hpp"      // the lookups of a generated struct with delayed reads (the time loops call them)
 #include "vihds_args.hpp"
 
 // registered models take ids from here on (far above the built-in enum vihds_model)
@@ -62,6 +63,10 @@ struct GenModelRecord {
   // steps of the lead-in phase before the first observation point (vihds_models.hpp lead_in<>: 0 for none, else 1 ..
   // kMaxLeadInSteps); above 0 the fixed-grid solvers only, likewise
   int lead_in_steps;
+  // delayed reads of the generated struct (vihds_models.hpp n_delays<>, 0 .. 4): the forward launch needs the trajectory buffer
+  // (it reads back what the same thread stored), the adjoint n_delays * T * B * S floats of aux for its history adjoint
+  // (vihds_ode_bwd_aux_floats); the fixed-grid solvers only
+  int n_delays;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

@@ -971,6 +971,23 @@ struct n_forcings<M, std::void_t<decltype(M::N_FORCINGS)>> {
   static constexpr int value = M::N_FORCINGS;
 };
 
+// A core generated with delayed reads (delays, vihds/modelgen.py; vihds_delay.hpp has the definition) declares N_DELAYS = E > 0
+// and reserves 2 E + 1 entries of p from DELAY_SLOT on, behind the forcings': per read a value and a slope, and one interval
+// start.  rhs reads entry e at stage time t as value + (t - start) * slope, and -- unlike a forcing -- rhs_vjp adds the read's
+// adjoint to pb of the value and the slope entry.  delay_species(e) / delay_param(e) say which species is read and which entry
+// of p holds the delay; set_delay(p, t_lo, inv_dt, d_lo, d_hi), called by the time loops ahead of every step, writes the
+// entries from the two lookups (nothing else does: prepare leaves them alone, prepare_vjp does not read their pb entries, the
+// adjoint's time loop takes and clears them after every step).  0 for every hand-written model; WithPrec<> does not forward it
+// (a generated model with delays takes no NeuralPrecisions).
+template <class M, class = void>
+struct n_delays {
+  static constexpr int value = 0;
+};
+template <class M>
+struct n_delays<M, std::void_t<decltype(M::N_DELAYS)>> {
+  static constexpr int value = M::N_DELAYS;
+};
+
 // A core generated with `implicit = True` (vihds/modelgen.py) declares NEWTON (the Newton iterations of one implicit step),
 // JAC_NZ (the structural non-zeros of its Jacobian, bit i N + j) and one more member of the time loop:
 //   rhs_jac(t, y, p, wg, J)     J[i N + j] = d dy_i / d y_j at (t, y), the forcings read as rhs reads them

@@ -21,6 +21,7 @@
 #include "vihds_models.hpp"
 #include "vihds_rk_adaptive.hpp"
 #include "vihds_implicit.hpp"
+#include "vihds_delay.hpp"
 #include "vihds_substeps.hpp"
 #include "vihds_blackbox.hpp"
 #include "vihds_iwae_inline.hpp"
@@ -570,6 +571,17 @@ struct WithNextState : Feed {
 };
 template <int NF, int N, bool IMPLICIT>
 using bwd_feed_t = std::conditional_t<IMPLICIT, WithNextState<ForcingFeed<NF>, N>, ForcingFeed<NF>>;
+// what the time loops keep for a model with delayed reads (n_delays<M> = ND > 0, vihds_delay.hpp) beside their feed: per read
+// the stored state of its species at t_0 (the constant history) and the search cursor, the index of s_lo's interval, which
+// climbs in the forward and descends in the adjoint.  Every other model's loop declares the feed alone, as it did
+// (delay_feed_t), so its code is what it was.
+template <class Feed, int ND>
+struct WithDelayState : Feed {
+  float y0[ND];
+  int cur[ND];
+};
+template <class Feed, int ND>
+using delay_feed_t = std::conditional_t<(ND > 0), WithDelayState<Feed, ND>, Feed>;
 // ---- forward -------------------------------------------------------------------------------------
 // LDS_IN: the time grid and the observation rows of the data rows this block spans are staged in LDS once, so the
 // time loop holds no vector-memory loads and its trajectory / x_predict stores are never waited on (see
@@ -581,11 +593,12 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   constexpr bool OWN_PREC = own_prec<M>::value;
   constexpr bool OWN_LIK = own_lik<M>::value;  // the log density is the model's own member (vihds_models.hpp)
   constexpr int NF = n_forcings<M>::value;     // forcings: K series of T samples per data row behind its treatments in cond
+  constexpr int ND = n_delays<M>::value;       // delayed reads: looked up in the rows of traj this thread stored earlier
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations | [nb][NF][T] forcing samples
   const float* wts = stage_weights<M>(a, wlds);
   int ob_off = 0;
-  ForcingFeed<NF> ff;
+  delay_feed_t<ForcingFeed<NF>, ND> ff;  // (ForcingFeed<NF>; a model with delayed reads also keeps y_0 and its cursors)
   if (LDS_IN) {
     const int first = blockIdx.x * blockDim.x, last = min(first + (int)blockDim.x, a.n) - 1;
     const int b0 = first / a.S, nb = last / a.S - b0 + 1;
@@ -662,6 +675,12 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
       ode_lead_in<M, SOLVER>(tA, y, p, wts);
     }
   }
+  if constexpr (ND > 0) {  // the history before t_0 is the state stored at t_0 (after start, where the model has one)
+    VIHDS_UNROLL for (int e = 0; e < ND; ++e) {
+      ff.y0[e] = y[M::delay_species(e)];
+      ff.cur[e] = 0;
+    }
+  }
   for (int k = 0; k < a.T; ++k) {
     const float tC = (k + 1 < a.T) ? time_at(k + 1) : tB;
     if (a.logp && k + 1 < a.T) {
@@ -675,6 +694,22 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     }
     if (k > 0) {
       if constexpr (NF > 0) M::set_interval(p, tA, 1.f / (tB - tA), ff.lo, ff.hi);
+      if constexpr (ND > 0) {
+        // delayed reads of the interval k - 1 = [tA, tB]: the two lookups per read into the points 0 .. k - 1, which this
+        // thread stored in its earlier iterations (vihds_delay.hpp: the indices are clamped into that range before any load)
+        float d_lo[ND], d_hi[ND];
+        const float t0 = time_at(0);
+        VIHDS_UNROLL for (int e = 0; e < ND; ++e) {
+          const float tau = p[M::delay_param(e)];
+          auto y_at = [&](int q) { return a.traj[((size_t)q * NT + M::delay_species(e)) * n + i]; };
+          const DelayEnds en = delay_ends(tA, tB, tau);
+          ff.cur[e] = delay_seek_up(time_at, ff.cur[e], k - 1, en.s_lo);
+          d_lo[e] = delay_lookup(time_at, y_at, ff.cur[e], en.s_lo, t0, ff.y0[e], tau).value;
+          const int jh = delay_seek_up(time_at, ff.cur[e], k - 1, en.s_hi);
+          d_hi[e] = delay_lookup(time_at, y_at, jh, en.s_hi, t0, ff.y0[e], tau).value;
+        }
+        M::set_delay(p, tA, 1.f / (tB - tA), d_lo, d_hi);
+      }
       if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts);  // (one interval, several steps)
       else ode_step<M, SOLVER>(tA, tB, h0, y, p, wts);
       tA = tB;
@@ -931,6 +966,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   constexpr bool OWN_PREC = own_prec<M>::value;
   constexpr bool OWN_LIK = own_lik<M>::value;  // the log density's adjoint is the model's own member (vihds_models.hpp)
   constexpr int NF = n_forcings<M>::value;     // forcings: K series of T samples per data row behind its treatments in cond
+  constexpr int ND = n_delays<M>::value;       // delayed reads: looked up in traj_in, their adjoint scattered into aux
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   const float* wts = stage_weights<M>(a, wlds);
   const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -970,7 +1006,19 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   float tHi = a.times[a.T - 1], tLo = tHi;
   // forcing samples travel with the times: ff.hi at tHi, ff.lo at tK, the next lower point's (ff.ahead) requested one
   // iteration ahead like tLo
-  bwd_feed_t<NF, N, solver_is_implicit(SOLVER)> ff;  // (ForcingFeed<NF>; an implicit solver's also keeps y_k+1)
+  // (ForcingFeed<NF>; an implicit solver's also keeps y_k+1, a model with delayed reads y_0 and its cursors)
+  delay_feed_t<bwd_feed_t<NF, N, solver_is_implicit(SOLVER)>, ND> ff;
+  if constexpr (ND > 0) {
+    // the history adjoint A[entry][T] of this trajectory: its own column of aux, zeroed here and touched by no other thread
+    // (a tail lane shadows the last trajectory: it reads that column and never writes it)
+    VIHDS_UNROLL for (int e = 0; e < ND; ++e) {
+      ff.y0[e] = a.traj_in[(size_t)M::delay_species(e) * n + i];
+      ff.cur[e] = a.T - 2;
+      if (live) {
+        for (int q = 0; q < a.T; ++q) a.aux[((size_t)e * a.T + q) * n + i] = 0.f;
+      }
+    }
+  }
   if constexpr (NF > 0) {
     ff.src = a.cond + (size_t)b * a.C + (a.C - NF * a.T);
     VIHDS_UNROLL for (int j = 0; j < NF; ++j) { ff.ahead[j] = ff.src[j * a.T + a.T - 1]; ff.hi[j] = ff.ahead[j]; }
@@ -994,7 +1042,42 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     if constexpr (NF > 0) {  // the interval (k, k + 1) ...
       if (k < a.T - 1) M::set_interval(p, tK, 1.f / (tHi - tK), ff.lo, ff.hi);
     }
-    if constexpr (has_jump<M>::value) {
+    if constexpr (ND > 0) {
+      // delayed reads (a branch of its own: every other model's code stays what it was; such a model has no jump, sub-steps
+      // or implicit scheme).  The interval k = [tK, tHi] repeats the forward's two lookups per read on the forward's operands
+      // (the same bits), runs the step adjoint, then takes and clears the read's value and slope adjoints and scatters them
+      // into the history adjoint at the points the lookups read -- which may be the point k itself: A[.][k] joins lam below
+      if (k < a.T - 1) {
+        float d_lo[ND], d_hi[ND];
+        DelayHit lo[ND], hi[ND];
+        bool moves[ND];
+        const float t0 = a.times[0], inv_dt = 1.f / (tHi - tK);
+        auto time_at = [&](int q) { return a.times[q]; };
+        VIHDS_UNROLL for (int e = 0; e < ND; ++e) {
+          const float tau = p[M::delay_param(e)];
+          auto y_at = [&](int q) { return a.traj_in[((size_t)q * NT + M::delay_species(e)) * n + i]; };
+          const DelayEnds en = delay_ends(tK, tHi, tau);
+          ff.cur[e] = delay_seek_down(time_at, ff.cur[e], k, en.s_lo);
+          lo[e] = delay_lookup(time_at, y_at, ff.cur[e], en.s_lo, t0, ff.y0[e], tau);
+          hi[e] = delay_lookup(time_at, y_at, delay_seek_up(time_at, ff.cur[e], k, en.s_hi), en.s_hi, t0, ff.y0[e], tau);
+          moves[e] = !en.clamped;
+          d_lo[e] = lo[e].value;
+          d_hi[e] = hi[e].value;
+        }
+        M::set_delay(p, tK, inv_dt, d_lo, d_hi);
+        ode_step_vjp<M, SOLVER>(tK, tHi, h0, y, p, wts, lam, pb, wtsb);
+        VIHDS_UNROLL for (int e = 0; e < ND; ++e) {
+          const float g_hi = pb[M::DELAY_SLOT + ND + e] * inv_dt, g_lo = pb[M::DELAY_SLOT + e] - g_hi;
+          pb[M::DELAY_SLOT + e] = 0.f;
+          pb[M::DELAY_SLOT + ND + e] = 0.f;
+          if (live) {
+            auto a_at = [&](int q) -> float& { return a.aux[((size_t)e * a.T + q) * n + i]; };
+            const float taub = delay_scatter(a_at, lo[e], g_lo, true) + delay_scatter(a_at, hi[e], g_hi, moves[e]);
+            if (p[M::delay_param(e)] > 0.f) pb[M::delay_param(e)] += taub;  // (taue = fmaxf(tau, 0))
+          }
+        }
+      }
+    } else if constexpr (has_jump<M>::value) {
       // a state jump of the model's own (a branch of its own: every other model's code stays what it was).  The stored y is the
       // left limit y_k and the interval started from yj = jump(y_k): recomputed here by the forward's call on the forward's
       // operands (the value entries of p are u_k after set_interval), so the same bits.  The step adjoint runs from yj -- an
@@ -1109,6 +1192,9 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     else observe_vjp<M::OBS>(y, xpb, lam);
     if (a.g_traj) {
       VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] += a.g_traj[((size_t)k * NT + j) * n + i];
+    }
+    if constexpr (ND > 0) {  // what the later intervals' delayed reads took from the stored y_k
+      VIHDS_UNROLL for (int e = 0; e < ND; ++e) lam[M::delay_species(e)] += a.aux[((size_t)e * a.T + k) * n + i];
     }
   }
   if constexpr (has_start<M>::value || lead_in<M>::value > 0) {
@@ -1272,13 +1358,14 @@ template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
   if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value || has_start<M>::value ||
-                lead_in<M>::value > 0) {
+                lead_in<M>::value > 0 || n_delays<M>::value > 0) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
     // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it.  A model with sub-steps
     // likewise: they divide the intervals of a fixed-grid scheme, an adaptive pair chooses its own steps.  A model with a state
     // jump likewise: the jump is applied between two intervals of the observation grid, which only these time loops walk.  A
-    // model with a start map or a lead-in phase likewise: only these kernels call start and run the steps before t_0
+    // model with a start map or a lead-in phase likewise: only these kernels call start and run the steps before t_0.  A model
+    // with delayed reads likewise: its history is the trajectory these kernels store on the observation grid
     if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
 #define VIHDS_CASE(SV)                                           \
   case SV:                                                       \

@@ -52,6 +52,10 @@ GENERATED_LEAD_IN = {}
 # registered generated models with algebraic variables (`algebraic`, `constraint`): key -> the number of unknowns their struct
 # solves for inside rhs and observe (nothing else differs: every explicit solver takes them)
 GENERATED_ALGEBRAIC = {}
+# registered generated models with delayed reads (`delays`): key -> their count.  They decline the adaptive solvers (the history
+# is the trajectory stored on the observation grid), their forward needs the trajectory buffer and their adjoint a workspace of
+# n_delays * T * B * S floats in aux (vihds_ode_bwd_aux_floats), wanted whether or not a weight gradient is
+GENERATED_DELAYS = {}
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8, "beuler": 9}

@@ -272,6 +272,34 @@ iteration with torch ops (autograd Jacobians, a pivoted solve); it keeps the ite
 gradient, and torch_problem's right-hand side and torch_observe use it, so autograd through the host paths stays correct;
 torch_constraint_jacobian evaluates the generated dg/dz, to check the generator against autograd.
 
+Delayed reads.  A right-hand side may read a species at an earlier time, y_i(t - tau) -- transcription, translation and
+maturation lags, delayed negative feedback, a signal relay -- with the delay an effective parameter like any other:
+
+        delays = {"Rlag": ("R", "tau")}              # name -> (species, key of what prepare returns); at most MAX_DELAYS
+
+        def rhs(self, t, y, p, c):
+            production = p.beta / (1.0 + (self.delayed.Rlag / p.K) ** 2)     # R at t - p.tau
+
+self.delayed.Rlag is readable in rhs only (arithmetic, where conditions; a read in prepare, initial_state, start or a hook
+raises and names the place).  The delay is in the units of `times`; being a key of prepare's dict it may be clamped, scaled or
+shared, and its gradient reaches theta through prepare_vjp.  The value, defined per observation interval k = [t_k, t_k+1] with
+taue = fmaxf(tau, 0.f) (csrc/vihds_delay.hpp): s_lo = t_k - taue and s_hi = fminf(t_k+1 - taue, t_k) -- the history is known up
+to the start of the step only --; H(s) is the stored state at t_0 (after start, where the class has one) for s <= t_0, a constant
+history, and otherwise the linear interpolant fmaf(w, y_j+1 - y_j, y_j) of the float32 states stored at the observation points,
+j the largest index of [0, k-1] with t_j <= s; every stage of the step reads the chord from H(s_lo) to H(s_hi).  The struct
+reserves 2 E + 1 more entries of p behind the forcings' (values, slopes, the interval start) that its member set_delay writes from
+the time loop; rhs reads p[v] + (t - p[t0]) p[s] as it reads a forcing, and -- the difference -- rhs_vjp adds the read's adjoint
+to pb[v] and pb[s].  The adjoint kernel repeats the lookups, scatters those adjoints back to the earlier time points with the
+interpolation weights (a per-trajectory history adjoint in its aux buffer, no atomics, the same bits run to run) and adds
+-(y_j+1 - y_j) / (t_j+1 - t_j) times each to the adjoint of tau where the lookup moves with it.  Consequences: the interpolant
+is linear, so a scheme's order is capped at 2; for taue below the step the read lags by up to h - taue -- the term is then
+treated like explicit Euler (sub-steps would be the remedy and are not combined yet); at s on a grid point, and at taue equal to
+a step, the gradient with respect to tau jumps.  A delay that is not finite makes the read NaN.  Combines with start, forcings,
+piecewise terms and the hooks; declined in this version: implicit = True, substeps > 1, lead_in, jump, networks, algebraic,
+NeuralPrecisions, the adaptive solvers (solve raises before anything is queued) and the one-pass summaries.  torch_problem's rhs
+takes the values as rhs(t, state, delayed=[...]) and lists (species index, delay) per read as rhs.delays; the integration loop
+that looks them up is the caller's (tests/modelgen_delay_models.py has the float64 definition).
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -306,6 +334,7 @@ OBSERVE_KINDS = {"default": ("OBS_DEFAULT", 6), "direct": ("OBS_DIRECT", 4)}  # 
 OBSERVE_CUSTOM = "custom"  # observe_kind of a class that defines observe(y, p, c): the struct's own map, OBS_CUSTOM
 # networks of a generated model (the hidden layer is walked one unit at a time, the inputs and outputs live in registers)
 MAX_NETWORKS, MAX_NET_INPUTS, MAX_NET_HIDDEN, MAX_NET_OUTPUTS = 2, 16, 32, 8
+MAX_DELAYS = 4  # delayed reads of a generated model (each costs the kernels two lookups per interval and three registers)
 MAX_FORCINGS = 4  # time-varying inputs of a generated model (each costs the kernels two registers and a sample in flight)
 NET_ACTIVATIONS = ("relu", "tanh")
 # species of a model with `implicit = True`: the N x N matrix of a Newton step lives in registers beside the states, and its
@@ -374,7 +403,10 @@ _LEAVES += ("ob", "pr")
 _LEAVES += ("f",)
 # ... and the algebraic variables (rhs and observe): the unknowns z of the class's constraint, solved for where they are read
 _LEAVES += ("z",)
-_NO_ADJOINT = ("ob", "f")
+# ... and the delayed reads (rhs only): the trajectory's own past, y_i(t - tau) -- a leaf WITH an adjoint, which rhs_vjp adds to
+# the value and slope entries of the read's reserved slots ("dt": the stage time minus the interval start, its helper leaf)
+_LEAVES += ("d", "dt")
+_NO_ADJOINT = ("ob", "f", "dt")
 
 
 def _control_flow(*_args, **_kw):
@@ -1030,6 +1062,39 @@ class _Forcings(object):
         raise ModelDefinitionError("forcings are read-only")
 
 
+def _class_delays(cls):
+    """[(name, species, effective parameter)] of the class's delayed reads, in declaration order."""
+    d = getattr(cls, "delays", None) or {}
+    return [(k, v[0], v[1]) for k, v in d.items()] if isinstance(d, dict) else []
+
+
+class _Delayed(object):
+    """`self.delayed` of the instance the functions run on: `self.delayed.<name>` is that species at t - tau where rhs is
+    evaluated.  read(e, name) does the work (symbolic or torch)."""
+
+    def __init__(self, cls, read):
+        object.__setattr__(self, "_names", [d[0] for d in _class_delays(cls)])
+        object.__setattr__(self, "_read", read)
+        object.__setattr__(self, "_cls", cls.__name__)
+
+    def __getattr__(self, name):
+        if name not in self._names:
+            raise ModelDefinitionError("unknown delayed read '%s' (%s.delays declares: %s)"
+                                       % (name, self._cls, ", ".join(self._names) or "none"))
+        return self._read(self._names.index(name), name)
+
+    __getitem__ = __getattr__
+
+    def __setattr__(self, name, value):
+        raise ModelDefinitionError("delayed reads are read-only")
+
+
+def _delay_misread(name, where):
+    raise ModelDefinitionError(
+        "delayed read '%s' read in %s: a delayed read is the trajectory's own past at the stage time of a step, so it is read "
+        "in rhs(self, t, y, p, c) only (not in prepare, initial_state, start, constraint or any hook)" % (name, where))
+
+
 def _class_algebraic(cls):
     return list(getattr(cls, "algebraic", None) or ())
 
@@ -1237,6 +1302,14 @@ class Trace(object):
             return g.leaf("z", i)
 
         object.__setattr__(inst, "algebraic", _Algebraic(cls, read_z))
+        self.delays = _class_delays(cls)
+
+        def read_d(e, name):
+            if self._phase != "rhs":
+                _delay_misread(name, self._phase)
+            return g.leaf("d", e)
+
+        object.__setattr__(inst, "delayed", _Delayed(cls, read_d))
         N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
         th = _Named([(n, g.leaf("th", s)) for s, n in enumerate(P)], "parameter")
         cs = [g.leaf("c", q) for q in range(C)]
@@ -1245,6 +1318,10 @@ class Trace(object):
             raise ModelDefinitionError("%s.prepare must return a dict {name: value}" % cls.__name__)
         self.p_names = list(prepared)
         self.p_exprs = [g._arg(prepared[k]) for k in self.p_names]
+        for name, _sp, par in self.delays:
+            if par not in self.p_names:
+                raise ModelDefinitionError("%s.delays: '%s' names the delay '%s', which is no effective parameter (prepare "
+                                           "returns: %s)" % (cls.__name__, name, par, ", ".join(self.p_names)))
         self._phase = "initial_state"
         y0 = inst.initial_state(th, _Conditions(cs))
         self.y0 = self._state_list(y0, "initial_state", N)
@@ -1292,6 +1369,8 @@ class Trace(object):
         self.c_slot = {NPU + q: NPU + k for k, q in enumerate(self.c_in_rhs)}
         # the forcings' entries of p follow: K values, K slopes, one interval start (the struct's set_interval / set_point)
         self.F0 = self.NP
+        # ... and the delayed reads' behind them: E values, E slopes, one interval start (the struct's set_delay)
+        self.D0 = self.F0 + (2 * len(self.forcings) + 1 if self.forcings else 0)
 
     def _unknown_list(self, v, what, M):
         if not isinstance(v, (list, tuple)) or len(v) != M:
@@ -1332,6 +1411,10 @@ class _Emitter(object):
         if n.op == "const": return _lit(n.val)
         if n.op == "f":  # (a forcing: the text of its value where this function is evaluated)
             return self.leaf_names["f"][n.val]
+        if n.op == "d":  # (a delayed read: the chord of the interval at the stage time)
+            return self.leaf_names["d"][n.val]
+        if n.op == "dt":
+            return self.leaf_names["dt"]
         if n.op in _LEAVES:
             base = self.leaf_names[n.op]
             idx = self.p_map.get(n.val, n.val) if n.op == "p" else n.val
@@ -1524,6 +1607,10 @@ def generate_source(cls, neural=False):
         raise ModelDefinitionError("%s declares algebraic variables: WithPrec<> evaluates the precision ODE beside a rhs that has no "
                                    "unknowns, so a model with algebraic variables does not take NeuralPrecisions (constant "
                                    "precisions, or a precision map of its own)" % cls.__name__)
+    if neural and tr.delays:
+        raise ModelDefinitionError("%s declares delays: WithPrec<> forwards neither the reserved slots nor set_delay, so a model "
+                                   "with delayed reads does not take NeuralPrecisions (constant precisions, or a precision map "
+                                   "of its own)" % cls.__name__)
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -1568,6 +1655,14 @@ def generate_source(cls, neural=False):
     v = [g.leaf("seed", j) for j in range(N)]
     adj1 = vjp(g, tr.dy, v)
     rhs_vjp = pull(adj1, [("y", "yb"), ("p", "pb")])
+    # delayed reads: entries D0 .. of p hold E values, E slopes and the interval start (set_delay); rhs reads the chord at its
+    # stage time, and -- unlike a forcing -- the read has an adjoint: rhs_vjp adds it to pb of the value and the slope entry
+    E, D0 = len(tr.delays), tr.D0
+    d_at_t = ["(p[%d] + (t - p[%d]) * p[%d])" % (D0 + e, D0 + 2 * E, D0 + E + e) for e in range(E)]
+    for e in range(E):
+        db = adj1.get(g.leaf("d", e).id)
+        if db is not None:
+            rhs_vjp += [("pb[%d]" % (D0 + e), "+=", db), ("pb[%d]" % (D0 + E + e), "+=", db * g.leaf("dt", 0))]
 
     # forcings: entries F0 .. of p hold K values, K slopes and the interval start; rhs (and its adjoint) reads the interpolant
     # at its stage time, a hook the value (set_point: the sample of the time point)
@@ -1577,7 +1672,7 @@ def generate_source(cls, neural=False):
 
     def body(assign, fast, seed, p_map=None, forcing=None):
         names = {"th": "th", "c": "c", "y": "y", "p": "p", "t": "t", "seed": seed, "x": "xp", "ob": "ob", "pr": "pr",
-                 "f": forcing, "z": "z"}
+                 "f": forcing, "z": "z", "d": d_at_t, "dt": "(t - p[%d])" % (D0 + 2 * E)}
         return "\n".join(_Emitter(fast, names, p_map).emit(assign))
 
     # algebraic variables: a member that reads them opens with the solve, its adjoint repeats the solve and closes with the mu
@@ -1649,6 +1744,23 @@ def generate_source(cls, neural=False):
             "  __device__ static void set_point(float* p, const float* u) {",
         ] + ["    p[%d] = u[%d];" % (F0 + k, k) for k in range(K)] + [
             "    p[%d] = 0.f;" % (F0 + K + k) for k in range(K)] + [
+            "  }",
+        ]
+    delay_decl = []
+    if E:
+        sp = [cls.species.index(d[1]) for d in tr.delays]
+        tau = [tr.p_names.index(d[2]) for d in tr.delays]
+        pick = lambda v: " : ".join(["e == %d ? %d" % (e, x) for e, x in enumerate(v[:-1])] + ["%d" % v[-1]])  # noqa: E731
+        delay_decl = [
+            "  static constexpr int N_DELAYS = %d;  // %s: p[%d ..] values, p[%d ..] slopes, p[%d] the interval start" % (
+                E, ", ".join("%s = %s(t - %s)" % d for d in tr.delays), D0, D0 + E, D0 + 2 * E),
+            "  static constexpr int DELAY_SLOT = %d;  // the first reserved entry of p (and of pb: value and slope adjoints)" % D0,
+            "  __host__ __device__ static constexpr int delay_species(int e) { return %s; }" % pick(sp),
+            "  __host__ __device__ static constexpr int delay_param(int e) { return %s; }  // the delay's entry of p" % pick(tau),
+            "  __device__ static void set_delay(float* p, float t_lo, float inv_dt, const float* d_lo, const float* d_hi) {",
+        ] + ["    p[%d] = d_lo[%d];" % (D0 + e, e) for e in range(E)] + [
+            "    p[%d] = (d_hi[%d] - d_lo[%d]) * inv_dt;" % (D0 + E + e, e, e) for e in range(E)] + [
+            "    p[%d] = t_lo;" % (D0 + 2 * E),
             "  }",
         ]
     # implicit = True: the Jacobian of rhs for the Newton step of the implicit solvers and for their adjoint (after everything
@@ -1739,8 +1851,8 @@ def generate_source(cls, neural=False):
         "  static constexpr int NC = %d;" % C,
         "  static constexpr int OBS = %s;" % obs_enum,
         "  static constexpr int NSLOT = %d;" % len(P),
-        "  static constexpr int NP = %d;" % (max(tr.NP, 1) if not K else tr.NP + 2 * K + 1),
-    ] + substeps_decl + implicit_decl + forcing_decl + net_decl + algebraic_decl + [
+        "  static constexpr int NP = %d;" % (D0 + 2 * E + 1 if E else max(tr.NP, 1) if not K else tr.NP + 2 * K + 1),
+    ] + substeps_decl + implicit_decl + forcing_decl + delay_decl + net_decl + algebraic_decl + [
         "  __host__ static const char* slot_name(int s) {",
         "    static const char* n[] = {%s};" % names,
         "    return n[s];",
@@ -1871,6 +1983,8 @@ def register_kernel(cls, neural=False):
         hip.GENERATED_IMPLICIT_ORDER[key] = int(cls.implicit_order)
     if cls._trace.algebraic:  # (unknowns of a constraint, solved inside the struct's rhs and observe)
         hip.GENERATED_ALGEBRAIC[key] = len(cls._trace.algebraic)
+    if cls._trace.delays:  # (delayed reads: the fixed-grid schemes only; the adjoint needs its history workspace)
+        hip.GENERATED_DELAYS[key] = len(cls._trace.delays)
     hip.GENERATED_SUBSTEPS[key] = int(cls.substeps)  # (above 1: the library holds the fixed-grid schemes only)
     if cls._trace.jmp is not None:  # (a state jump at the observation points: the fixed-grid schemes only, likewise)
         hip.GENERATED_JUMP.add(key)
@@ -1902,6 +2016,7 @@ class GeneratedOdeModel(OdeModel):
     _start_def = None  # ... and of its start map (START_HOOK)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
+    delays = None  # {name: (species, effective parameter)}: delayed reads, self.delayed.<name> in rhs (module docstring)
     implicit = False  # True: the Jacobian of rhs is generated and the implicit solvers take the model (module docstring)
     newton_iterations = 4  # Newton iterations of one implicit step, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
     implicit_order = 1  # the order of the implicit scheme: 1 backward Euler, 2 the two-stage SDIRK (needs implicit = True)
@@ -2018,6 +2133,11 @@ class GeneratedOdeModel(OdeModel):
                     "%s %s: only the kernels of the fixed-grid schemes run it, the adaptive solver '%s' is not available to it "
                     "(fixed-grid solvers: %s)" % (type(self).__name__, what, config.params.solver,
                                                   ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if _class_delays(type(self)) and config.params.solver in hip.ADAPTIVE_SOLVERS:  # (likewise)
+            raise NotImplementedError(
+                "%s declares delays, which read the trajectory stored on the observation grid: the adaptive solver '%s' "
+                "integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
+                    type(self).__name__, config.params.solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         K = len(_class_forcings(type(self)))
         if K:  # (checked before anything is built or queued)
             if config.params.solver in hip.ADAPTIVE_SOLVERS:
@@ -2141,7 +2261,10 @@ class GeneratedOdeModel(OdeModel):
         weights: {network name: (W1 [H][I], b1 [H], W2 [O][H], b2 [O])} for a model with networks (an instance's
         network_weights(), or tensors of the caller's own that require grad: autograd then gives the weight gradients).
         x0 is the state the integration starts from: a class's start map is applied to its initial state (start=False: the
-        initial state alone); the steps of a lead-in phase are the caller's to take, on lead_in_times."""
+        initial state alone); the steps of a lead-in phase are the caller's to take, on lead_in_times.
+        A class with delayed reads: rhs(t, state, delayed=[one [B,S] tensor per entry of cls.delays]) takes the values of its
+        reads as it takes a forcing's -- what they are (the lookup into the trajectory so far) is the caller's integration loop's
+        to say; rhs.delays lists (species index, the delay [B,S] as prepare returned it) per entry."""
         inst = cls.__new__(cls)
         nets = _class_networks(cls)
         if nets:
@@ -2169,13 +2292,22 @@ class GeneratedOdeModel(OdeModel):
         full = lambda v: v if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
         unknowns = _class_algebraic(cls)
         object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda _i, name: _algebraic_misread(name, "prepare, initial_state or start")))
+        lags, now_d = _class_delays(cls), {}
+        if lags:
+            object.__setattr__(inst, "delayed", _Delayed(
+                cls, lambda e, name: now_d["d"][e] if now_d.get("d") is not None else _delay_misread(name, "prepare, initial_state or start")))
         p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
         x0 = torch.stack([full(v) for v in inst.initial_state(thn, _Conditions(cs))], dim=2)
         if start and cls._start_def is not None:  # (the state the integration starts from)
             x0 = cls.torch_start(x0, th, cond, **({"n_times": tg.shape[0]} if names else {}))
 
-        def rhs(t, state):
+        def rhs(t, state, delayed=None):
             y = list(torch.unbind(state[:, :, :N], dim=2))
+            if lags:
+                if delayed is None or len(delayed) != len(lags):
+                    raise ValueError("%s.torch_problem's rhs needs delayed=[%s]: the values of the class's delayed reads at t"
+                                     % (cls.__name__, ", ".join(d[0] for d in lags)))
+                now_d["d"] = list(delayed)
             if names:
                 # the linear interpolant of the row's samples at t: on [t_k, t_k+1], u_k + (t - t_k) (u_k+1 - u_k) / (t_k+1 - t_k)
                 tt = torch.as_tensor(t, dtype=ref.dtype, device=ref.device)
@@ -2188,6 +2320,8 @@ class GeneratedOdeModel(OdeModel):
                 object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda i, _name: z[i]))
             return torch.stack([full(v) for v in inst.rhs(t, y, p, _Conditions(cs))], dim=2)
 
+        if lags:
+            rhs.delays = [(list(cls.species).index(sp), full(p[par])) for _name, sp, par in lags]
         return rhs, x0
 
     @classmethod
@@ -2518,6 +2652,33 @@ def _validate(cls):
                                    % (name, len(forc), MAX_FORCINGS))
     nets = getattr(cls, "networks", None)
     alg = getattr(cls, "algebraic", None) or ()
+    dl = getattr(cls, "delays", None)
+    if dl:
+        if not isinstance(dl, dict) or not all(
+                isinstance(k, str) and k.isidentifier() and isinstance(v, (list, tuple)) and len(v) == 2
+                and all(isinstance(x, str) for x in v) for k, v in dl.items()):
+            raise ModelDefinitionError("%s.delays must be a dict {name: (species, effective parameter holding the delay)}" % name)
+        if len(dl) > MAX_DELAYS:
+            raise ModelDefinitionError("%s: %d delays; a generated model reads at most %d (MAX_DELAYS)" % (name, len(dl), MAX_DELAYS))
+        clash = [k for k in dl if k in cls.species or k in cls.parameter_names or k in forc or k in alg]
+        if clash:
+            raise ModelDefinitionError("%s.delays: %s %s also a species, a parameter, a forcing or an algebraic variable; a "
+                                       "delayed read needs a name of its own" % (name, ", ".join("'%s'" % k for k in clash),
+                                                                                 "is" if len(clash) == 1 else "are"))
+        for k, (sp, _par) in dl.items():
+            if sp not in cls.species:
+                raise ModelDefinitionError("%s.delays: '%s' reads the unknown species '%s' (species: %s)"
+                                           % (name, k, sp, ", ".join(cls.species)))
+        for has, what, why in (
+                (cls.implicit is True, "implicit = True", "the read would be data of the implicit step, and neither the "
+                                                          "Jacobian's use of it nor its adjoint is built"),
+                (cls.substeps != 1, "substeps = %r" % (cls.substeps,), "the history is stored at the observation points only"),
+                (cls.lead_in != 0, "lead_in = %r" % (cls.lead_in,), "the history before the first point is the constant stored state"),
+                (getattr(cls, "_jump_def", None) is not None, "jump(self, y, p, c)", "the stored history holds the left limits"),
+                (bool(nets), "networks", "the adjoint's dump of a network and the history workspace share the aux buffer"),
+                (bool(alg), "algebraic variables", "the solve inside rhs_vjp does not pass the read's adjoint on")):
+            if has:
+                raise ModelDefinitionError("%s has delays and %s: %s -- declined in this version" % (name, what, why))
     if not isinstance(alg, (list, tuple)) or not all(isinstance(a, str) and a.isidentifier() for a in alg):
         raise ModelDefinitionError("%s.algebraic must be a list of names (valid identifiers)" % name)
     if alg:

@@ -108,6 +108,11 @@ class OdeProblemSpec:
                     model, " and ".join(["a start map (start)"] * (model in hip.GENERATED_START)
                                         + ["a lead-in phase (lead_in)"] * (model in hip.GENERATED_LEAD_IN)),
                     solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if solver in hip.ADAPTIVE_SOLVERS and model in hip.GENERATED_DELAYS:  # (likewise)
+            raise NotImplementedError(
+                "model '%s' has delayed reads of the trajectory stored on the observation grid: the adaptive solver '%s' "
+                "integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
+                    model, solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         self.model, self.solver = model, solver
         sized = False
         if model == "dr_blackbox":
@@ -151,6 +156,8 @@ class OdeProblemSpec:
         self.networks = list(hip.GENERATED_NETWORKS.get(model, ()))
         # a generated model's own precision map: n_states - n_species = 4 rows the kernel stores, not a precision network
         self.own_precision = model in hip.GENERATED_OWN_PRECISION
+        # a generated model's delayed reads: the adjoint's aux buffer is its history workspace, with or without weights
+        self.n_delays = hip.GENERATED_DELAYS.get(model, 0)
         self.covers_all_rows = len({row_of[s] for s in self.slots}) == n_rows
         self.unwritten_rows = sorted(set(range(n_rows)) - {row_of[s] for s in self.slots})  # rows the adjoint leaves alone
         self.cache = {}  # device-side constants derived from this spec
@@ -313,8 +320,9 @@ class OdeSolveObserve(torch.autograd.Function):
         g_theta = torch.empty_like(theta) if (ctx.spec.covers_all_rows or assign_src) else torch.zeros_like(theta)
         n_aux = hip.lib().vihds_ode_bwd_aux_floats(ctypes.byref(ctx.prob))
         blackbox = ctx.spec.model == "dr_blackbox"
-        if not blackbox and not (weights is not None and ctx.needs_input_grad[6]):
+        if not blackbox and not ctx.spec.n_delays and not (weights is not None and ctx.needs_input_grad[6]):
             n_aux = 0  # neural precisions: the dump is only worth it when the weight gradients are wanted
+        # (a model with delayed reads: aux is the adjoint's history workspace, needed whatever gradients are wanted)
         # (dr_blackbox: the weight gradients come from the dump below, the kernel does not touch g_weights)
         g_w = torch.zeros_like(weights) if weights is not None and not blackbox else None
         prob = ctx.prob
@@ -333,7 +341,7 @@ class OdeSolveObserve(torch.autograd.Function):
             hip.ptr(weights), hip.ptr(s.traj), hip.ptr(g_traj), hip.ptr(g_xpred), hip.ptr(g_logp), hip.ptr(g_theta),
             hip.ptr(g_w), hip.ptr(aux), hip.current_stream()))
         hip.check(rc, "vihds_ode_bwd")
-        if aux is not None and ctx.needs_input_grad[6]:
+        if aux is not None and ctx.needs_input_grad[6] and not ctx.spec.n_delays:
             if blackbox:
                 g_w = blackbox_weight_grads(ctx.spec, ctx.prob, aux, theta, s.cond, dev1hot)
             elif not hip.lib().vihds_ode_bwd_reduces_weights(ctypes.byref(ctx.prob)):
@@ -1519,8 +1527,8 @@ class GeneralTail(StepTail):
             P, dev = fwd.q_all.shape[0] // 2, fwd.q_all.device
             n_aux = int(L.vihds_ode_bwd_aux_floats(ctypes.byref(prob)))
             lanes_reduce = (weights is not None and not blackbox and bool(L.vihds_ode_bwd_reduces_weights(ctypes.byref(prob))))
-            if not blackbox and weights is None:
-                n_aux = 0
+            if not blackbox and weights is None and not fwd.spec.n_delays:
+                n_aux = 0  # (a model with delayed reads keeps it: the adjoint's history workspace)
             n_flat = sum(t.numel() for t in self.flat_tensors)
             n_all = sum(p.numel() for p in self.optimizer.param_groups[0]["params"] if p.requires_grad)
             Lc = s.L - s.K + 1
