@@ -45,6 +45,10 @@ static_assert(!(n_delays<VIHDS_GEN_CORE>::value > 0 &&
                  lead_in<VIHDS_GEN_CORE>::value > 0 || net_fields<VIHDS_GEN_CORE>::value > 0)),
               "delayed reads combine with the explicit fixed-grid schemes only: no implicit, substeps, jump, lead_in or networks");
 static_assert(n_delays<VIHDS_GEN_CORE>::value >= 0 && n_delays<VIHDS_GEN_CORE>::value <= 4, "delays: at most 4");
+static_assert(!(has_diffusion<VIHDS_GEN_CORE>::value &&
+                (VIHDS_GEN_NEURAL != 0 || has_jacobian<VIHDS_GEN_CORE>::value || net_fields<VIHDS_GEN_CORE>::value > 0 ||
+                 lead_in<VIHDS_GEN_CORE>::value > 0 || n_delays<VIHDS_GEN_CORE>::value > 0)),
+              "process noise combines with the explicit fixed-grid schemes only: no NeuralPrecisions, implicit, networks, lead_in or delays");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
@@ -95,7 +99,7 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
                                    net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
                                    n_forcings<GenM>::value, implicit_order<GenM>::value, substeps<GenM>::value,
                                    has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value,
-                                   n_delays<GenM>::value};
+                                   n_delays<GenM>::value, has_diffusion<GenM>::value ? 1 : 0};
   return &r;
 }
 #endif

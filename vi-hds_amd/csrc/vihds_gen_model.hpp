@@ -67,6 +67,10 @@ struct GenModelRecord {
   // (it reads back what the same thread stored), the adjoint n_delays * T * B * S floats of aux for its history adjoint
   // (vihds_ode_bwd_aux_floats); the fixed-grid solvers only
   int n_delays;
+  // 1: the generated struct has process noise (diffusion / diffusion_vjp, vihds_models.hpp has_diffusion<>; vihds_sde.hpp): a
+  // data row of cond ends with the two words of its key, so a problem needs C >= n_cond + n_forcings * T + 2; the explicit
+  // fixed-grid solvers only
+  int diffusion;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

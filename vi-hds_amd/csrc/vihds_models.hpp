@@ -1060,6 +1060,23 @@ struct lead_in<M, std::void_t<decltype(M::LEAD_STEPS), decltype(M::LEAD_TIME)>> 
   static constexpr int value = M::LEAD_STEPS;
 };
 
+// A core generated with process noise (vihds/modelgen.py: diffusion(self, y, p, c)) declares HAS_DIFFUSION = true, NOISE_MASK
+// (bit j: species j has an amplitude that is not the constant 0) and two members that run once per step of the scheme:
+//   diffusion(y, p, g)                   g[j] = the noise amplitude of species j at the step's start state (noisy species only)
+//   diffusion_vjp(y, p, gb, yb, pb)      yb += (d g/d y)^T gb ; pb += (d g/d p)^T gb   (forward values recomputed)
+// vihds_sde.hpp wraps the step (noisy_step / noisy_step_vjp) and defines the draws; the row's key is the last two floats of its
+// row of cond, behind the forcing samples.  Such a model takes the explicit fixed-grid solvers only.  False for every
+// hand-written model and for WithPrec<> (which declares no HAS_DIFFUSION and does not forward its core's members).
+template <class M, class = void>
+struct has_diffusion : std::false_type {};
+template <class M>
+struct has_diffusion<M, std::void_t<decltype(M::HAS_DIFFUSION)>> : std::bool_constant<M::HAS_DIFFUSION> {};
+// floats of a row of cond behind the forcing samples: the two key words of such a model (vihds_sde.hpp), none otherwise
+template <class M>
+constexpr int cond_tail() {
+  return has_diffusion<M>::value ? 2 : 0;
+}
+
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
 template <class Ctx, class = void>
 struct ctx_has_wb : std::false_type {};

@@ -23,6 +23,7 @@
 #include "vihds_implicit.hpp"
 #include "vihds_delay.hpp"
 #include "vihds_substeps.hpp"
+#include "vihds_sde.hpp"
 #include "vihds_blackbox.hpp"
 #include "vihds_iwae_inline.hpp"
 
@@ -373,13 +374,18 @@ __device__ __forceinline__ void ode_step_vjp_implicit_any(float t0, float t1, co
 // `if constexpr (substeps<M>::value > 1)`, so every other model's kernels are what they were.
 
 // the forward's interval: MS steps of the scheme, a rolled loop (the code does not grow with MS)
+// (k, key: the interval's index and the thread's noise stream, read by a model with process noise only -- vihds_sde.hpp)
 template <class M, int SOLVER>
-__device__ __forceinline__ void ode_substeps(float t0, float t1, float h0, float* y, const float* p, const float* wts) {
+__device__ __forceinline__ void ode_substeps(float t0, float t1, float h0, float* y, const float* p, const float* wts,
+                                             int k = 0, const SdeKey& key = SdeKey{}) {
   constexpr int MS = substeps<M>::value;
   const SubGrid<MS> sg(t0, t1);
   const float hm = SubGrid<MS>::fixed_step(h0);
 #pragma unroll 1
-  for (int j = 0; j < MS; ++j) ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, y, p, wts);
+  for (int j = 0; j < MS; ++j) {
+    if constexpr (has_diffusion<M>::value) noisy_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, sde_step_index(k, MS, j), key, y, p, wts);
+    else ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, y, p, wts);
+  }
 }
 
 // Where the adjoint keeps an interval's intermediate states u_1 .. u_MS-1: ROWS = (MS - 1) * N rows of 256 floats in LDS.
@@ -407,7 +413,8 @@ constexpr int substate_rows() {
 // An explicit scheme's adjoint starts from u_j, the implicit one's from u_j+1.  Both loops stay rolled.
 template <class M, int SOLVER, class Ctx>
 __device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, const float* y, const float* y_next,
-                                                 const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb) {
+                                                 const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb,
+                                                 int k = 0, const SdeKey& key = SdeKey{}) {
   constexpr int N = M::N, MS = substeps<M>::value;
   float* col = SubstateLds<substate_rows<M>()>::column();
   const SubGrid<MS> sg(t0, t1);
@@ -416,7 +423,9 @@ __device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, c
   VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y[q];
 #pragma unroll 1
   for (int j = 0; j < MS - 1; ++j) {  // u_j -> u_j+1, kept as row block j
-    ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, u, p, wts);
+    // (a model with process noise: the forward's noisy step with the forward's step index, so the forward's draws and bits)
+    if constexpr (has_diffusion<M>::value) noisy_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, sde_step_index(k, MS, j), key, u, p, wts);
+    else ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, u, p, wts);
     VIHDS_UNROLL for (int q = 0; q < N; ++q) col[(j * N + q) * 256] = u[q];
   }
   if constexpr (solver_is_implicit(SOLVER)) {
@@ -442,7 +451,9 @@ __device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, c
   } else {  // (u holds u_MS-1)
 #pragma unroll 1
     for (int j = MS - 1; j >= 0; --j) {
-      ode_step_vjp<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, u, p, wts, lam, pb, wtsb);
+      if constexpr (has_diffusion<M>::value)
+        noisy_step_vjp<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, sde_step_index(k, MS, j), key, u, p, wts, lam, pb, wtsb);
+      else ode_step_vjp<M, SOLVER>(sg.at(j), sg.at(j + 1), hm, u, p, wts, lam, pb, wtsb);
       if (j > 1) {  // u_j-1 for the sub-step below
         VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = col[((j - 2) * N + q) * 256];
       } else {
@@ -582,6 +593,15 @@ struct WithDelayState : Feed {
 };
 template <class Feed, int ND>
 using delay_feed_t = std::conditional_t<(ND > 0), WithDelayState<Feed, ND>, Feed>;
+// what the time loops keep for a model with process noise (has_diffusion<M>, vihds_sde.hpp) beside their feed: the row's key and
+// the trajectory's index, loaded once ahead of the loop.  Every other model's loop declares the feed alone, as it did
+// (noise_feed_t), so its code is what it was.
+template <class Feed>
+struct WithNoiseKey : Feed {
+  SdeKey key;
+};
+template <class Feed, bool ON>
+using noise_feed_t = std::conditional_t<ON, WithNoiseKey<Feed>, Feed>;
 // ---- forward -------------------------------------------------------------------------------------
 // LDS_IN: the time grid and the observation rows of the data rows this block spans are staged in LDS once, so the
 // time loop holds no vector-memory loads and its trajectory / x_predict stores are never waited on (see
@@ -598,7 +618,8 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations | [nb][NF][T] forcing samples
   const float* wts = stage_weights<M>(a, wlds);
   int ob_off = 0;
-  delay_feed_t<ForcingFeed<NF>, ND> ff;  // (ForcingFeed<NF>; a model with delayed reads also keeps y_0 and its cursors)
+  // (ForcingFeed<NF>; a model with delayed reads also keeps y_0 and its cursors, one with process noise its key)
+  noise_feed_t<delay_feed_t<ForcingFeed<NF>, ND>, has_diffusion<M>::value> ff;
   if (LDS_IN) {
     const int first = blockIdx.x * blockDim.x, last = min(first + (int)blockDim.x, a.n) - 1;
     const int b0 = first / a.S, nb = last / a.S - b0 + 1;
@@ -607,7 +628,7 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     for (int q = threadIdx.x; q < nb * 4 * a.T; q += blockDim.x) in_lds[a.T + q] = src[q];
     if constexpr (NF > 0) {  // (a row's samples are contiguous, the rows are C apart)
       const int per_row = NF * a.T, f_base = a.T + nb * 4 * a.T;
-      const float* fsrc = a.cond + (size_t)b0 * a.C + (a.C - per_row);
+      const float* fsrc = a.cond + (size_t)b0 * a.C + (a.C - cond_tail<M>() - per_row);
       for (int q = threadIdx.x; q < nb * per_row; q += blockDim.x)
         in_lds[f_base + q] = fsrc[(size_t)(q / per_row) * a.C + q % per_row];
     }
@@ -653,7 +674,7 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   VIHDS_UNROLL for (int j = 0; j < 4; ++j) { obc[j] = a.logp ? obs_at(j, 0) : 0.f; obn[j] = 0.f; }
   // forcing samples travel with the times: ff.lo / ff.hi at tA / tB, the next point's requested one iteration ahead like tC
   if constexpr (NF > 0) {
-    ff.src = a.cond + (size_t)b * a.C + (a.C - NF * a.T);
+    ff.src = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - NF * a.T);
     VIHDS_UNROLL for (int j = 0; j < NF; ++j) {
       ff.lo[j] = LDS_IN ? in_lds[ff.lds + j * a.T] : ff.src[j * a.T];
       ff.hi[j] = LDS_IN ? in_lds[ff.lds + j * a.T + 1] : ff.src[j * a.T + 1];
@@ -675,6 +696,7 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
       ode_lead_in<M, SOLVER>(tA, y, p, wts);
     }
   }
+  if constexpr (has_diffusion<M>::value) ff.key = sde_load_key(a.cond, a.C, b, i);
   if constexpr (ND > 0) {  // the history before t_0 is the state stored at t_0 (after start, where the model has one)
     VIHDS_UNROLL for (int e = 0; e < ND; ++e) {
       ff.y0[e] = y[M::delay_species(e)];
@@ -710,7 +732,12 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
         }
         M::set_delay(p, tA, 1.f / (tB - tA), d_lo, d_hi);
       }
-      if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts);  // (one interval, several steps)
+      if constexpr (has_diffusion<M>::value) {
+        // process noise (a branch of its own: every other model's code stays what it was): every step of the interval k - 1 adds
+        // g(u) sqrt(h) xi, its draws counted by the trajectory, the species and the step (vihds_sde.hpp)
+        if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts, k - 1, ff.key);
+        else noisy_step<M, SOLVER>(tA, tB, h0, sde_step_index(k - 1, 1, 0), ff.key, y, p, wts);
+      } else if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts);  // (one interval, several steps)
       else ode_step<M, SOLVER>(tA, tB, h0, y, p, wts);
       tA = tB;
       if constexpr (NF > 0) {
@@ -1006,8 +1033,9 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   float tHi = a.times[a.T - 1], tLo = tHi;
   // forcing samples travel with the times: ff.hi at tHi, ff.lo at tK, the next lower point's (ff.ahead) requested one
   // iteration ahead like tLo
-  // (ForcingFeed<NF>; an implicit solver's also keeps y_k+1, a model with delayed reads y_0 and its cursors)
-  delay_feed_t<bwd_feed_t<NF, N, solver_is_implicit(SOLVER)>, ND> ff;
+  // (ForcingFeed<NF>; an implicit solver's also keeps y_k+1, a model with delayed reads y_0 and its cursors, one with process
+  // noise its key)
+  noise_feed_t<delay_feed_t<bwd_feed_t<NF, N, solver_is_implicit(SOLVER)>, ND>, has_diffusion<M>::value> ff;
   if constexpr (ND > 0) {
     // the history adjoint A[entry][T] of this trajectory: its own column of aux, zeroed here and touched by no other thread
     // (a tail lane shadows the last trajectory: it reads that column and never writes it)
@@ -1019,8 +1047,9 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
       }
     }
   }
+  if constexpr (has_diffusion<M>::value) ff.key = sde_load_key(a.cond, a.C, b, i);
   if constexpr (NF > 0) {
-    ff.src = a.cond + (size_t)b * a.C + (a.C - NF * a.T);
+    ff.src = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - NF * a.T);
     VIHDS_UNROLL for (int j = 0; j < NF; ++j) { ff.ahead[j] = ff.src[j * a.T + a.T - 1]; ff.hi[j] = ff.ahead[j]; }
   }
   for (int k = a.T - 1; k >= 0; --k) {
@@ -1075,6 +1104,27 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
             const float taub = delay_scatter(a_at, lo[e], g_lo, true) + delay_scatter(a_at, hi[e], g_hi, moves[e]);
             if (p[M::delay_param(e)] > 0.f) pb[M::delay_param(e)] += taub;  // (taue = fmaxf(tau, 0))
           }
+        }
+      }
+    } else if constexpr (has_diffusion<M>::value) {
+      // process noise (a branch of its own: every other model's code stays what it was; such a model has no implicit scheme, no
+      // delays and no lead-in).  The interval k started from the stored y_k, or from jump(y_k) recomputed as below; every step
+      // adjoint regenerates its draws from the forward's counters (noisy_step_vjp), a sub-stepped interval recomputes its
+      // sub-states by the forward's noisy steps (ode_substeps_vjp)
+      if (k < a.T - 1) {
+        float ys[N];
+        if constexpr (has_jump<M>::value) {
+          M::jump(y, p, ys);
+        } else {
+          VIHDS_UNROLL for (int j = 0; j < N; ++j) ys[j] = y[j];
+        }
+        if constexpr (substeps<M>::value > 1) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, ys, nullptr, p, wts, lam, pb, wtsb, k, ff.key);
+        else noisy_step_vjp<M, SOLVER>(tK, tHi, h0, sde_step_index(k, 1, 0), ff.key, ys, p, wts, lam, pb, wtsb);
+        if constexpr (has_jump<M>::value) {
+          float lamk[N];
+          VIHDS_UNROLL for (int j = 0; j < N; ++j) lamk[j] = 0.f;
+          M::jump_vjp(y, p, lam, lamk, pb);
+          VIHDS_UNROLL for (int j = 0; j < N; ++j) lam[j] = lamk[j];
         }
       }
     } else if constexpr (has_jump<M>::value) {
@@ -1358,14 +1408,15 @@ template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
   if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value || has_start<M>::value ||
-                lead_in<M>::value > 0 || n_delays<M>::value > 0) {
+                lead_in<M>::value > 0 || n_delays<M>::value > 0 || has_diffusion<M>::value) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
     // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it.  A model with sub-steps
     // likewise: they divide the intervals of a fixed-grid scheme, an adaptive pair chooses its own steps.  A model with a state
     // jump likewise: the jump is applied between two intervals of the observation grid, which only these time loops walk.  A
     // model with a start map or a lead-in phase likewise: only these kernels call start and run the steps before t_0.  A model
-    // with delayed reads likewise: its history is the trajectory these kernels store on the observation grid
+    // with delayed reads likewise: its history is the trajectory these kernels store on the observation grid.  A model with
+    // process noise likewise: its draws are counted by the steps of the observation grid (vihds_sde.hpp)
     if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
 #define VIHDS_CASE(SV)                                           \
   case SV:                                                       \

@@ -56,6 +56,9 @@ GENERATED_ALGEBRAIC = {}
 # is the trajectory stored on the observation grid), their forward needs the trajectory buffer and their adjoint a workspace of
 # n_delays * T * B * S floats in aux (vihds_ode_bwd_aux_floats), wanted whether or not a weight gradient is
 GENERATED_DELAYS = {}
+# keys of registered generated models with process noise (`diffusion(self, y, p, c)`): they decline the adaptive solvers (the
+# draws are counted by the steps of the observation grid), and a row of their cond ends with the two words of its noise key
+GENERATED_DIFFUSION = set()
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8, "beuler": 9}

@@ -300,6 +300,46 @@ NeuralPrecisions, the adaptive solvers (solve raises before anything is queued) 
 takes the values as rhs(t, state, delayed=[...]) and lists (species index, delay) per read as rhs.delays; the integration loop
 that looks them up is the caller's (tests/modelgen_delay_models.py has the float64 definition).
 
+Process noise.  Well-to-well scatter that enters the state and is propagated by the dynamics -- intrinsic fluctuations of
+expression and growth -- is neither observation noise nor a parameter: the model is dX = f dt + g dW.  A class may define
+
+        def diffusion(self, y, p, c):                # -> one amplitude per species, like rhs; 0.0 for a species without noise
+            return [p.sigma * sqrt(maximum(y.X, 0.0)), 0.0, ...]
+
+Diagonal Ito noise: one independent Wiener process per species.  For every step the scheme takes -- every sub-step when
+substeps > 1 -- from the state u over a step of length h,  u' = Phi_h(u) + g(u, p) * (sqrt(h) * xi),  Phi the unchanged step of
+the chosen fixed-grid solver, g evaluated at the step's START state, xi ~ N(0,1) per species, h the length the scheme itself
+advances by (modeuler: its fixed step, as the step uses it; every other solver: t1 - t0).  This is Euler-Maruyama for euler;
+for the other schemes it is a drift / noise splitting of the same strong order 1/2 (the drift's higher order buys nothing
+pathwise).  The noise path is sampled from its prior: it is not a variational parameter, so the IWAE bound gains no term -- the
+bound averages over the path as it does over theta's samples.  The hook has no t and is read-only; a forcing reads the sample
+of the interval's first point, as in jump.  The struct gains HAS_DIFFUSION, NOISE_MASK, diffusion(y, p, g) and
+diffusion_vjp(y, p, gb, yb, pb) (reverse mode, forward values recomputed, it adds); a species whose amplitude folds to the
+constant 0 draws nothing and has no adjoint.  The draws are stored nowhere (csrc/vihds_sde.hpp): xi of species q at step
+k * substeps + j of trajectory b * S + s is normal q & 3 of the Philox4x32-10 block at the counter (b * S + s, q >> 2,
+k * substeps + j, a non-zero tag -- the theta stream has 0 there), keyed by two 24-bit words per data row that travel as the
+last two floats of the row of cond: [n_conditions | K x T | key lo, key hi].  The adjoint regenerates each draw from its
+counter (gb = lam' sqrt(h) xi, diffusion_vjp, the scheme's step adjoint, lam += yb): no atomics, gradients repeat bit for bit.
+row_inputs appends the key columns and cond_width counts them.  A batch may carry 'noise_key' (one pair of ints or [rows, 2],
+each in [0, 2^24), checked on the host); without it the model keeps a two-word state on the device, seeded from the class
+attribute noise_seed: in training mode row_inputs reads it and advances it in place (a captured step draws afresh on every
+replay; the counter wraps at 2^24 into the second word), in evaluation mode the key is the seed's, so evaluations repeat.
+The state is the buffer noise_key_state: it is saved in state_dict (a resumed run continues the stream), moved by Module.to, and
+moved as it stands -- never seeded again -- when a batch arrives on another device.  The hook's record, DIFFUSION_HOOK, stands
+beside HOOKS and ALL_HOOKS rather than inside HOOKS: those two tuples are pinned by earlier tests as the per-time-point hooks and
+the start map, and this hook is called per step of the scheme; TRACED_HOOKS = ALL_HOOKS + (DIFFUSION_HOOK,) is what tracing, code
+generation and the capture of the definitions walk.
+One trap: the derivative of sqrt is infinite at 0, so a species with the amplitude sigma * sqrt(maximum(y, 0.0)) that starts at
+0 (or is driven there) has a gradient that is not finite, and the training step skips its update; start it above 0 or put a
+floor under the root, sqrt(maximum(y, 0.0) + eps).
+Combines with forcings, substeps, jump, start, the three observation hooks and the piecewise operations.  Refused at class
+definition, each with its reason: implicit = True, networks, NeuralPrecisions, algebraic, delays, lead_in > 0, a wrong arity
+(there is no t to read) or a wrong number of returned values.  Such a model takes the fixed-grid solvers only (solve and
+ops.OdeProblemSpec raise NotImplementedError before anything is built or queued; the library answers VIHDS_E_UNSUPPORTED).
+Open: non-diagonal noise, Milstein or Stratonovich schemes, drift-implicit steps, the refused combinations, S sharded over
+ranks (the trajectory index is the launch's), noise in the lead-in.  torch_diffusion restates the hook with torch ops;
+tests/modelgen_sde_models.py has the float64 definition of the scheme, which takes the draws as an argument.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -1183,12 +1223,14 @@ class Hook(object):
       none_resets        `name = None` in a subclass returns to the kernels' default
       checks_arguments   the definition must take exactly the arguments of the signature (more with defaults, and
                          keyword-only helpers, are the author's own)
-      settle             called for every subclass after the capture"""
+      settle             called for every subclass after the capture
+      skips_zero         an output that folds to the constant 0 is not written and its seed is not read; the struct declares
+                         NOISE_MASK, bit j set for every output that is left (process noise)"""
 
     switch_note = excludes_neural = settle = None
     note = ""
     n_outputs = 4
-    hides_method = none_resets = checks_arguments = False
+    hides_method = none_resets = checks_arguments = skips_zero = False
 
     def __init__(self, name, **fields):
         self.name = name
@@ -1256,8 +1298,25 @@ HOOKS = (
          note=": it sees the species at one time point (the left limit), the effective parameters and the treatments -- no t "
               "(or None in a subclass, for no jump)"),
 )
+# process noise: called once per step of the scheme (every sub-step), on the step's start state -- not once per time point, so it
+# is a record of its own beside HOOKS, as the start map is (TRACED_HOOKS, below, is what tracing, code generation and the capture
+# of the definitions walk); sees the species, the effective parameters and the treatments -- no t; a forcing reads the sample of
+# the interval's first point, as jump does.  It returns one noise amplitude per species; one that folds to the constant 0 is not
+# written, draws nothing and has no adjoint (skips_zero: the struct's NOISE_MASK says which are left)
+DIFFUSION_HOOK = \
+    Hook("diffusion", signature="diffusion(self, y, p, c)", groups=("y",),
+         outputs="the noise amplitude of each species, one value per species; 0.0 for a species without noise",
+         n_outputs="species", attr="_diffusion_def", traced="dif", c_out="g", seed="gb",
+         switch="HAS_DIFFUSION", switch_note="process noise, u' = Phi_h(u) + g(u) sqrt(h) xi per step: diffusion / diffusion_vjp (vihds_sde.hpp)",
+         c_forward=["  __device__ static void diffusion(const float* y, const float* p, float* g) {"],
+         c_adjoint=["  __device__ static void diffusion_vjp(const float* y, const float* p, const float* gb, float* yb, float* pb) {"],
+         excludes_neural="process noise", none_resets=True, checks_arguments=True, skips_zero=True,
+         note=": it sees the species at a step's start, the effective parameters and the treatments -- no t "
+              "(or None in a subclass, for no process noise)")
+
 ALL_HOOKS = (START_HOOK,) + HOOKS  # in the order in which the forward kernel calls them
-HOOK = {h.name: h for h in ALL_HOOKS}
+TRACED_HOOKS = ALL_HOOKS + (DIFFUSION_HOOK,)  # ... and the hook of the scheme's step behind them
+HOOK = {h.name: h for h in TRACED_HOOKS}
 
 
 class Trace(object):
@@ -1350,7 +1409,7 @@ class Trace(object):
                     cls.__name__, name, "no derivative depends on its outputs" if name in self._called
                     else "never called in rhs"))
         # the hooks (optional) see their groups of leaves, the effective parameters and the treatments
-        for h in ALL_HOOKS:
+        for h in TRACED_HOOKS:
             setattr(self, h.traced, None)
             definition = getattr(cls, h.attr, None)
             if definition is not None:
@@ -1361,7 +1420,7 @@ class Trace(object):
                     raise ModelDefinitionError("%s.%s must return a list of %d entries (%s)"
                                                % (cls.__name__, h.name, h.count(N), h.outputs))
                 setattr(self, h.traced, [g._arg(x) for x in out])
-        used = {n.val for n in _topo(self.dy + [x for h in ALL_HOOKS for x in getattr(self, h.traced) or []]
+        used = {n.val for n in _topo(self.dy + [x for h in TRACED_HOOKS for x in getattr(self, h.traced) or []]
                                      + (self.z0 or []) + (self.con or [])) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
@@ -1587,7 +1646,7 @@ def generate_source(cls, neural=False):
     recomputed inside them) and the switches csrc/generated/ode_generated_model.hip reads.  Deterministic: the same
     definition gives byte-identical text; its hash (with the kernel headers') names the library."""
     tr = cls._trace
-    for h in ALL_HOOKS:
+    for h in TRACED_HOOKS:
         if neural and h.excludes_neural and getattr(tr, h.traced) is not None:
             raise ModelDefinitionError("%s defines %s: a model with a %s of its own does not take NeuralPrecisions"
                                        % (cls.__name__, h.signature, h.excludes_neural))
@@ -1718,16 +1777,23 @@ def generate_source(cls, neural=False):
         net_decl = []
     # the hooks a model defines: value and adjoint run once per time point inside the time loop
     hook_decl = []
-    for h in ALL_HOOKS:
+    for h in TRACED_HOOKS:
         outs = getattr(tr, h.traced)
         if outs is None:
             continue
-        adj = vjp(g, outs, [g.leaf("seed", j) for j in range(h.count(N))])
+        kept = [(j, e) for j, e in enumerate(outs) if not (h.skips_zero and _is_const(e, 0.0))]
+        if not kept:
+            raise ModelDefinitionError("%s.%s returns the constant 0 for every species: a model without noise defines no %s"
+                                       % (cls.__name__, h.name, h.name))
+        adj = vjp(g, [e for _j, e in kept], [g.leaf("seed", j) for j, _e in kept])
         if h.switch_note:
             hook_decl.append("  static constexpr bool %s = true;  // %s" % (h.switch, h.switch_note))
+        if h.skips_zero:
+            hook_decl.append("  static constexpr unsigned NOISE_MASK = 0x%xu;  // bit j: species j has noise (%s)" % (
+                sum(1 << j for j, _e in kept), ", ".join(cls.species[j] for j, _e in kept)))
         with_z = reads_z(outs)  # (observe alone may: a class without algebraic variables emits what it emitted before)
         hook_decl += h.c_forward + (solve_z(f_at_point) if with_z else []) + [
-            body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in enumerate(outs)], True, h.seed, tr.c_slot, f_at_point), "  }"]
+            body([("%s[%d]" % (h.c_out, j), "=", e) for j, e in kept], True, h.seed, tr.c_slot, f_at_point), "  }"]
         hook_decl += h.c_adjoint + (solve_z(f_at_point) + ["    float zb[%d];" % M] if with_z else []) + [
             body(pull(adj, h.targets) + (pull_z(adj) if with_z else []), True, h.seed, tr.c_slot, f_at_point)] + (
             ["    algebraic_vjp(y, z, p, u, zb, yb, pb);"] if with_z else []) + ["  }"]
@@ -1992,6 +2058,8 @@ def register_kernel(cls, neural=False):
         hip.GENERATED_START.add(key)
     if cls.lead_in > 0:  # (a lead-in phase: the fixed-grid schemes only, likewise)
         hip.GENERATED_LEAD_IN[key] = (float(cls.lead_in), int(cls.lead_in_steps))
+    if cls._trace.dif is not None:  # (process noise: the fixed-grid schemes only; a row of cond ends with its noise key)
+        hip.GENERATED_DIFFUSION.add(key)
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -2014,6 +2082,8 @@ class GeneratedOdeModel(OdeModel):
     observe_kind = "default"
     _observe_def = _precision_def = _likelihood_def = _jump_def = None  # the definitions of the hooks the class has (HOOKS: attr)
     _start_def = None  # ... and of its start map (START_HOOK)
+    _diffusion_def = None  # ... and of its process noise (HOOKS: diffusion)
+    noise_seed = 0  # the seed of the noise key a model with process noise keeps on the device (module docstring), 0 .. 2^48 - 1
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
     delays = None  # {name: (species, effective parameter)}: delayed reads, self.delayed.<name> in rhs (module docstring)
@@ -2037,7 +2107,7 @@ class GeneratedOdeModel(OdeModel):
             cls.parameter_names = list(declared)
             del cls.parameters
         # ... and its hooks (HOOKS says how each is taken from the class body)
-        for h in ALL_HOOKS:
+        for h in TRACED_HOOKS:
             definition = cls.__dict__.get(h.name)
             if definition is not None:
                 ok = callable(definition)
@@ -2072,6 +2142,13 @@ class GeneratedOdeModel(OdeModel):
         if type(self)._precision_def is not None:  # the model's own precision map: the rows the kernel stores behind the species
             from vihds.precisions import ModelPrecisions
             self.precisions = ModelPrecisions()
+        if type(self)._diffusion_def is not None:
+            # process noise: the two-word key state a training step reads and advances (a persistent buffer: checkpoints keep the
+            # stream's position) and the fixed key of evaluation passes (derived from the seed: not saved)
+            seed = int(type(self).noise_seed)
+            words = torch.tensor([float(seed % NOISE_KEY_WORD), float((seed // NOISE_KEY_WORD) % NOISE_KEY_WORD)], dtype=torch.float32)
+            self.register_buffer("noise_key_state", words.clone())
+            self.register_buffer("noise_eval_key", words, persistent=False)
         # the networks' weights (created under the seed the caller set for the whole model, like every module here): the
         # weight matrices as the reference's NeuralStates initialises them, the biases nn.Linear's default
         nets = _class_networks(type(self))
@@ -2089,6 +2166,48 @@ class GeneratedOdeModel(OdeModel):
 
     # forcings: the samples travel in the rows of cond, behind the treatments
     def row_inputs(self, data):
+        rows = self._forcing_rows(data)
+        if type(self)._diffusion_def is None:
+            return rows
+        # process noise: the two words of the row's key close the row (csrc/vihds_sde.hpp)
+        key = data.get("noise_key", None) if hasattr(data, "get") else getattr(data, "noise_key", None)
+        B = rows.shape[0]
+        if key is not None:  # (the batch's own: checked on the host, then uploaded)
+            cols = noise_key_rows(key, B).to(rows.device, rows.dtype)
+        else:
+            cols = self._next_noise_key(rows.device).to(rows.dtype)[None, :].expand(B, NOISE_KEY_COLUMNS)
+        return torch.cat([rows, cols], dim=1)
+
+    def _next_noise_key(self, device):
+        """The key [2] of a batch without 'noise_key'.  Training mode: the model's two-word state on the device, then advanced
+        by one with in-place torch operations (lo + 1, carried into hi, both modulo 2^24) -- a captured step therefore draws
+        afresh on every replay.  Evaluation mode: the seed's key, fixed, so evaluations repeat."""
+        state = self.noise_state(device)
+        if not self.training:
+            return self.noise_eval_key
+        key = state.clone()
+        with torch.no_grad():
+            state[0].add_(1.0)
+            carry = (state[0] >= float(NOISE_KEY_WORD)).to(state.dtype)
+            state[0].sub_(carry * float(NOISE_KEY_WORD))
+            state[1].add_(carry)
+            state[1].sub_((state[1] >= float(NOISE_KEY_WORD)).to(state.dtype) * float(NOISE_KEY_WORD))
+        return key
+
+    def noise_state(self, device):
+        """The model's two-word key state on `device` (float32 [2]): what a training step's row_inputs reads and advances.  It is
+        the buffer `noise_key_state`, seeded from noise_seed when the model is built: part of state_dict (a resumed run continues the
+        stream) and moved by Module.to like every buffer; asked for on another device it is moved there as it stands (never
+        seeded again), together with the evaluation key.  Training's capture warm-up snapshots and rolls it back with the other
+        device-side generator states."""
+        state = self._buffers["noise_key_state"]
+        moved = state.to(device)  # (the tensor itself where it is there already: nothing is allocated)
+        if moved is not state:
+            self._buffers["noise_key_state"] = moved
+            self._buffers["noise_eval_key"] = self._buffers["noise_eval_key"].to(device)
+        return self._buffers["noise_key_state"]
+
+    def _forcing_rows(self, data):
         K = len(_class_forcings(type(self)))
         if not K:
             return data.inputs
@@ -2107,7 +2226,7 @@ class GeneratedOdeModel(OdeModel):
         if K and n_times is None:
             raise RuntimeError("%s declares forcings: the width of a row of cond depends on the number of time points"
                                % type(self).__name__)
-        return self.n_treatments + (K * int(n_times) if K else 0)
+        return self.n_treatments + (K * int(n_times) if K else 0) + _noise_key_columns(type(self))
 
     def solve(self, config, times, theta, conditions, dev_1hot, observations=None, request=None):
         if config.params.solver in hip.IMPLICIT_SOLVERS and not type(self).implicit:  # (before anything is built or queued)
@@ -2138,6 +2257,14 @@ class GeneratedOdeModel(OdeModel):
                 "%s declares delays, which read the trajectory stored on the observation grid: the adaptive solver '%s' "
                 "integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
                     type(self).__name__, config.params.solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if type(self)._diffusion_def is not None:  # (likewise)
+            if config.params.solver in hip.ADAPTIVE_SOLVERS:
+                raise NotImplementedError(
+                    "%s defines diffusion(self, y, p, c), process noise drawn once per step of a fixed-grid scheme on the "
+                    "observation grid: the adaptive solver '%s' chooses its own steps and is not available to it (fixed-grid "
+                    "solvers: %s)" % (type(self).__name__, config.params.solver,
+                                      ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+            _check_forcing_width(type(self), conditions.shape[1], len(times), self.n_treatments)
         K = len(_class_forcings(type(self)))
         if K:  # (checked before anything is built or queued)
             if config.params.solver in hip.ADAPTIVE_SOLVERS:
@@ -2167,6 +2294,11 @@ class GeneratedOdeModel(OdeModel):
     def has_jump(self):
         """True for a model with a state jump at the observation points (module docstring)."""
         return type(self)._jump_def is not None
+
+    @property
+    def has_diffusion(self):
+        """True for a model with process noise, diffusion(self, y, p, c) (module docstring)."""
+        return type(self)._diffusion_def is not None
 
     @property
     def has_start(self):
@@ -2457,6 +2589,17 @@ class GeneratedOdeModel(OdeModel):
         return _hook_torch(cls, HOOK["jump"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond)
 
     @classmethod
+    def torch_diffusion(cls, y, theta, cond, n_times=None):
+        """The model's own noise amplitudes with torch ops in y's dtype (the float64 reference of the generated diffusion /
+        diffusion_vjp, as torch_jump is for the jump): y [B,S,N,T] species at the start of steps (one column per time point:
+        the step that starts at point k reads forcing sample k), theta {parameter name: [B,S]} -- prepare is applied to it
+        first -- and cond [B,C] as the kernels take it, the two key columns last (n_times: how many samples a forcing series
+        has where y holds another number of columns) -> the amplitudes [B,S,N,T]; 0 for a species without noise."""
+        if cls._diffusion_def is None:
+            raise ModelDefinitionError("%s defines no diffusion(self, y, p, c): its trajectories are deterministic" % cls.__name__)
+        return _hook_torch(cls, HOOK["diffusion"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond, n_times)
+
+    @classmethod
     def torch_start(cls, y, theta, cond, n_times=None):
         """The model's own start map with torch ops in y's dtype (the float64 reference of the generated start / start_vjp): y
         [B,S,N] what initial_state returned, theta {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as
@@ -2529,20 +2672,54 @@ def _treatments_torch(cls, cond, like, S):
     return [torch.transpose(tt[:, q].repeat([S, 1]), 0, 1) for q in range(C)]
 
 
+NOISE_KEY_COLUMNS = 2  # floats of a row of cond behind the forcing samples of a model with process noise: key lo, key hi
+NOISE_KEY_WORD = 1 << 24  # each an integer-valued float in [0, 2^24) (csrc/vihds_sde.hpp converts by truncation)
+
+
+def _noise_key_columns(cls):
+    return NOISE_KEY_COLUMNS if getattr(cls, "_diffusion_def", None) is not None else 0
+
+
+def noise_key_rows(key, n_rows):
+    """The two key columns [n_rows, 2] (float32, on the host) of a batch's 'noise_key': one pair of ints for every row, or
+    [n_rows, 2]; each word an integer in [0, 2^24).  Checked here, before anything is uploaded."""
+    if isinstance(key, torch.Tensor):
+        key = key.detach().cpu().numpy()
+    try:
+        k = np.asarray(key).astype(np.float64)
+    except (TypeError, ValueError):
+        k = np.empty(0)
+    if k.size == 0 or not np.all(np.isfinite(k)) or np.any(k != np.floor(k)):
+        raise ValueError("noise_key must hold integers (one pair, or [rows, 2]), got %r" % (key,))
+    k = k.astype(np.int64)
+    if k.shape == (2,):
+        k = np.broadcast_to(k, (n_rows, 2))
+    if k.shape != (n_rows, 2):
+        raise ValueError("noise_key must be one pair of ints or [%d rows, 2], got shape %s" % (n_rows, list(np.shape(key))))
+    if k.min() < 0 or k.max() >= NOISE_KEY_WORD:
+        raise ValueError("noise_key: each word is an integer in [0, 2^24) (it travels as a float32 of cond), got %d .. %d"
+                         % (k.min(), k.max()))
+    return torch.from_numpy(np.ascontiguousarray(k, dtype=np.float32))
+
+
 def _check_forcing_width(cls, width, n_times, n_treatments=None):
     """A row of cond is [treatments | K x T samples].  n_treatments: how many treatments the rows hold (an instance knows: its
     data may carry more than the n_conditions the model reads); None: at least the model's n_conditions."""
     K, C = len(_class_forcings(cls)), int(cls.n_conditions) if n_treatments is None else int(n_treatments)
-    if width - C != K * n_times and (n_treatments is not None or width - K * n_times < C):
-        raise ValueError("%s reads %d forcing(s) on %d time points: a row of cond must hold %d samples behind its %d treatment(s), "
-                         "and holds %d (width %d)" % (cls.__name__, K, n_times, K * n_times, C, width - C, width))
+    tail = _noise_key_columns(cls)  # (the two key columns of a model with process noise close the row)
+    if width - C - tail != K * n_times and (n_treatments is not None or width - tail - K * n_times < C):
+        raise ValueError("%s reads %d forcing(s) on %d time points: a row of cond must hold %d samples behind its %d treatment(s)%s, "
+                         "and holds %d (width %d)" % (cls.__name__, K, n_times, K * n_times, C,
+                                                      " and its 2 noise-key columns behind them" if tail else "",
+                                                      width - C - tail, width))
 
 
 def _forcing_series(cls, cond, like, n_times):
     """The forcing samples of the wide cond [B, C] in `like`'s dtype: [B, K, T], the last K * T columns of each row, raw."""
     K = len(_class_forcings(cls))
     _check_forcing_width(cls, cond.shape[1], n_times)
-    return cond[:, cond.shape[1] - K * n_times:].to(like.dtype).to(like.device).reshape(cond.shape[0], K, n_times)
+    end = cond.shape[1] - _noise_key_columns(cls)
+    return cond[:, end - K * n_times:end].to(like.dtype).to(like.device).reshape(cond.shape[0], K, n_times)
 
 
 def _algebraic_torch(cls, inst, y, p, cs):
@@ -2585,7 +2762,7 @@ def _algebraic_torch(cls, inst, y, p, cs):
     return list(torch.unbind(z, dim=-1)), last
 
 
-def _hook_torch(cls, h, inst, groups, th, cond):
+def _hook_torch(cls, h, inst, groups, th, cond, n_times=None):
     """The class's definition of hook h with torch ops in the dtype of its first group: groups of [B,S,.,T] tensors (in
     the hook's order), th {parameter name: [B,S]} -- prepare is applied to it -- and cond [B,C] -> [B,S,4,T] (the hook's
     n_outputs: [B,S,N,T] for the state jump)."""
@@ -2595,7 +2772,7 @@ def _hook_torch(cls, h, inst, groups, th, cond):
     over_time = lambda v: v[:, :, None] if isinstance(v, torch.Tensor) else v  # noqa: E731
     p = _Named([(k, over_time(v)) for k, v in inst.prepare(thn, _Conditions(cs)).items()], "effective parameter")
     if _class_forcings(cls):  # the samples of every time point, [B,1,T] each
-        series = _forcing_series(cls, cond, ref, ref.shape[-1])
+        series = _forcing_series(cls, cond, ref, ref.shape[-1] if n_times is None else int(n_times))
         object.__setattr__(inst, "forcing", _Forcings(cls, lambda k, _name: series[:, k, None, :]))
     if _class_algebraic(cls):
         if h.name in _ALGEBRAIC_READERS:  # (observe: the constraint's solution at every time point's state)
@@ -2681,6 +2858,26 @@ def _validate(cls):
                 raise ModelDefinitionError("%s has delays and %s: %s -- declined in this version" % (name, what, why))
     if not isinstance(alg, (list, tuple)) or not all(isinstance(a, str) and a.isidentifier() for a in alg):
         raise ModelDefinitionError("%s.algebraic must be a list of names (valid identifiers)" % name)
+    if getattr(cls, "_diffusion_def", None) is not None:
+        # process noise: what does not combine with it in this version, each with its reason
+        for has, what, why in (
+                (cls.implicit is True, "implicit = True", "a drift-implicit step of an SDE is a scheme of its own, and the implicit "
+                                                          "step's adjoint at the stored end state does not know the noise term"),
+                (bool(nets), "networks", "the adjoint's dump of a network holds one evaluation per stage, and the noisy step's "
+                                         "adjoint evaluates the hook beside them"),
+                (bool(alg), "algebraic variables", "the amplitude would read the constraint's solution at the step's start, "
+                                                   "which only rhs and observe solve for"),
+                (bool(dl), "delays", "the stored history holds one realisation's states, and the read's adjoint does not pass "
+                                     "through the noise term"),
+                (cls.lead_in != 0, "lead_in = %r" % (cls.lead_in,), "the steps before the first observation point have no step "
+                                                                    "index in the noise stream (noise in the lead-in is open)")):
+            if has:
+                raise ModelDefinitionError("%s defines diffusion(self, y, p, c) and has %s: %s -- declined in this version"
+                                           % (name, what, why))
+        seed = cls.noise_seed
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < (1 << 48):
+            raise ModelDefinitionError("%s.noise_seed = %r; the seed of the noise key is an int, 0 .. 2^48 - 1 (two words of 24 bits)"
+                                       % (name, seed))
     if alg:
         if len(set(alg)) != len(alg):
             raise ModelDefinitionError("%s.algebraic has duplicates" % name)

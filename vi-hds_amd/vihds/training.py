@@ -652,6 +652,8 @@ class Training:
         st = getattr(ode, "_rng_state", None)
         if st is not None:
             out.append(st)
+        if getattr(ode, "has_diffusion", False):  # (the key state of a generated model with process noise, vihds/modelgen.py)
+            out.append(ode.noise_state(next(self.model.parameters()).device))
         return out
 
     def _restore_training_state(self, snap):
