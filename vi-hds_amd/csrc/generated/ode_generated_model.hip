@@ -99,7 +99,8 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
                                    net_fields<VIHDS_GEN_CORE>::value, own_prec<GenM>::value ? 1 : 0,
                                    n_forcings<GenM>::value, implicit_order<GenM>::value, substeps<GenM>::value,
                                    has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value,
-                                   n_delays<GenM>::value, has_diffusion<GenM>::value ? 1 : 0};
+                                   n_delays<GenM>::value, has_diffusion<GenM>::value ? 1 : 0,
+                                   masked_obs<GenM>::value ? 1 : 0};
   return &r;
 }
 #endif

@@ -129,6 +129,9 @@ struct ModelEntry {
   // a registered model with process noise (GenModelRecord::diffusion): a row of cond ends with its two key words, and it takes
   // the explicit fixed-grid solvers only
   bool diffusion = false;
+  // a registered model with missing observations (GenModelRecord::masked_obs): a row of cond carries T mask words behind its
+  // forcing samples (ahead of the noise key), and it takes the fixed-grid solvers only
+  bool masked_obs = false;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
   bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
   int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
@@ -184,7 +187,7 @@ static std::atomic<int> g_gen_count{0};
 static ModelEntry gen_entry_of(const GenModelRecord* r) {
   return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
           r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps, r->jump != 0,
-          r->start != 0, r->lead_in_steps, r->n_delays, r->diffusion != 0};
+          r->start != 0, r->lead_in_steps, r->n_delays, r->diffusion != 0, r->masked_obs != 0};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -285,12 +288,19 @@ static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& 
   if (e->diffusion && (solver_is_adaptive(p->solver) || solver_is_implicit(p->solver)))
     return fail(VIHDS_E_UNSUPPORTED, "the model has process noise (diffusion), drawn per step of an explicit fixed-grid scheme on the "
                                      "observation grid: an adaptive or implicit solver is not available to it");
+  if (e->masked_obs && solver_is_adaptive(p->solver))
+    return fail(VIHDS_E_UNSUPPORTED, "the model has missing observations (missing_observations), one mask word per point of the "
+                                     "observation grid: an adaptive solver integrates on a grid of its own and is not available to it");
   if (p->C < e->n_cond) return fail(VIHDS_E_BADARG, "the model reads more treatments per row than C provides");
   if (e->n_forcings > 0 && (long long)p->C < (long long)e->n_cond + (long long)e->n_forcings * p->T)
     return fail(VIHDS_E_BADARG, "the model reads n_forcings series of T samples per row behind its treatments: C is too small");
   if (e->diffusion && (long long)p->C < (long long)e->n_cond + (long long)e->n_forcings * p->T + 2)
     return fail(VIHDS_E_BADARG, "the model has process noise: a row of cond ends with the two words of its key, behind the "
                                 "treatments and the forcing samples (C >= n_cond + n_forcings * T + 2): C is too small");
+  if (e->masked_obs &&
+      (long long)p->C < (long long)e->n_cond + ((long long)e->n_forcings + 1) * p->T + (e->diffusion ? 2 : 0))
+    return fail(VIHDS_E_BADARG, "the model has missing observations: a row of cond carries T mask words behind the treatments and "
+                                "the forcing samples, ahead of the noise key (C >= n_cond + n_forcings * T + T): C is too small");
   if (p->model == VIHDS_MODEL_DR_BLACKBOX && p->n_const < p->C + p->D)
     return fail(VIHDS_E_BADARG, "dr_blackbox: n_const must cover the C treatments and the D-wide device one-hot");
   const int ns = v ? v->n_slots : e->n_slots + e->n_prec_slots();
@@ -406,7 +416,7 @@ int vihds_model_register(const char* library_path) {
       (r->lead_in_steps && r->n_net_weights > 0) || r->n_delays < 0 || r->n_delays > 4 ||
       (r->n_delays > 0 && (r->neural_prec || r->n_net_weights > 0 || r->implicit || r->substeps > 1 || r->jump ||
                            r->lead_in_steps)) ||
-      (r->diffusion != 0 && r->diffusion != 1) ||
+      (r->diffusion != 0 && r->diffusion != 1) || (r->masked_obs != 0 && r->masked_obs != 1) ||
       (r->diffusion && (r->neural_prec || r->n_net_weights > 0 || r->implicit || r->lead_in_steps || r->n_delays > 0))) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");

@@ -71,6 +71,10 @@ struct GenModelRecord {
   // data row of cond ends with the two words of its key, so a problem needs C >= n_cond + n_forcings * T + 2; the explicit
   // fixed-grid solvers only
   int diffusion;
+  // 1: the generated struct has missing observations (MASKED_OBS, vihds_models.hpp masked_obs<>; vihds_mask.hpp): a data row of
+  // cond carries one mask word per time point behind its forcing samples and ahead of the noise key, so a problem needs
+  // C >= n_cond + n_forcings * T + T (+ 2 with process noise); the fixed-grid solvers only
+  int masked_obs;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

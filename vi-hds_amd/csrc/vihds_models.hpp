@@ -1071,10 +1071,23 @@ template <class M, class = void>
 struct has_diffusion : std::false_type {};
 template <class M>
 struct has_diffusion<M, std::void_t<decltype(M::HAS_DIFFUSION)>> : std::bool_constant<M::HAS_DIFFUSION> {};
-// floats of a row of cond behind the forcing samples: the two key words of such a model (vihds_sde.hpp), none otherwise
+// A core generated with `missing_observations = True` (vihds/modelgen.py) declares MASKED_OBS = true: a data row of cond carries
+// one mask word per time point behind its forcing samples (vihds_mask.hpp: bit j says whether signal j has a read there), and
+// the scoring point of the forward and the adjoint time loops selects by it.  False for every hand-written model; WithPrec<>
+// forwards its core's value, so NeuralPrecisions works with such a model.
+template <class M, class = void>
+struct masked_obs : std::false_type {};
+template <class M>
+struct masked_obs<M, std::void_t<decltype(M::MASKED_OBS)>> : std::bool_constant<M::MASKED_OBS> {};
+// floats of a row of cond behind the forcing samples: the T mask words of a model with missing observations (cond_mask_words,
+// vihds_mask.hpp), then the two key words of a model with process noise (cond_tail, vihds_sde.hpp); none otherwise
 template <class M>
 constexpr int cond_tail() {
   return has_diffusion<M>::value ? 2 : 0;
+}
+template <class M>
+__host__ __device__ constexpr int cond_mask_words(int T) {
+  return masked_obs<M>::value ? T : 0;
 }
 
 // whether an adjoint context accumulates the precision network's weight gradient in registers (WeightGradCtx)
@@ -1134,6 +1147,8 @@ struct WithPrec {
     Core::set_interval(p, t_lo, inv_dt, u_lo, u_hi);
   }
   __device__ static void set_point(float* p, const float* u) { Core::set_point(p, u); }
+  // a core with missing observations: the mask words of its rows of cond are read by the time loops, not by the model
+  static constexpr bool MASKED_OBS = masked_obs<Core>::value;
   __device__ static void hidden(float t, const float* y, float* h) {
     h[0] = ftanh(t);
     VIHDS_UNROLL for (int i = 0; i < NS; ++i) h[i + 1] = ftanh(y[i]);

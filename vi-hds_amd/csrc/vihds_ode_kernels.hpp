@@ -24,6 +24,7 @@
 #include "vihds_delay.hpp"
 #include "vihds_substeps.hpp"
 #include "vihds_sde.hpp"
+#include "vihds_mask.hpp"
 #include "vihds_blackbox.hpp"
 #include "vihds_iwae_inline.hpp"
 
@@ -602,6 +603,18 @@ struct WithNoiseKey : Feed {
 };
 template <class Feed, bool ON>
 using noise_feed_t = std::conditional_t<ON, WithNoiseKey<Feed>, Feed>;
+// what the time loops keep for a model with missing observations (masked_obs<M>, vihds_mask.hpp) beside their feed: where the
+// thread's data row has its mask words -- cond[b * C + (C - cond_tail - T) + k], or the block's staged copy -- and the word
+// requested one iteration ahead, as the observations are.  Every other model's loop declares the feed alone, as it did
+// (mask_feed_t), so its code is what it was.
+template <class Feed>
+struct WithObsMask : Feed {
+  const float* msrc;  // the row's mask words in cond (the unstaged forward, the adjoint)
+  int mlds;           // ... in in_lds (the staged forward)
+  float word, word_ahead;
+};
+template <class Feed, bool ON>
+using mask_feed_t = std::conditional_t<ON, WithObsMask<Feed>, Feed>;
 // ---- forward -------------------------------------------------------------------------------------
 // LDS_IN: the time grid and the observation rows of the data rows this block spans are staged in LDS once, so the
 // time loop holds no vector-memory loads and its trajectory / x_predict stores are never waited on (see
@@ -614,12 +627,14 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   constexpr bool OWN_LIK = own_lik<M>::value;  // the log density is the model's own member (vihds_models.hpp)
   constexpr int NF = n_forcings<M>::value;     // forcings: K series of T samples per data row behind its treatments in cond
   constexpr int ND = n_delays<M>::value;       // delayed reads: looked up in the rows of traj this thread stored earlier
+  constexpr bool MASKED = masked_obs<M>::value;  // missing observations: one mask word per time point in the row of cond
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
-  extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations | [nb][NF][T] forcing samples
+  extern __shared__ float in_lds[];  // [T] times | [nb][4][T] observations | [nb][NF][T] forcing samples | [nb][T] mask words
   const float* wts = stage_weights<M>(a, wlds);
   int ob_off = 0;
-  // (ForcingFeed<NF>; a model with delayed reads also keeps y_0 and its cursors, one with process noise its key)
-  noise_feed_t<delay_feed_t<ForcingFeed<NF>, ND>, has_diffusion<M>::value> ff;
+  // (ForcingFeed<NF>; a model with delayed reads also keeps y_0 and its cursors, one with process noise its key, one with
+  // missing observations its mask words)
+  mask_feed_t<noise_feed_t<delay_feed_t<ForcingFeed<NF>, ND>, has_diffusion<M>::value>, MASKED> ff;
   if (LDS_IN) {
     const int first = blockIdx.x * blockDim.x, last = min(first + (int)blockDim.x, a.n) - 1;
     const int b0 = first / a.S, nb = last / a.S - b0 + 1;
@@ -628,14 +643,20 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     for (int q = threadIdx.x; q < nb * 4 * a.T; q += blockDim.x) in_lds[a.T + q] = src[q];
     if constexpr (NF > 0) {  // (a row's samples are contiguous, the rows are C apart)
       const int per_row = NF * a.T, f_base = a.T + nb * 4 * a.T;
-      const float* fsrc = a.cond + (size_t)b0 * a.C + (a.C - cond_tail<M>() - per_row);
+      const float* fsrc = a.cond + (size_t)b0 * a.C + (a.C - cond_tail<M>() - cond_mask_words<M>(a.T) - per_row);
       for (int q = threadIdx.x; q < nb * per_row; q += blockDim.x)
         in_lds[f_base + q] = fsrc[(size_t)(q / per_row) * a.C + q % per_row];
+    }
+    if constexpr (MASKED) {  // (a row's T words are contiguous behind its forcing samples, the rows are C apart)
+      const int m_base = a.T + nb * (4 + NF) * a.T;
+      const float* msrc = a.cond + (size_t)b0 * a.C + (a.C - cond_tail<M>() - a.T);
+      for (int q = threadIdx.x; q < nb * a.T; q += blockDim.x) in_lds[m_base + q] = msrc[(size_t)(q / a.T) * a.C + q % a.T];
     }
     __syncthreads();
     const int ii = min((int)(blockIdx.x * blockDim.x + threadIdx.x), a.n - 1);
     ob_off = a.T + (ii / a.S - b0) * 4 * a.T;
     if constexpr (NF > 0) ff.lds = a.T + nb * 4 * a.T + (ii / a.S - b0) * NF * a.T;
+    if constexpr (MASKED) ff.mlds = a.T + nb * (4 + NF) * a.T + (ii / a.S - b0) * a.T;
   }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
@@ -674,11 +695,17 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   VIHDS_UNROLL for (int j = 0; j < 4; ++j) { obc[j] = a.logp ? obs_at(j, 0) : 0.f; obn[j] = 0.f; }
   // forcing samples travel with the times: ff.lo / ff.hi at tA / tB, the next point's requested one iteration ahead like tC
   if constexpr (NF > 0) {
-    ff.src = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - NF * a.T);
+    ff.src = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - cond_mask_words<M>(a.T) - NF * a.T);
     VIHDS_UNROLL for (int j = 0; j < NF; ++j) {
       ff.lo[j] = LDS_IN ? in_lds[ff.lds + j * a.T] : ff.src[j * a.T];
       ff.hi[j] = LDS_IN ? in_lds[ff.lds + j * a.T + 1] : ff.src[j * a.T + 1];
     }
+  }
+  // mask words travel with the observations: ff.word at the current point, the next point's requested one iteration ahead
+  if constexpr (MASKED) {
+    ff.msrc = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - a.T);
+    ff.word = LDS_IN ? in_lds[ff.mlds] : ff.msrc[0];
+    ff.word_ahead = ff.word;
   }
   if constexpr (has_start<M>::value || lead_in<M>::value > 0) {
     // where the trajectory starts, for a generated model that says so (a branch of its own: every other model's code stays what
@@ -707,6 +734,9 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     const float tC = (k + 1 < a.T) ? time_at(k + 1) : tB;
     if (a.logp && k + 1 < a.T) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) obn[j] = obs_at(j, k + 1);
+    }
+    if constexpr (MASKED) {
+      if (k + 1 < a.T) ff.word_ahead = LDS_IN ? in_lds[ff.mlds + k + 1] : ff.msrc[k + 1];
     }
     if constexpr (NF > 0) {
       VIHDS_UNROLL for (int j = 0; j < NF; ++j) {
@@ -762,7 +792,44 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     if (a.xpred) {
       VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.xpred[((size_t)k * 4 + j) * n + i] = xp[j];
     }
-    if constexpr (OWN_LIK) {
+    if constexpr (MASKED) {
+      // missing observations (vihds_mask.hpp; a branch of its own: every other model's code stays what it was).  The three
+      // branches below in one: the precisions are the model's own map's (stored behind the species as there), the precision
+      // states or the constant slots; every term is formed from obu = ob', the read where the point's mask word has one and the
+      // predicted signal where it has none -- the placeholder never enters the arithmetic --, and joins lp by a select
+      const ObsMask om(ff.word);
+      ff.word = ff.word_ahead;
+      float prl[4];
+      if constexpr (OWN_PREC) {
+        M::precision(y, xp, p, prl);
+        if (a.traj) {
+          if (nt_traj) {
+            VIHDS_UNROLL for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(prl[j], &a.traj[((size_t)k * NT + N + j) * n + i]);
+          } else {
+            VIHDS_UNROLL for (int j = 0; j < 4; ++j) a.traj[((size_t)k * NT + N + j) * n + i] = prl[j];
+          }
+        }
+      } else {
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) prl[j] = M::NEURAL_PREC ? y[(M::N - 4) + j] : prec[j];
+      }
+      if (a.logp) {
+        float obu[4], ll[4];
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) obu[j] = om.read(j, obc[j], xp[j]);
+        if constexpr (OWN_LIK) {
+          M::loglik(xp, obu, prl, p, ll);
+        } else {
+          VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+            const float e = xp[j] - obu[j];
+            if (OWN_PREC || M::NEURAL_PREC) ll[j] = -0.5f * (LOG2PI_F - logf(prl[j]) + prl[j] * e * e);
+            else ll[j] = -0.5f * (lc[j] + prl[j] * e * e);
+          }
+        }
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+          lp[j] += om.gate(j, ll[j]);
+          obc[j] = obn[j];
+        }
+      }
+    } else if constexpr (OWN_LIK) {
       // an observation log density of the model's own (a branch of its own: every other model's code stays what it was).  Its
       // precisions are the constant slots, or the values of the model's own map, which are stored as in the branch below
       float prl[4];
@@ -994,6 +1061,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   constexpr bool OWN_LIK = own_lik<M>::value;  // the log density's adjoint is the model's own member (vihds_models.hpp)
   constexpr int NF = n_forcings<M>::value;     // forcings: K series of T samples per data row behind its treatments in cond
   constexpr int ND = n_delays<M>::value;       // delayed reads: looked up in traj_in, their adjoint scattered into aux
+  constexpr bool MASKED = masked_obs<M>::value;  // missing observations: one mask word per time point in the row of cond
   __shared__ float wlds[M::NW > 0 ? M::NW : 1];
   const float* wts = stage_weights<M>(a, wlds);
   const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1034,8 +1102,13 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   // forcing samples travel with the times: ff.hi at tHi, ff.lo at tK, the next lower point's (ff.ahead) requested one
   // iteration ahead like tLo
   // (ForcingFeed<NF>; an implicit solver's also keeps y_k+1, a model with delayed reads y_0 and its cursors, one with process
-  // noise its key)
-  noise_feed_t<delay_feed_t<bwd_feed_t<NF, N, solver_is_implicit(SOLVER)>, ND>, has_diffusion<M>::value> ff;
+  // noise its key, one with missing observations its mask words)
+  mask_feed_t<noise_feed_t<delay_feed_t<bwd_feed_t<NF, N, solver_is_implicit(SOLVER)>, ND>, has_diffusion<M>::value>, MASKED> ff;
+  // mask words travel with the observations: the word of the point k - 1 (ff.word_ahead) requested one iteration ahead like obn
+  if constexpr (MASKED) {
+    ff.msrc = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - a.T);
+    ff.word_ahead = ff.msrc[a.T - 1];
+  }
   if constexpr (ND > 0) {
     // the history adjoint A[entry][T] of this trajectory: its own column of aux, zeroed here and touched by no other thread
     // (a tail lane shadows the last trajectory: it reads that column and never writes it)
@@ -1049,7 +1122,7 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   }
   if constexpr (has_diffusion<M>::value) ff.key = sde_load_key(a.cond, a.C, b, i);
   if constexpr (NF > 0) {
-    ff.src = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - NF * a.T);
+    ff.src = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - cond_mask_words<M>(a.T) - NF * a.T);
     VIHDS_UNROLL for (int j = 0; j < NF; ++j) { ff.ahead[j] = ff.src[j * a.T + a.T - 1]; ff.hi[j] = ff.ahead[j]; }
   }
   for (int k = a.T - 1; k >= 0; --k) {
@@ -1059,6 +1132,10 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     const float tK = tLo;
     if constexpr (NF > 0) {
       VIHDS_UNROLL for (int j = 0; j < NF; ++j) ff.lo[j] = ff.ahead[j];
+    }
+    if constexpr (MASKED) {
+      ff.word = ff.word_ahead;
+      if (k > 0) ff.word_ahead = ff.msrc[k - 1];
     }
     if (k > 0) {
       VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(k - 1) * NT + j) * n + i];
@@ -1179,7 +1256,45 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     float xp[4], xpb[4];
     if constexpr (M::OBS == OBS_CUSTOM) M::observe(y, p, xp);
     else observe<M::OBS>(y, xp);
-    if constexpr (OWN_LIK) {
+    if constexpr (MASKED) {
+      // missing observations (vihds_mask.hpp; a branch of its own: every other model's code stays what it was).  The three
+      // branches below in one, in their order of adjoints: the residuals are formed from obu = ob', as the forward's were, and the
+      // log-likelihood's seed of an unobserved signal is 0 by a select; what arrives for x_predict and for the precision rows of
+      // the trajectory is not masked.  On the in-kernel importance-weight route glp holds the trajectory's weight as before
+      const ObsMask om(ff.word);
+      float prl[4], prb4[4], obu[4], sd[4];
+      if constexpr (OWN_PREC) {
+        M::precision(y, xp, p, prl);
+      } else {
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) prl[j] = M::NEURAL_PREC ? y[(M::N - 4) + j] : prec[j];
+      }
+      VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+        obu[j] = om.read(j, obk[j], xp[j]);
+        sd[j] = om.gate(j, glp[j]);
+        xpb[j] = 0.f;
+        prb4[j] = 0.f;
+      }
+      if constexpr (OWN_LIK) {
+        if (a.g_logp || a.iw_logp) M::loglik_vjp(xp, obu, prl, p, sd, xpb, prb4, pb);  // (skipped as below where no gradient arrives)
+      } else {
+        VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+          const float e = xp[j] - obu[j];
+          xpb[j] = -sd[j] * prl[j] * e;
+          prb4[j] = sd[j] * (0.5f / prl[j] - 0.5f * e * e);
+        }
+      }
+      VIHDS_UNROLL for (int j = 0; j < 4; ++j) {
+        if constexpr (OWN_PREC) {
+          if (a.g_traj) prb4[j] += a.g_traj[((size_t)k * NT + N + j) * n + i];
+        } else if constexpr (M::NEURAL_PREC) {
+          lam[(M::N - 4) + j] += prb4[j];
+        } else {
+          precb[j] += prb4[j];
+        }
+        if (a.g_xpred) xpb[j] += a.g_xpred[((size_t)k * 4 + j) * n + i];
+      }
+      if constexpr (OWN_PREC) M::precision_vjp(y, xp, p, prb4, lam, xpb, pb);
+    } else if constexpr (OWN_LIK) {
       // an observation log density of the model's own (a branch of its own: every other model's code stays what it was).
       // Three adjoints in this order: the log density's (seeded with glp; it adds into xpb, prb4 and pb), then the precision
       // map's where the model has one (prb4 plus what arrives for the precision rows of the trajectory; into lam, xpb and
@@ -1335,6 +1450,7 @@ inline void launch_fwd_s(const OdeArgs& a, hipStream_t st) {
   const int nb = min(a.B, (blk - 1) / a.S + 2);
   size_t lds = ((size_t)a.T + (size_t)nb * 4 * a.T) * sizeof(float);
   lds += (size_t)nb * n_forcings<M>::value * a.T * sizeof(float);  // (the rows' forcing samples behind the observations)
+  lds += (size_t)nb * cond_mask_words<M>(a.T) * sizeof(float);     // (... and the mask words of a model with missing observations)
   if (lds <= 32 * 1024)
     hipLaunchKernelGGL((ode_fwd_kernel<M, SOLVER, true>), dim3((a.n + blk - 1) / blk), dim3(blk), lds, st, a);
   else
@@ -1408,7 +1524,7 @@ template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
   if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value || has_start<M>::value ||
-                lead_in<M>::value > 0 || n_delays<M>::value > 0 || has_diffusion<M>::value) {
+                lead_in<M>::value > 0 || n_delays<M>::value > 0 || has_diffusion<M>::value || masked_obs<M>::value) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
     // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it.  A model with sub-steps
@@ -1416,7 +1532,8 @@ inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t s
     // jump likewise: the jump is applied between two intervals of the observation grid, which only these time loops walk.  A
     // model with a start map or a lead-in phase likewise: only these kernels call start and run the steps before t_0.  A model
     // with delayed reads likewise: its history is the trajectory these kernels store on the observation grid.  A model with
-    // process noise likewise: its draws are counted by the steps of the observation grid (vihds_sde.hpp)
+    // process noise likewise: its draws are counted by the steps of the observation grid (vihds_sde.hpp).  A model with missing
+    // observations likewise: its mask words live on the observation grid (vihds_mask.hpp)
     if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
 #define VIHDS_CASE(SV)                                           \
   case SV:                                                       \

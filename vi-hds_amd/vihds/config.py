@@ -133,7 +133,7 @@ def get_results_directory():
 def apply_defaults_data(config):
     out = attrify({
         "groups": {"default": [0] * len(config.devices)}, "default_devices": dict(), "normalize": None,
-        "merge": True, "subtract_background": True, "separate_conditions": False, "dtype": "float32",
+        "merge": True, "merge_tolerance": 0.0, "subtract_background": True, "separate_conditions": False, "dtype": "float32",
     })
     for k in config:
         out[k] = config[k]

@@ -59,6 +59,9 @@ GENERATED_DELAYS = {}
 # keys of registered generated models with process noise (`diffusion(self, y, p, c)`): they decline the adaptive solvers (the
 # draws are counted by the steps of the observation grid), and a row of their cond ends with the two words of its noise key
 GENERATED_DIFFUSION = set()
+# keys of registered generated models with missing observations (`missing_observations = True`): they decline the adaptive
+# solvers (the mask words live on the observation grid), and a row of their cond carries T mask words behind its forcing samples
+GENERATED_MASKED = set()
 E_UNSUPPORTED = -2  # VIHDS_E_UNSUPPORTED (include/vihds_hip.h)
 SOLVERS = {"modeuler": 0, "modeulerwhile": 1, "euler": 2, "midpoint": 3, "rk4": 4, "dopri5": 5, "bosh3": 6,
            "adaptive_heun": 7, "dopri8": 8, "beuler": 9}

@@ -340,6 +340,44 @@ Open: non-diagonal noise, Milstein or Stratonovich schemes, drift-implicit steps
 ranks (the trajectory index is the launch's), noise in the lead-in.  torch_diffusion restates the hook with torch ops;
 tests/modelgen_sde_models.py has the float64 definition of the scheme, which takes the draws as an argument.
 
+Missing observations.  Plate-reader data has dropped and saturated reads, plates of different duration and channels that a plate
+does not record; the kernels' data contract is otherwise a complete rectangle of finite reads.  A class may set
+
+        missing_observations = True                  # a bool; default False
+
+and a batch may then carry 'observed', [rows, 4, T] of 0 / 1 as bool or float, 1 where the read exists (anything else raises on
+the host: observed_mask checks shape and values wherever the data is still there -- training.batch_to_device does before it
+uploads; a tensor that is on a device already is taken as it is, reading it back would stall the queue).  Without the key every
+point counts as observed.  Defined exactly, at time point k and signal j with m = observed[j][k] and x the predicted signal:
+ob' = m ? obs[j][k] : x[j] -- the predicted signal stands in for the placeholder, the residual-0 point of any density, so what
+stands under the mask (NaN, inf, a saturated value) never enters the arithmetic --, the signal's term is formed from ob' (the
+constant-precision Gaussian, the Gaussian of NeuralPrecisions or of an own precision with its log pr part, the model's own
+log_likelihood), and logp[j] += m ? term : 0.  The adjoint seeds the point with m ? g_logp[j] : 0 and forms its residuals from
+ob'; what arrives for x_predict and the trajectory is not masked, and the in-kernel importance weight is formed as before.
+Everything is a select: nothing is multiplied by 0 and no branch depends on the data.  The trajectory, x_predict and the
+precision rows are stored at every point as before.  The struct gains one line, MASKED_OBS = true (vihds_models.hpp:
+masked_obs<M>, false for every hand-written model; WithPrec<> forwards its core's value, so NeuralPrecisions takes such a
+model); a class without the attribute generates byte for byte the text it generated before.  The mask travels in the rows of
+cond like the forcings and the noise key: [n_conditions treatments | K x T forcing samples | T mask words | key lo, key hi],
+mask word k of a row the float sum_j observed[j][k] * 2^j -- an integer 0 .. 15, exact in float32, one float per time point
+(mask_words; csrc/vihds_mask.hpp decodes it and holds the selects, __host__ __device__).  row_inputs builds the words and
+cond_width counts them; solve checks the width before anything is queued; OdeArgs and the C ABI get no field.  The staged forward
+keeps the words in LDS beside the observations, the unstaged forward and the adjoint fetch them one point ahead.  The mask is
+read at the scoring point only, so it combines with every other feature of this module.  Refused: the adaptive solvers (solve and
+ops.OdeProblemSpec raise NotImplementedError before anything is built or queued, the library answers VIHDS_E_UNSUPPORTED -- the
+words live on the observation grid, as forcing samples do); a batch with 'observed' that reaches any other model raises in
+row_inputs (a look at the batch's keys, nothing is read back).  The host paths that restate the likelihood take the mask with
+the same selects: training.log_prob_observations(..., observed=), torch_log_likelihood(..., observed=), masked_terms.  The encoder
+is not told about the mask and must never see a NaN: a dataset with missing entries stores datasets.fill_unobserved(times,
+observations, observed) -- linear interpolation in time between observed neighbours, the nearest observed value before the first
+and after the last, 0 for a signal without any -- as 'observations' and the mask as 'observed'; datasets.load_csv reads a blank or
+'nan' cell as unobserved, and the spec's data block takes merge: union (with merge_tolerance), the sorted union of the files'
+time points with each file observed at its own, where the default resamples every file onto the shortest one's grid.
+Open: masks for the built-in models' kernels (the time-parallel decoder, the lane kernels, dr_blackbox).
+An encoder that reads the mask.  Per-row time grids without a union grid.
+Skipping integration steps for rows whose remaining points are all unobserved.  Adaptive solvers for masked models.
+tests/modelgen_missing_models.py has the float64 definition.
+
 Learned terms.  A model may declare small networks and call each of them (at most once) inside rhs:
 
         networks = {"latent": Network(n_inputs=5, n_hidden=8, n_outputs=4, hidden="relu")}     # hidden: "relu" | "tanh"
@@ -1903,6 +1941,11 @@ def generate_source(cls, neural=False):
         substeps_decl += ["  static constexpr int LEAD_STEPS = %d;  // steps of the scheme over [t_0 - LEAD_TIME, t_0], nothing stored"
                           % int(cls.lead_in_steps),
                           "  static constexpr float LEAD_TIME = %s;" % _lit(cls.lead_in)]
+    # missing_observations = True: the one line the kernels' scoring points read (vihds_models.hpp masked_obs<>); none without it,
+    # likewise
+    if cls.missing_observations:
+        substeps_decl += ["  static constexpr bool MASKED_OBS = true;  // a row of cond carries one mask word per time point "
+                          "(vihds_mask.hpp)"]
     out = [
         "// Generated by vihds.modelgen from %s.%s (model_key %s): the model contract of vihds_models.hpp." % (
             cls.__module__, cls.__qualname__, key),
@@ -2060,6 +2103,8 @@ def register_kernel(cls, neural=False):
         hip.GENERATED_LEAD_IN[key] = (float(cls.lead_in), int(cls.lead_in_steps))
     if cls._trace.dif is not None:  # (process noise: the fixed-grid schemes only; a row of cond ends with its noise key)
         hip.GENERATED_DIFFUSION.add(key)
+    if cls.missing_observations:  # (missing observations: the fixed-grid schemes only; a row of cond carries its mask words)
+        hip.GENERATED_MASKED.add(key)
     _REGISTERED[key] = (cls, neural)
     return mid
 
@@ -2084,6 +2129,7 @@ class GeneratedOdeModel(OdeModel):
     _start_def = None  # ... and of its start map (START_HOOK)
     _diffusion_def = None  # ... and of its process noise (HOOKS: diffusion)
     noise_seed = 0  # the seed of the noise key a model with process noise keeps on the device (module docstring), 0 .. 2^48 - 1
+    missing_observations = False  # True: a batch may carry 'observed' [rows, 4, T], 1 where a read exists (module docstring)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
     forcings = ()  # names of the time-varying inputs, read as self.forcing.<name> (module docstring)
     delays = None  # {name: (species, effective parameter)}: delayed reads, self.delayed.<name> in rhs (module docstring)
@@ -2167,6 +2213,12 @@ class GeneratedOdeModel(OdeModel):
     # forcings: the samples travel in the rows of cond, behind the treatments
     def row_inputs(self, data):
         rows = self._forcing_rows(data)
+        observed = _batch_get(data, "observed")
+        if type(self).missing_observations:
+            # missing observations: one mask word per time point behind the forcing samples (csrc/vihds_mask.hpp)
+            rows = torch.cat([rows, self._mask_rows(data, observed, rows)], dim=1)
+        elif observed is not None:
+            raise RuntimeError(_OBSERVED_WITHOUT_MASK % (type(self).__name__, "does not set missing_observations = True"))
         if type(self)._diffusion_def is None:
             return rows
         # process noise: the two words of the row's key close the row (csrc/vihds_sde.hpp)
@@ -2177,6 +2229,16 @@ class GeneratedOdeModel(OdeModel):
         else:
             cols = self._next_noise_key(rows.device).to(rows.dtype)[None, :].expand(B, NOISE_KEY_COLUMNS)
         return torch.cat([rows, cols], dim=1)
+
+    def _mask_rows(self, data, observed, rows):
+        """The mask words [rows, T] of a batch, in the dtype and on the device of `rows`: from the batch's 'observed' [rows, 4, T]
+        (0/1 as bool or float; checked here where it is still on the host, see observed_mask), 15 everywhere without the key."""
+        B = rows.shape[0]
+        if observed is None:
+            times = _batch_get(data, "times")
+            T = int(times.shape[0]) if times is not None else int(data.observations.shape[-1])
+            return torch.full((B, T), 15.0, dtype=rows.dtype, device=rows.device)
+        return mask_words(observed_mask(observed, B)).to(rows.device, rows.dtype)
 
     def _next_noise_key(self, device):
         """The key [2] of a batch without 'noise_key'.  Training mode: the model's two-word state on the device, then advanced
@@ -2226,7 +2288,11 @@ class GeneratedOdeModel(OdeModel):
         if K and n_times is None:
             raise RuntimeError("%s declares forcings: the width of a row of cond depends on the number of time points"
                                % type(self).__name__)
-        return self.n_treatments + (K * int(n_times) if K else 0) + _noise_key_columns(type(self))
+        if type(self).missing_observations and n_times is None:
+            raise RuntimeError("%s has missing_observations = True: the width of a row of cond depends on the number of time "
+                               "points (one mask word each)" % type(self).__name__)
+        return (self.n_treatments + (K * int(n_times) if K else 0) + _mask_columns(type(self), n_times)
+                + _noise_key_columns(type(self)))
 
     def solve(self, config, times, theta, conditions, dev_1hot, observations=None, request=None):
         if config.params.solver in hip.IMPLICIT_SOLVERS and not type(self).implicit:  # (before anything is built or queued)
@@ -2264,6 +2330,14 @@ class GeneratedOdeModel(OdeModel):
                     "observation grid: the adaptive solver '%s' chooses its own steps and is not available to it (fixed-grid "
                     "solvers: %s)" % (type(self).__name__, config.params.solver,
                                       ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+            _check_forcing_width(type(self), conditions.shape[1], len(times), self.n_treatments)
+        if type(self).missing_observations:  # (likewise)
+            if config.params.solver in hip.ADAPTIVE_SOLVERS:
+                raise NotImplementedError(
+                    "%s has missing_observations = True, whose mask words live on the observation grid: the adaptive solver "
+                    "'%s' integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
+                        type(self).__name__, config.params.solver,
+                        ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
             _check_forcing_width(type(self), conditions.shape[1], len(times), self.n_treatments)
         K = len(_class_forcings(type(self)))
         if K:  # (checked before anything is built or queued)
@@ -2565,16 +2639,22 @@ class GeneratedOdeModel(OdeModel):
         return _hook_torch(cls, HOOK["precision"], inst, [y, x], theta, cond)
 
     @classmethod
-    def torch_log_likelihood(cls, x, obs, prec, theta, cond):
+    def torch_log_likelihood(cls, x, obs, prec, theta, cond, observed=None):
         """The model's own observation log density with torch ops in x's dtype (the float64 reference of the generated loglik
         / loglik_vjp): x [B,S,4,T] predicted signals, obs [B,4,T] observations, prec [B,S,4,T] precisions (anything that
         broadcasts to it), theta {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as the data
-        holds it -> the per-signal log densities of every time point [B,S,4,T] (the kernels sum them over time)."""
+        holds it -> the per-signal log densities of every time point [B,S,4,T] (the kernels sum them over time).
+        observed [B,4,T] (a class with missing_observations = True; None: every point): the density is evaluated on ob' -- the
+        read where there is one, x itself where there is none, so a placeholder never enters -- and an unobserved point's term is
+        0.0 by a select (masked_terms)."""
         if cls._likelihood_def is None:
             raise ModelDefinitionError("%s defines no log_likelihood(self, x, obs, pr, p, c): its observation log density is "
                                        "the Gaussian's" % cls.__name__)
+        if observed is not None and not cls.missing_observations:
+            raise RuntimeError(_OBSERVED_WITHOUT_MASK % (cls.__name__, "does not set missing_observations = True"))
         obs, prec = obs.to(x.dtype)[:, None].expand(x.shape), prec.to(x.dtype).expand(x.shape)
-        return _hook_torch(cls, HOOK["log_likelihood"], cls.__new__(cls), [x, obs, prec], theta, cond)
+        return masked_terms(lambda ob: _hook_torch(cls, HOOK["log_likelihood"], cls.__new__(cls), [x, ob, prec], theta, cond),
+                            x, obs, observed)
 
     @classmethod
     def torch_jump(cls, y, theta, cond):
@@ -2611,17 +2691,19 @@ class GeneratedOdeModel(OdeModel):
                                        % cls.__name__)
         K, T = len(_class_forcings(cls)), 1
         if K:
-            T = int(n_times) if n_times is not None else (cond.shape[1] - int(cls.n_conditions)) // K
+            T = int(n_times) if n_times is not None else (cond.shape[1] - int(cls.n_conditions)) // (
+                K + (1 if cls.missing_observations else 0))
         y = y[:, :, :len(cls.species)]
         return _hook_torch(cls, HOOK["start"], cls.__new__(cls), [y.unsqueeze(-1).expand(y.shape + (T,))], theta, cond)[..., 0]
 
-    def _log_likelihood_map(self, x_predict, observations, precisions):
+    def _log_likelihood_map(self, x_predict, observations, precisions, observed=None):
         """The model's own log density on tensors of the host paths (the host-driven adaptive route, the plugin fallback of
         Training.cost), with theta and the treatments of the last solve, as _observe_map: x_predict [B,S,4,T], observations
         [B,4,T], precisions broadcastable to x_predict -> [B,S,4,T]."""
         theta, cond = self._last_theta(x_predict.device, "%s.log_likelihood reads theta and the treatments of the last solve, and "
                                        "nothing has been solved yet")
-        return type(self).torch_log_likelihood(x_predict, observations.to(x_predict.device), precisions, theta, cond)
+        return type(self).torch_log_likelihood(x_predict, observations.to(x_predict.device), precisions, theta, cond,
+                                               observed=observed)
 
     def _observe_map(self, x_sample):
         """OdeModel.observe on a tensor that is not the last solution: the model's own map (torch_observe) with theta and
@@ -2702,15 +2784,78 @@ def noise_key_rows(key, n_rows):
     return torch.from_numpy(np.ascontiguousarray(k, dtype=np.float32))
 
 
+_OBSERVED_WITHOUT_MASK = ("the batch carries 'observed' (a mask of missing observations), and %s %s: only a generated model "
+                          "with missing_observations = True scores by it -- every other model's kernels would score the "
+                          "placeholders")
+
+
+def _batch_get(data, name):
+    return data.get(name, None) if hasattr(data, "get") else getattr(data, name, None)
+
+
+def _mask_columns(cls, n_times):
+    """Floats of a row of cond behind the forcing samples of a model with missing observations: one mask word per time point."""
+    return int(n_times) if getattr(cls, "missing_observations", False) else 0
+
+
+def observed_mask(observed, n_rows=None, n_times=None):
+    """A batch's 'observed' as a float32 tensor [rows, 4, T] of 0.0 / 1.0, where it is: 1 means the read exists.  Accepts bool or
+    0/1 numbers (tensor, array or nested lists); a wrong shape raises, and so does any other value wherever the data is still
+    on the host -- a numpy array, a list, a CPU tensor, which is how a dataset hands it over (training.batch_to_device checks
+    before it uploads).  A tensor that is on a device already is taken as it is: reading it back would stall the queue."""
+    o = observed if isinstance(observed, torch.Tensor) else torch.as_tensor(np.asarray(observed))
+    if o.dim() != 3 or o.shape[1] != 4 or (n_rows is not None and o.shape[0] != n_rows) or (
+            n_times is not None and o.shape[2] != n_times):
+        raise ValueError("'observed' must be [%s rows, 4 signals, %s time points], got %s" % (
+            "?" if n_rows is None else n_rows, "?" if n_times is None else n_times, list(o.shape)))
+    if o.dtype == torch.bool:
+        return o.to(torch.float32)
+    if o.device.type == "cpu":
+        if o.is_complex() or not bool(((o == 0) | (o == 1)).all()):
+            raise ValueError("'observed' must hold 0 / 1 (1: the read exists), as bool or numbers; it holds other values "
+                             "(a NaN belongs into 'observations' under a 0 here, not into the mask)")
+    return o.to(torch.float32)
+
+
+def mask_words(observed):
+    """The mask words [rows, T] of observed [rows, 4, T] (0.0 / 1.0): word k = sum_j observed[j][k] * 2^j, an integer 0 .. 15,
+    exact in float32 (csrc/vihds_mask.hpp decodes it).  Plain arithmetic on the tensor's device: nothing is uploaded, so a
+    captured step may form the words of its static batch."""
+    o = observed.to(torch.float32)
+    return o[:, 0] + 2.0 * o[:, 1] + 4.0 * o[:, 2] + 8.0 * o[:, 3]
+
+
+def mask_bits(words):
+    """The inverse of mask_words: words [rows, T] -> bool [rows, 4, T], bit j of (int) word."""
+    w = words.to(torch.int64)
+    return torch.stack([((w >> j) & 1).bool() for j in range(4)], dim=1)
+
+
+def masked_terms(terms_of, x, obs, observed):
+    """The scoring rule of a model with missing observations on the host, the kernels' select for select: with m = observed
+    (bool, broadcast over the samples), ob' = where(m, obs, x) -- the predicted signal stands in for the placeholder, which never
+    enters the arithmetic, so no NaN reaches a gradient either --, and the result is where(m, terms_of(ob'), 0).  x [B,S,4,T];
+    obs broadcastable to it; observed [B,4,T] or None (every point observed: terms_of(obs) as it is)."""
+    if observed is None:
+        return terms_of(obs)
+    m = observed_mask(observed, x.shape[0], x.shape[-1]).to(x.device).bool()[:, None].expand(x.shape)
+    # (x detached under the mask: the stand-in is a value, not a path -- the residual there is exactly 0 and carries no gradient)
+    terms = terms_of(torch.where(m, obs.expand(x.shape), x.detach()))
+    return torch.where(m, terms, torch.zeros((), dtype=terms.dtype, device=terms.device))
+
+
 def _check_forcing_width(cls, width, n_times, n_treatments=None):
-    """A row of cond is [treatments | K x T samples].  n_treatments: how many treatments the rows hold (an instance knows: its
+    """A row of cond is [treatments | K x T samples | T mask words | 2 key words] (the last two parts for a model with missing
+    observations and one with process noise).  n_treatments: how many treatments the rows hold (an instance knows: its
     data may carry more than the n_conditions the model reads); None: at least the model's n_conditions."""
     K, C = len(_class_forcings(cls)), int(cls.n_conditions) if n_treatments is None else int(n_treatments)
-    tail = _noise_key_columns(cls)  # (the two key columns of a model with process noise close the row)
+    words = _mask_columns(cls, n_times)  # (the mask words of a model with missing observations follow the samples)
+    tail = _noise_key_columns(cls) + words  # (the two key columns of a model with process noise close the row)
     if width - C - tail != K * n_times and (n_treatments is not None or width - tail - K * n_times < C):
-        raise ValueError("%s reads %d forcing(s) on %d time points: a row of cond must hold %d samples behind its %d treatment(s)%s, "
+        raise ValueError("%s reads %d forcing(s) on %d time points: a row of cond must hold %d samples behind its %d treatment(s)%s%s, "
                          "and holds %d (width %d)" % (cls.__name__, K, n_times, K * n_times, C,
-                                                      " and its 2 noise-key columns behind them" if tail else "",
+                                                      " and its %d mask words behind them" % words if words else "",
+                                                      " and its 2 noise-key columns behind them" if tail - words else "",
                                                       width - C - tail, width))
 
 
@@ -2718,7 +2863,7 @@ def _forcing_series(cls, cond, like, n_times):
     """The forcing samples of the wide cond [B, C] in `like`'s dtype: [B, K, T], the last K * T columns of each row, raw."""
     K = len(_class_forcings(cls))
     _check_forcing_width(cls, cond.shape[1], n_times)
-    end = cond.shape[1] - _noise_key_columns(cls)
+    end = cond.shape[1] - _noise_key_columns(cls) - _mask_columns(cls, n_times)
     return cond[:, end - K * n_times:end].to(like.dtype).to(like.device).reshape(cond.shape[0], K, n_times)
 
 
@@ -2932,6 +3077,9 @@ def _validate(cls):
         if len(cls.species) > MAX_IMPLICIT_STATES:
             raise ModelDefinitionError("%s has implicit = True and %d species; the matrix of a Newton step lives in registers: at "
                                        "most %d (MAX_IMPLICIT_STATES)" % (name, len(cls.species), MAX_IMPLICIT_STATES))
+    if not isinstance(cls.missing_observations, (bool, np.bool_)):
+        raise ModelDefinitionError("%s.missing_observations = %r; it is True or False (True: a batch may carry 'observed', "
+                                   "[rows, 4, T], 1 where a read exists)" % (name, cls.missing_observations))
     m = cls.substeps
     if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or not 1 <= m <= MAX_SUBSTEPS:
         raise ModelDefinitionError("%s.substeps = %r; a fixed-grid solver takes a whole number of steps over each observation "

@@ -319,7 +319,14 @@ class OdeModel(nn.Module):
 
     def row_inputs(self, data):
         """The rows of `cond` the kernels read for a batch: the treatments.  (A generated model with forcings appends their
-        samples, vihds/modelgen.py; callers that solve for a batch pass this, not data.inputs.)"""
+        samples, vihds/modelgen.py; callers that solve for a batch pass this, not data.inputs.)  A batch with 'observed' -- a
+        mask of missing observations -- is for a generated model with missing_observations = True alone: these kernels would
+        score the placeholders, so it is refused here (a look at the batch's keys: nothing is read back from the device)."""
+        observed = data.get("observed", None) if hasattr(data, "get") else getattr(data, "observed", None)
+        if observed is not None:
+            raise RuntimeError("the batch carries 'observed' (a mask of missing observations), and %s is not a generated model "
+                               "with missing_observations = True: only such a model scores by it -- every other model's "
+                               "kernels would score the placeholders" % type(self).__name__)
         return data.inputs
 
     def cond_width(self, n_times=None):

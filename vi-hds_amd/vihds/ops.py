@@ -118,6 +118,11 @@ class OdeProblemSpec:
                 "model '%s' has process noise (diffusion), drawn once per step of a fixed-grid scheme on the observation grid: the "
                 "adaptive solver '%s' chooses its own steps and is not available to it (fixed-grid solvers: %s)" % (
                     model, solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if solver in hip.ADAPTIVE_SOLVERS and model in hip.GENERATED_MASKED:  # (likewise)
+            raise NotImplementedError(
+                "model '%s' has missing observations (missing_observations = True), one mask word per point of the observation "
+                "grid: the adaptive solver '%s' integrates on a grid of its own and is not available to it (fixed-grid solvers: "
+                "%s)" % (model, solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         self.model, self.solver = model, solver
         sized = False
         if model == "dr_blackbox":

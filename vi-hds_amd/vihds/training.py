@@ -27,14 +27,26 @@ def log_prob_gaussian(x_obs, x_predict, precisions):
     return -0.5 * (math.log(2.0 * math.pi) - precisions.log() + precisions * (x_predict - x_obs).pow(2))
 
 
-def log_prob_observations(model, x_predict, x_obs, precisions, use_laplace=False):
-    """reference training.py:24-33 -> [B,S,4]."""
+def log_prob_observations(model, x_predict, x_obs, precisions, use_laplace=False, observed=None):
+    """reference training.py:24-33 -> [B,S,4].  observed [B,4,T] (a batch's mask of missing observations, for a generated model
+    with missing_observations = True; None: every point): an unobserved point contributes exactly 0 and its placeholder never
+    enters the arithmetic -- the kernels' rule, select for select (modelgen.masked_terms)."""
     if use_laplace:
         raise NotImplementedError("Laplace likelihood is dead code in the reference (training.py:36-38)")
     ode_model = getattr(getattr(model, "decoder", None), "ode_model", None)
+    if observed is not None and not getattr(type(ode_model), "missing_observations", False):
+        raise RuntimeError("the batch carries 'observed' (a mask of missing observations), and %s is not a generated model with "
+                           "missing_observations = True: only such a model scores by it" % type(ode_model).__name__)
     if getattr(ode_model, "likelihood_kind", "gaussian") == "custom":
         # a generated model's own log density (vihds/modelgen.py), with theta and the treatments of its last solve
+        if observed is not None:
+            return torch.sum(ode_model._log_likelihood_map(x_predict, x_obs, precisions, observed=observed), 3)
         return torch.sum(ode_model._log_likelihood_map(x_predict, x_obs, precisions), 3)
+    if observed is not None:
+        from vihds.modelgen import masked_terms
+        prec = precisions.expand(x_predict.shape) if isinstance(precisions, torch.Tensor) else precisions
+        return torch.sum(masked_terms(lambda ob: log_prob_gaussian(ob, x_predict, prec), x_predict,
+                                      torch.unsqueeze(x_obs, 1).to(x_predict.dtype), observed), 3)
     return torch.sum(log_prob_gaussian(torch.unsqueeze(x_obs, 1), x_predict, precisions), 3)
 
 
@@ -67,6 +79,9 @@ def batch_to_device(times, device, d):
     d["observations"] = d["observations"].to(device).contiguous()
     if d.get("forcings", None) is not None:  # per-row time series of a generated model with forcings [rows, K, T]
         d["forcings"] = d["forcings"].to(device).float().contiguous()
+    if d.get("observed", None) is not None:  # the mask of missing observations [rows, 4, T]: checked on the host, then uploaded
+        from vihds.modelgen import observed_mask
+        d["observed"] = observed_mask(d["observed"], d["observations"].shape[0], d["observations"].shape[-1]).to(device).contiguous()
     return attrify(d)
 
 
@@ -80,6 +95,8 @@ def collate_merged(times, device, batch):
     }
     if batch and "forcings" in batch[0]:
         dd["forcings"] = torch.stack([torch.as_tensor(b["forcings"], dtype=torch.float32) for b in batch])
+    if batch and "observed" in batch[0]:
+        dd["observed"] = torch.stack([torch.as_tensor(b["observed"], dtype=torch.float32) for b in batch])
     return batch_to_device(times, device, dd)
 
 
@@ -293,7 +310,8 @@ class Training:
             log_p_by_species = fused
         else:
             log_p_by_species = log_prob_observations(self.model, x_predict, batch_data.observations, precisions,
-                                                     self.settings.params.use_laplace)
+                                                     self.settings.params.use_laplace,
+                                                     observed=batch_data.get("observed", None))
             logp = log_p_by_species.permute(2, 0, 1).contiguous()
         log_q_theta = q.log_prob(theta)
         log_p_theta = p.log_prob(theta)
@@ -810,7 +828,8 @@ class Training:
                 return out
         g, static, loss = self._graphs[key]
         if self._staged.get(key) is not batch:  # a batch that is already resident in the graph's inputs is not re-copied
-            for k in ("dev_1hot", "inputs", "observations", "times") + (("forcings",) if "forcings" in static else ()):
+            for k in ("dev_1hot", "inputs", "observations", "times") + tuple(
+                    k for k in ("forcings", "observed") if static.get(k, None) is not None):
                 static[k].copy_(batch[k], non_blocking=True)
             static["delta_obs"].copy_(_delta_obs(static.observations))
             self._staged[key] = batch
@@ -845,6 +864,10 @@ class Training:
             if "forcings" not in out:
                 out["forcings"] = torch.empty((B,) + tuple(src.forcings.shape[1:]), device=dev)
             torch.index_select(src.forcings, 0, rows, out=out.forcings)
+        if src.get("observed", None) is not None:  # (... and so does the mask of missing observations)
+            if "observed" not in out:
+                out["observed"] = torch.empty((B,) + tuple(src.observed.shape[1:]), device=dev)
+            torch.index_select(src.observed, 0, rows, out=out.observed)
         return out
 
     class _IndexStaging:
