@@ -119,8 +119,11 @@ const char* vihds_last_error(void);
 /* Introspection so the host maps YAML parameter names to kernel slots without duplicating tables. */
 int vihds_model_n_states(int model);      /* rows per time point of the trajectory: ODE state size N (incl. 4 precision states for
                                              *_precisions); species + 4 for a registered model with a precision map of its own
-                                             (four algebraic precision rows behind the species, never integrated) */
-int vihds_model_n_species(int model);     /* states handed to observe(): n_states minus the four precision rows where it has them */
+                                             (four algebraic precision rows behind the species, never integrated); one more,
+                                             the last, for a registered model with step control (each interval's step count:
+                                             +count where its tolerance was met, -ceiling where it was not; 0 at point 0) */
+int vihds_model_n_species(int model);     /* states handed to observe(): n_states minus the four precision rows and the count
+                                             row where it has them */
 int vihds_model_n_slots(int model);       /* number of theta slots the kernel reads */
 const char* vihds_model_slot_name(int model, int slot); /* reference parameter name of a slot */
 int vihds_model_n_weights(const vihds_ode_problem* p);  /* floats in the `weights` buffer (0 if none) */

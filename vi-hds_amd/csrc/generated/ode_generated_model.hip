@@ -30,6 +30,10 @@ static_assert(!(substeps<VIHDS_GEN_CORE>::value > 1 && (VIHDS_GEN_NEURAL != 0 ||
               "a model with sub-steps takes no networks and no NeuralPrecisions: the adjoint's dump holds (T-1) x stages evaluations");
 static_assert(substeps<VIHDS_GEN_CORE>::value >= 1 && substeps<VIHDS_GEN_CORE>::value <= kMaxSubsteps,
               "substeps: 1 .. 8 (vihds_substeps.hpp)");
+static_assert(!step_control<VIHDS_GEN_CORE>::value ||
+                  ((substeps<VIHDS_GEN_CORE>::value == 2 || substeps<VIHDS_GEN_CORE>::value == 4 || substeps<VIHDS_GEN_CORE>::value == 8) &&
+                   n_delays<VIHDS_GEN_CORE>::value == 0 && !has_diffusion<VIHDS_GEN_CORE>::value),
+              "step control: SUBSTEPS is the ladder's ceiling 2, 4 or 8; no delays and no process noise (vihds_stepctl.hpp)");
 static_assert(!(VIHDS_GEN_NEURAL != 0 && has_jump<VIHDS_GEN_CORE>::value),
               "a model with a state jump does not take NeuralPrecisions: WithPrec<> does not forward jump / jump_vjp");
 static_assert(!(VIHDS_GEN_NEURAL != 0 && (has_start<VIHDS_GEN_CORE>::value || lead_in<VIHDS_GEN_CORE>::value > 0)),
@@ -100,7 +104,7 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
                                    n_forcings<GenM>::value, implicit_order<GenM>::value, substeps<GenM>::value,
                                    has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value,
                                    n_delays<GenM>::value, has_diffusion<GenM>::value ? 1 : 0,
-                                   masked_obs<GenM>::value ? 1 : 0};
+                                   masked_obs<GenM>::value ? 1 : 0, step_control<GenM>::value ? 1 : 0};
   return &r;
 }
 #endif

@@ -132,8 +132,12 @@ struct ModelEntry {
   // a registered model with missing observations (GenModelRecord::masked_obs): a row of cond carries T mask words behind its
   // forcing samples (ahead of the noise key), and it takes the fixed-grid solvers only
   bool masked_obs = false;
+  // a registered model with step control (GenModelRecord::step_control): one more row of n_states behind the species and the
+  // precision rows holds each interval's step count; it takes euler, midpoint, rk4 and the implicit solver only
+  bool step_control = false;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
-  bool prec_rows() const { return neural_prec || own_prec; }  // the last four rows of n_states are precisions
+  bool prec_rows() const { return neural_prec || own_prec; }  // four rows of n_states behind the species are precisions
+  int n_species() const { return n_states - (prec_rows() ? 4 : 0) - (step_control ? 1 : 0); }
   int n_prec_slots() const { return prec_rows() ? 0 : 4; }    // the prec_* theta rows behind the model's own slots
   const char* slot_name(int s) const { return slot_names ? slot_names[s] : slot_name_of(s); }
 };
@@ -187,7 +191,8 @@ static std::atomic<int> g_gen_count{0};
 static ModelEntry gen_entry_of(const GenModelRecord* r) {
   return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
           r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps, r->jump != 0,
-          r->start != 0, r->lead_in_steps, r->n_delays, r->diffusion != 0, r->masked_obs != 0};
+          r->start != 0, r->lead_in_steps, r->n_delays, r->diffusion != 0, r->masked_obs != 0,
+          r->step_control != 0};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -276,6 +281,9 @@ static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& 
   if (e->substeps > 1 && solver_is_adaptive(p->solver))
     return fail(VIHDS_E_UNSUPPORTED, "the model has substeps > 1, which divide the observation intervals of a fixed-grid scheme: "
                                      "an adaptive solver chooses its own steps and is not available to it");
+  if (e->step_control && (p->solver == VIHDS_SOLVER_MODEULER || p->solver == VIHDS_SOLVER_MODEULERWHILE))
+    return fail(VIHDS_E_UNSUPPORTED, "the model has step control (step_tolerance), which divides the observation interval: modeuler "
+                                     "and modeulerwhile take a fixed step that is not the interval and are not available to it");
   if (e->jump && solver_is_adaptive(p->solver))
     return fail(VIHDS_E_UNSUPPORTED, "the model has a state jump at the observation points, applied between two steps of a fixed-grid "
                                      "scheme: an adaptive solver integrates on a grid of its own and is not available to it");
@@ -417,7 +425,10 @@ int vihds_model_register(const char* library_path) {
       (r->n_delays > 0 && (r->neural_prec || r->n_net_weights > 0 || r->implicit || r->substeps > 1 || r->jump ||
                            r->lead_in_steps)) ||
       (r->diffusion != 0 && r->diffusion != 1) || (r->masked_obs != 0 && r->masked_obs != 1) ||
-      (r->diffusion && (r->neural_prec || r->n_net_weights > 0 || r->implicit || r->lead_in_steps || r->n_delays > 0))) {
+      (r->diffusion && (r->neural_prec || r->n_net_weights > 0 || r->implicit || r->lead_in_steps || r->n_delays > 0)) ||
+      (r->step_control != 0 && r->step_control != 1) ||
+      (r->step_control && ((r->substeps != 2 && r->substeps != 4 && r->substeps != 8) || r->n_delays > 0 || r->diffusion ||
+                           r->n_states < (r->own_prec ? 6 : 2)))) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
   }
@@ -438,7 +449,7 @@ int vihds_model_n_states(int model) {
 }
 int vihds_model_n_species(int model) {
   const ModelEntry* e = entry(model);
-  return e ? e->n_states - (e->prec_rows() ? 4 : 0) : VIHDS_E_UNSUPPORTED;
+  return e ? e->n_species() : VIHDS_E_UNSUPPORTED;
 }
 int vihds_model_n_slots(int model) {
   const ModelEntry* e = entry(model);
@@ -668,7 +679,7 @@ __global__ void __launch_bounds__(256) summ_finish_kernel(int B, int T, int nch,
 }  // namespace vihds
 static int summ_species(const vihds_ode_problem* p, const ModelEntry* e) {
   const int n_states = vihds_problem_n_states(p);
-  return n_states < 0 ? n_states : (e->prec_rows() ? n_states - 4 : n_states);
+  return n_states < 0 ? n_states : n_states - (e->prec_rows() ? 4 : 0) - (e->step_control ? 1 : 0);
 }
 int vihds_ode_fwd_summaries_supported(const vihds_ode_problem* p) {
   if (!p) return 0;

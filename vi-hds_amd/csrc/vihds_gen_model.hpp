@@ -27,7 +27,8 @@ struct GenModelRecord {
   int odeargs_size;                // sizeof(OdeArgs)
   unsigned long long header_hash;  // VIHDS_HDR_HASH
   int n_states;     // rows per time point of the trajectory: N (incl. the 4 precision states of a neural-precision model), or
-                    // species + 4 for a model with a precision map of its own (own_prec: four algebraic rows behind the species)
+                    // species + 4 for a model with a precision map of its own (own_prec: four algebraic rows behind the species);
+                    // + 1 for a model with step control (step_control: the count row, the last one)
   int n_slots;      // kernel theta slots (a neural-precision model's init_prec_* included, constant precisions not)
   int n_cond;       // treatments read per data row
   int observe_kind; // ObserveKind
@@ -75,6 +76,10 @@ struct GenModelRecord {
   // cond carries one mask word per time point behind its forcing samples and ahead of the noise key, so a problem needs
   // C >= n_cond + n_forcings * T + T (+ 2 with process noise); the fixed-grid solvers only
   int masked_obs;
+  // 1: the generated struct has step control (STEP_RTOL / STEP_ATOL, vihds_models.hpp step_control<>; vihds_stepctl.hpp): every
+  // trajectory picks its step count per observation interval up to `substeps`, the last row of n_states holds the counts (the
+  // forward writes it, the adjoint reads it from traj_in); euler, midpoint, rk4 and the implicit solver only
+  int step_control;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

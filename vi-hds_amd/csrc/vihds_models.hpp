@@ -933,11 +933,7 @@ template <class M, class = void>
 struct own_prec : std::false_type {};
 template <class M>
 struct own_prec<M, std::void_t<decltype(M::OWN_PREC)>> : std::bool_constant<M::OWN_PREC> {};
-// rows per time point of the trajectory buffer (traj, traj_in, g_traj)
-template <class M>
-struct traj_rows {
-  static constexpr int value = M::N + (own_prec<M>::value ? 4 : 0);
-};
+// (traj_rows<M>, the rows per time point of the trajectory buffer, follows step_control<> below)
 
 // A core generated with an observation log density of its own (vihds/modelgen.py) declares OWN_LIK = true and two members that
 // run once per time point, in place of the Gaussian term -0.5 (log 2 pi - log pr + pr e^2):
@@ -1022,6 +1018,23 @@ struct substeps {
 template <class M>
 struct substeps<M, std::void_t<decltype(M::SUBSTEPS)>> {
   static constexpr int value = M::SUBSTEPS;
+};
+
+// A core generated with `step_tolerance = (rtol, atol)` (vihds/modelgen.py) declares STEP_RTOL and STEP_ATOL beside SUBSTEPS = M
+// (2, 4 or 8): M is then the ceiling of a ladder 1 -> 2 -> .. -> M of step counts, of which every trajectory picks its own per
+// observation interval by step doubling (vihds_stepctl.hpp defines the rule).  The chosen counts travel in one more row of the
+// trajectory buffer, the last of traj_rows<M>, which the adjoint reads.  The explicit fixed-grid solvers whose step is the
+// interval (euler, midpoint, rk4) and the implicit one only.  False for every hand-written model and for WithPrec<> (which
+// declares neither and does not forward its core's).
+template <class M, class = void>
+struct step_control : std::false_type {};
+template <class M>
+struct step_control<M, std::void_t<decltype(M::STEP_RTOL), decltype(M::STEP_ATOL)>> : std::true_type {};
+// rows per time point of the trajectory buffer (traj, traj_in, g_traj): the species (and precision states), the four precision
+// rows of a model with a map of its own, then the count row of a model with step control
+template <class M>
+struct traj_rows {
+  static constexpr int value = M::N + (own_prec<M>::value ? 4 : 0) + (step_control<M>::value ? 1 : 0);
 };
 
 // A core generated with a state jump (vihds/modelgen.py: jump(self, y, p, c)) declares OWN_JUMP = true and two members that run

@@ -23,6 +23,7 @@
 #include "vihds_implicit.hpp"
 #include "vihds_delay.hpp"
 #include "vihds_substeps.hpp"
+#include "vihds_stepctl.hpp"
 #include "vihds_sde.hpp"
 #include "vihds_mask.hpp"
 #include "vihds_blackbox.hpp"
@@ -412,14 +413,14 @@ constexpr int substate_rows() {
 // implicit scheme only).  The intermediate states are stored nowhere: MS - 1 forward sub-steps from u_0 recompute them --
 // ode_step with SubGrid's times, exactly the forward's calls -- into LDS, then the step adjoints run for j = MS-1 down to 0.
 // An explicit scheme's adjoint starts from u_j, the implicit one's from u_j+1.  Both loops stay rolled.
-template <class M, int SOLVER, class Ctx>
-__device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, const float* y, const float* y_next,
-                                                 const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb,
-                                                 int k = 0, const SdeKey& key = SdeKey{}) {
-  constexpr int N = M::N, MS = substeps<M>::value;
+// (sg, MS: the interval's sub-grid and its step count -- SubGrid<substeps<M>> and that constant, or, for a model with step
+// control, SubGridN and the count its forward chose, at most substeps<M>: the rows of SubstateLds are sized by that ceiling)
+template <class M, int SOLVER, class Grid, class Ctx>
+__device__ __forceinline__ void ode_substeps_vjp_on(const Grid& sg, const int MS, float hm, const float* y, const float* y_next,
+                                                    const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb,
+                                                    int k, const SdeKey& key) {
+  constexpr int N = M::N;
   float* col = SubstateLds<substate_rows<M>()>::column();
-  const SubGrid<MS> sg(t0, t1);
-  const float hm = SubGrid<MS>::fixed_step(h0);
   float u[N];
   VIHDS_UNROLL for (int q = 0; q < N; ++q) u[q] = y[q];
 #pragma unroll 1
@@ -462,6 +463,53 @@ __device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, c
       }
     }
   }
+}
+template <class M, int SOLVER, class Ctx>
+__device__ __forceinline__ void ode_substeps_vjp(float t0, float t1, float h0, const float* y, const float* y_next,
+                                                 const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb,
+                                                 int k = 0, const SdeKey& key = SdeKey{}) {
+  constexpr int MS = substeps<M>::value;
+  ode_substeps_vjp_on<M, SOLVER>(SubGrid<MS>(t0, t1), MS, SubGrid<MS>::fixed_step(h0), y, y_next, p, wts, lam, pb, wtsb, k, key);
+}
+
+// ---- error-controlled sub-steps (step_control<M>, vihds_stepctl.hpp) ---------------------------------------------------
+// Instantiated for a generated model with `step_tolerance` only: the time loops reach it behind
+// `if constexpr (step_control<M>::value)`.  substeps<M> = MS is the ceiling of the ladder.
+
+// the forward's interval: Phi^1, Phi^2, Phi^4 .. from y = y_k until the acceptance test passes or the count reaches MS; y
+// becomes the accepted state and the row's code is returned.  y_k, coarse and fine stay in registers; one rolled loop holds the
+// one inlined step of the scheme, so the code does not grow with MS.  (The solvers in scope do not read modeuler's fixed step.)
+template <class M, int SOLVER>
+__device__ __forceinline__ float ode_stepctl(float t0, float t1, float* y, const float* p, const float* wts) {
+  constexpr int N = M::N, MS = substeps<M>::value;
+  static_assert(MS == 2 || MS == 4 || MS == 8, "step control: the ceiling of the ladder is 2, 4 or 8");
+  float coarse[N], fine[N];
+  float code = 0.f;
+#pragma unroll 1
+  for (int c = 1;; c *= 2) {  // c = 1: coarse = Phi^1(y_k), no test
+    const SubGridN sg(t0, t1, c);
+    VIHDS_UNROLL for (int q = 0; q < N; ++q) fine[q] = y[q];
+#pragma unroll 1
+    for (int j = 0; j < c; ++j) ode_step<M, SOLVER>(sg.at(j), sg.at(j + 1), 0.f, fine, p, wts);
+    if (c > 1) {
+      const bool passed = step_ratio<N>(fine, coarse, M::STEP_RTOL, M::STEP_ATOL) <= 1.f;
+      if (passed || c == MS) {
+        code = step_code(c, passed);
+        break;
+      }
+    }
+    VIHDS_UNROLL for (int q = 0; q < N; ++q) coarse[q] = fine[q];
+  }
+  VIHDS_UNROLL for (int q = 0; q < N; ++q) y[q] = fine[q];
+  return code;
+}
+// reverse of such an interval: the existing interval adjoint with the count the forward stored (code: the row's float at the
+// interval's end point, clamped into 1 .. MS before it bounds a loop or indexes LDS).  The ladder is not repeated
+template <class M, int SOLVER, class Ctx>
+__device__ __forceinline__ void ode_stepctl_vjp(float t0, float t1, float code, const float* y, const float* y_next,
+                                                const float* p, const float* wts, float* lam, float* pb, Ctx& wtsb) {
+  const int cnt = step_count_of(code, substeps<M>::value);
+  ode_substeps_vjp_on<M, SOLVER>(SubGridN(t0, t1, cnt), cnt, 0.f, y, y_next, p, wts, lam, pb, wtsb, 0, SdeKey{});
 }
 
 // ---- the lead-in phase (lead_in<M> = NL > 0: LEAD_STEPS steps over LEAD_TIME before the first observation point) -------
@@ -615,6 +663,16 @@ struct WithObsMask : Feed {
 };
 template <class Feed, bool ON>
 using mask_feed_t = std::conditional_t<ON, WithObsMask<Feed>, Feed>;
+// what the time loops keep for a model with step control (step_control<M>, vihds_stepctl.hpp) beside their feed: the float of
+// the count row -- in the forward the code of the interval that just ended, in the adjoint the code of the interval above the
+// point k and the one requested one iteration ahead, as the stored states are.  Every other model's loop declares the feed
+// alone, as it did (ctl_feed_t), so its code is what it was.
+template <class Feed>
+struct WithStepCode : Feed {
+  float code, code_ahead;
+};
+template <class Feed, bool ON>
+using ctl_feed_t = std::conditional_t<ON, WithStepCode<Feed>, Feed>;
 // ---- forward -------------------------------------------------------------------------------------
 // LDS_IN: the time grid and the observation rows of the data rows this block spans are staged in LDS once, so the
 // time loop holds no vector-memory loads and its trajectory / x_predict stores are never waited on (see
@@ -633,8 +691,9 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
   const float* wts = stage_weights<M>(a, wlds);
   int ob_off = 0;
   // (ForcingFeed<NF>; a model with delayed reads also keeps y_0 and its cursors, one with process noise its key, one with
-  // missing observations its mask words)
-  mask_feed_t<noise_feed_t<delay_feed_t<ForcingFeed<NF>, ND>, has_diffusion<M>::value>, MASKED> ff;
+  // missing observations its mask words, one with step control the code of the interval that just ended)
+  ctl_feed_t<mask_feed_t<noise_feed_t<delay_feed_t<ForcingFeed<NF>, ND>, has_diffusion<M>::value>, MASKED>, step_control<M>::value> ff;
+  if constexpr (step_control<M>::value) ff.code = 0.f;
   if (LDS_IN) {
     const int first = blockIdx.x * blockDim.x, last = min(first + (int)blockDim.x, a.n) - 1;
     const int b0 = first / a.S, nb = last / a.S - b0 + 1;
@@ -767,7 +826,8 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
         // g(u) sqrt(h) xi, its draws counted by the trajectory, the species and the step (vihds_sde.hpp)
         if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts, k - 1, ff.key);
         else noisy_step<M, SOLVER>(tA, tB, h0, sde_step_index(k - 1, 1, 0), ff.key, y, p, wts);
-      } else if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts);  // (one interval, several steps)
+      } else if constexpr (step_control<M>::value) ff.code = ode_stepctl<M, SOLVER>(tA, tB, y, p, wts);  // (the trajectory's own count)
+      else if constexpr (substeps<M>::value > 1) ode_substeps<M, SOLVER>(tA, tB, h0, y, p, wts);  // (one interval, several steps)
       else ode_step<M, SOLVER>(tA, tB, h0, y, p, wts);
       tA = tB;
       if constexpr (NF > 0) {
@@ -784,6 +844,10 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
         VIHDS_UNROLL for (int j = 0; j < N; ++j) __builtin_nontemporal_store(y[j], &a.traj[((size_t)k * NT + j) * n + i]);
       } else {
         VIHDS_UNROLL for (int j = 0; j < N; ++j) a.traj[((size_t)k * NT + j) * n + i] = y[j];
+      }
+      if constexpr (step_control<M>::value) {  // the count row, the last of the point's rows: the interval that ended here (0 at k = 0)
+        if (nt_traj) __builtin_nontemporal_store(ff.code, &a.traj[((size_t)k * NT + (NT - 1)) * n + i]);
+        else a.traj[((size_t)k * NT + (NT - 1)) * n + i] = ff.code;
       }
     }
     float xp[4];
@@ -1102,8 +1166,11 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
   // forcing samples travel with the times: ff.hi at tHi, ff.lo at tK, the next lower point's (ff.ahead) requested one
   // iteration ahead like tLo
   // (ForcingFeed<NF>; an implicit solver's also keeps y_k+1, a model with delayed reads y_0 and its cursors, one with process
-  // noise its key, one with missing observations its mask words)
-  mask_feed_t<noise_feed_t<delay_feed_t<bwd_feed_t<NF, N, solver_is_implicit(SOLVER)>, ND>, has_diffusion<M>::value>, MASKED> ff;
+  // noise its key, one with missing observations its mask words, one with step control the codes of the count row)
+  ctl_feed_t<mask_feed_t<noise_feed_t<delay_feed_t<bwd_feed_t<NF, N, solver_is_implicit(SOLVER)>, ND>, has_diffusion<M>::value>, MASKED>,
+             step_control<M>::value> ff;
+  // the count row travels with the stored states: the code of the point k (the interval below it) requested one iteration ahead
+  if constexpr (step_control<M>::value) ff.code_ahead = 0.f;
   // mask words travel with the observations: the word of the point k - 1 (ff.word_ahead) requested one iteration ahead like obn
   if constexpr (MASKED) {
     ff.msrc = a.cond + (size_t)b * a.C + (a.C - cond_tail<M>() - a.T);
@@ -1136,6 +1203,10 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
     if constexpr (MASKED) {
       ff.word = ff.word_ahead;
       if (k > 0) ff.word_ahead = ff.msrc[k - 1];
+    }
+    if constexpr (step_control<M>::value) {  // (ff.code: the count of the interval k, stored at the point k + 1)
+      ff.code = ff.code_ahead;
+      if (k > 0) ff.code_ahead = a.traj_in[((size_t)k * NT + (NT - 1)) * n + i];
     }
     if (k > 0) {
       VIHDS_UNROLL for (int j = 0; j < N; ++j) yn[j] = a.traj_in[((size_t)(k - 1) * NT + j) * n + i];
@@ -1212,7 +1283,11 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
       // adjoint of y_k and adds its parameter part to pb, ahead of the hook adjoints of the point, which add into that lam
       if (k < a.T - 1) {
         float yj[N], lamk[N];
-        if constexpr (substeps<M>::value > 1) {
+        if constexpr (step_control<M>::value) {  // (the count the forward chose for this interval: ode_stepctl_vjp)
+          M::jump(y, p, yj);
+          if constexpr (solver_is_implicit(SOLVER)) ode_stepctl_vjp<M, SOLVER>(tK, tHi, ff.code, yj, ff.y_next, p, wts, lam, pb, wtsb);
+          else ode_stepctl_vjp<M, SOLVER>(tK, tHi, ff.code, yj, nullptr, p, wts, lam, pb, wtsb);
+        } else if constexpr (substeps<M>::value > 1) {
           M::jump(y, p, yj);
           if constexpr (solver_is_implicit(SOLVER)) ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, yj, ff.y_next, p, wts, lam, pb, wtsb);
           else ode_substeps_vjp<M, SOLVER>(tK, tHi, h0, yj, nullptr, p, wts, lam, pb, wtsb);
@@ -1233,6 +1308,13 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
       }
       if constexpr (solver_is_implicit(SOLVER)) {  // (the interval below ends on the stored left limit y_k)
         VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
+      }
+    } else if constexpr (step_control<M>::value) {  // (the existing interval adjoint at the count the forward chose: ode_stepctl_vjp)
+      if constexpr (solver_is_implicit(SOLVER)) {
+        if (k < a.T - 1) ode_stepctl_vjp<M, SOLVER>(tK, tHi, ff.code, y, ff.y_next, p, wts, lam, pb, wtsb);
+        VIHDS_UNROLL for (int j = 0; j < N; ++j) ff.y_next[j] = y[j];
+      } else {
+        if (k < a.T - 1) ode_stepctl_vjp<M, SOLVER>(tK, tHi, ff.code, y, nullptr, p, wts, lam, pb, wtsb);
       }
     } else if constexpr (substeps<M>::value > 1) {  // (the interval's sub-states are recomputed from y = y_k: ode_substeps_vjp)
       if constexpr (solver_is_implicit(SOLVER)) {
@@ -1520,11 +1602,17 @@ inline int launch_ode_implicit(bool backward, int solver, const OdeArgs& a, hipS
     return VIHDS_E_UNSUPPORTED;
   }
 }
+// the fixed-grid solvers a model with step control takes (vihds_stepctl.hpp): every one but the modeuler family
+template <class M>
+constexpr bool step_control_takes(int sv) {
+  return !step_control<M>::value || (sv != VIHDS_SOLVER_MODEULER && sv != VIHDS_SOLVER_MODEULERWHILE);
+}
 template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
   if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value || has_start<M>::value ||
-                lead_in<M>::value > 0 || n_delays<M>::value > 0 || has_diffusion<M>::value || masked_obs<M>::value) {
+                lead_in<M>::value > 0 || n_delays<M>::value > 0 || has_diffusion<M>::value || masked_obs<M>::value ||
+                step_control<M>::value) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels
     // (ode_trial_kernel, the device-resident solver, ode_fwd_summ_kernel) is instantiated for it.  A model with sub-steps
@@ -1535,9 +1623,13 @@ inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t s
     // process noise likewise: its draws are counted by the steps of the observation grid (vihds_sde.hpp).  A model with missing
     // observations likewise: its mask words live on the observation grid (vihds_mask.hpp)
     if (mode.summ || mode.dev || mode.grid || solver_is_adaptive(solver)) return VIHDS_E_UNSUPPORTED;
+    // (a model with step control: modeuler's fixed step is not the interval -- neither kernel of that family is instantiated)
+    if constexpr (step_control<M>::value) {
+      if (solver == VIHDS_SOLVER_MODEULER || solver == VIHDS_SOLVER_MODEULERWHILE) return VIHDS_E_UNSUPPORTED;
+    }
 #define VIHDS_CASE(SV)                                           \
   case SV:                                                       \
-    if constexpr (solver_built_in<ONLY>(SV)) {                   \
+    if constexpr (solver_built_in<ONLY>(SV) && step_control_takes<M>(SV)) { \
       if (backward) launch_bwd_s<M, SV>(a, st);                  \
       else launch_fwd_s<M, SV>(a, st);                           \
       return VIHDS_OK;                                           \

@@ -41,6 +41,10 @@ GENERATED_IMPLICIT_ORDER = {}
 # registered generated models: key -> `substeps`, the steps a fixed-grid solver takes over each observation interval.  Above 1
 # the model declines the adaptive solvers (they choose their own steps)
 GENERATED_SUBSTEPS = {}
+# registered generated models with step control (`step_tolerance = (rtol, atol)`): key -> (ceiling, rtol, atol).  Every
+# trajectory picks its own step count per observation interval, 1 -> 2 -> .. -> ceiling (csrc/vihds_stepctl.hpp); the
+# trajectory has one more row, the last, with the counts.  They also decline modeuler and modeulerwhile (a fixed step h0)
+GENERATED_STEP_CONTROL = {}
 # keys of registered generated models with a state jump at the observation points (`jump(self, y, p, c)`): they decline the
 # adaptive solvers (the jump is applied between two steps of a fixed-grid scheme)
 GENERATED_JUMP = set()

@@ -191,6 +191,32 @@ adjoints last to first.  Such a model takes the fixed-grid solvers only: an adap
 declined (solve raises before anything is queued, the library answers VIHDS_E_UNSUPPORTED).  Refused in this version: together
 with networks and with NeuralPrecisions (the adjoint's dump holds one evaluation per stage and observation interval).
 
+Error-controlled sub-steps.  One `substeps` for every trajectory and every interval is paid for on every quiet interval and says
+nothing where it was too small.  A class that also sets
+
+        substeps = 8                                 # now the ceiling of the ladder: 2, 4 or 8
+        step_tolerance = (1e-3, 1e-6)                # (rtol, atol) on the species: finite floats >= 0, not both 0
+
+has every trajectory pick its own number of steps for every observation interval by step doubling (csrc/vihds_stepctl.hpp has the
+rule, exactly): with Phi^c the c steps of the scheme from y_k on the sub-grid of c steps, coarse = Phi^1, then fine = Phi^2c and
+r = max over the species of |fine - coarse| / (atol + rtol max(|fine|, |coarse|)); r <= 1 accepts fine with count 2c, otherwise
+c doubles, and at 2c = substeps fine is taken all the same and the interval counts as saturated.  A NaN or infinite r fails the
+test.  Only species enter r (algebraic unknowns and precision rows do not); jump applies to the accepted state afterwards, the
+steps of a lead-in phase are not controlled, and beuler starts each sub-step's Newton iteration from the previous sub-state as
+under `substeps`.  The choice is made in registers, with no barrier and no atomics; passing at the first test costs three steps
+for a count of 2.  The solution gains one row per time point, the last one (behind the four precision rows of a model with a
+precision map of its own): at point k + 1 the count of the interval that ended there as a float, +count where the test passed
+and -substeps where the ladder was exhausted, 0 at point 0.  substep_counts(traj, model) reads it back as (counts int32
+[T-1, B, S], saturated bool [T-1, B, S]); `saturated` means the tolerance was NOT met there.  expand_precisions and the
+evaluation summaries leave the row out.  The adjoint reads the row from the stored trajectory (clamped into 1 .. substeps before
+it bounds a loop or indexes LDS), never repeats the ladder, and runs the interval adjoint of `substeps` at that count: it is the
+exact discrete adjoint of the realised scheme, and a count carries no gradient, as a `where` condition carries none.  The struct
+gains STEP_RTOL and STEP_ATOL beside SUBSTEPS (a class without the attribute generates the text it generated before).  In float32
+a relative tolerance much below 1e-5 measures rounding, not truncation error.  Solvers: euler, midpoint, rk4 and beuler (either
+implicit_order); modeuler and modeulerwhile, whose fixed step h0 is not the interval, and the adaptive solvers are declined
+before anything is built or queued.  Combines with forcings, jump, start / lead_in, algebraic, missing_observations and the three
+observation hooks; refused in this version: networks, NeuralPrecisions, delays, diffusion.
+
 State jumps.  A discontinuity of the state at an observation point -- a culture diluted at a read, a bolus pipetted into a
 well, a turbidostat that dilutes above a threshold, a dose -- is neither a term of rhs nor a forcing (both change the
 derivative, not the state).  A class may define
@@ -425,6 +451,11 @@ MAX_NEWTON_ITERATIONS = 8
 # (tests/test_modelgen_substeps_host.py compiles that worst case without scratch)
 MAX_SUBSTEPS = 8
 MAX_SUBSTEP_ROWS = 56  # (substeps - 1) * species: a block's static LDS ends at 64 KB
+# `step_tolerance = (rtol, atol)`: the ceilings of the ladder 1 -> 2 -> 4 -> 8 that `substeps` may name (csrc/vihds_stepctl.hpp),
+# and the fixed-grid solvers that decline such a model -- their fixed step h0 is not the observation interval
+STEP_CONTROL_CEILINGS = (2, 4, 8)
+_F32_MAX = float(np.finfo(np.float32).max)
+STEP_CONTROL_DECLINED_SOLVERS = ("modeuler", "modeulerwhile")
 # steps of the lead-in phase before the first observation point (`lead_in_steps`).  The adjoint keeps its intermediate states in
 # the LDS rows the sub-steps use (never both at once): (lead_in_steps - 1) * species rows, at most MAX_SUBSTEP_ROWS
 MAX_LEAD_IN_STEPS = 8
@@ -1691,6 +1722,11 @@ def generate_source(cls, neural=False):
     if neural and cls.implicit:
         raise ModelDefinitionError("%s has implicit = True: the precision ODE of NeuralPrecisions has no generated Jacobian, so an "
                                    "implicit model takes constant precisions or a precision map of its own" % cls.__name__)
+    if neural and cls.step_tolerance is not None:
+        raise ModelDefinitionError("%s has step_tolerance = %r: the adjoint's dump of the precision network holds one evaluation "
+                                   "per stage and observation interval, and the count row is the last row of a trajectory whose "
+                                   "precision states WithPrec<> integrates -- a model with step control takes constant precisions "
+                                   "or a precision map of its own" % (cls.__name__, cls.step_tolerance))
     if neural and cls.substeps > 1:
         raise ModelDefinitionError("%s has substeps = %d: the adjoint's dump of the precision network holds one evaluation per "
                                    "stage and observation interval, so a sub-stepped model takes constant precisions or a "
@@ -1936,6 +1972,12 @@ def generate_source(cls, neural=False):
     # substeps = m > 1: the one line the kernels' time loops read (vihds_models.hpp substeps<>); a class without it generates
     # the text it generated before
     substeps_decl = ["  static constexpr int SUBSTEPS = %d;" % int(cls.substeps)] if cls.substeps > 1 else []
+    # step_tolerance = (rtol, atol): SUBSTEPS is the ceiling of the ladder, and the two lines the kernels' acceptance test reads
+    # (vihds_models.hpp step_control<>, vihds_stepctl.hpp); none without it, likewise
+    if cls.step_tolerance is not None:
+        substeps_decl += ["  static constexpr float STEP_RTOL = %s;  // step control: 1 -> 2 -> .. -> SUBSTEPS steps per interval, "
+                          "each trajectory's own (vihds_stepctl.hpp)" % _lit(cls.step_tolerance[0]),
+                          "  static constexpr float STEP_ATOL = %s;" % _lit(cls.step_tolerance[1])]
     # lead_in = L > 0: the two lines the kernels read (vihds_models.hpp lead_in<>); none without it, likewise
     if cls.lead_in > 0:
         substeps_decl += ["  static constexpr int LEAD_STEPS = %d;  // steps of the scheme over [t_0 - LEAD_TIME, t_0], nothing stored"
@@ -1993,6 +2035,25 @@ def generate_source(cls, neural=False):
         "",
     ]
     return "\n".join(line for line in out if line != "") + "\n"
+
+
+def substep_counts(traj, model):
+    """The step counts a model with step control chose (module docstring, "Error-controlled sub-steps"), from a stored trajectory:
+    `traj` is the kernels' buffer [T, rows, B, S] (DecodedSolution.traj_buffer) or the solution [B, S, rows, T]
+    (GeneratedOdeModel.simulate) -- told apart by where the rows are --, `model` the class or an instance.  Returns
+    (counts int32 [T-1, B, S], saturated bool [T-1, B, S]): entry k belongs to the observation interval [t_k, t_k+1].
+    `saturated` means the tolerance was NOT met there: the ladder reached its ceiling `substeps` and the interval was taken with
+    that many steps all the same."""
+    cls = model if isinstance(model, type) else type(model)
+    if getattr(cls, "step_tolerance", None) is None:
+        raise ModelDefinitionError("%s has no step_tolerance: its trajectory has no count row" % cls.__name__)
+    rows = len(cls.species) + (4 if cls._precision_def is not None else 0) + 1
+    if traj.dim() != 4 or rows not in (traj.shape[1], traj.shape[2]):
+        raise RuntimeError("%s: a trajectory [T, %d, B, S] or a solution [B, S, %d, T] is expected, got %s"
+                           % (cls.__name__, rows, rows, list(traj.shape)))
+    row = traj[:, -1] if traj.shape[1] == rows else traj[:, :, -1, :].permute(2, 0, 1)  # [T, B, S]
+    code = row[1:].detach()
+    return code.abs().round().to(torch.int32), code < 0
 
 
 def _ident(key):
@@ -2095,6 +2156,8 @@ def register_kernel(cls, neural=False):
     if cls._trace.delays:  # (delayed reads: the fixed-grid schemes only; the adjoint needs its history workspace)
         hip.GENERATED_DELAYS[key] = len(cls._trace.delays)
     hip.GENERATED_SUBSTEPS[key] = int(cls.substeps)  # (above 1: the library holds the fixed-grid schemes only)
+    if cls.step_tolerance is not None:  # (step control: substeps is the ladder's ceiling, the trajectory has a count row)
+        hip.GENERATED_STEP_CONTROL[key] = (int(cls.substeps), float(cls.step_tolerance[0]), float(cls.step_tolerance[1]))
     if cls._trace.jmp is not None:  # (a state jump at the observation points: the fixed-grid schemes only, likewise)
         hip.GENERATED_JUMP.add(key)
     if cls._trace.start is not None:  # (a start map: the fixed-grid schemes only, likewise)
@@ -2137,6 +2200,7 @@ class GeneratedOdeModel(OdeModel):
     newton_iterations = 4  # Newton iterations of one implicit step, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
     implicit_order = 1  # the order of the implicit scheme: 1 backward Euler, 2 the two-stage SDIRK (needs implicit = True)
     substeps = 1  # steps a fixed-grid solver takes over each observation interval, 1 .. MAX_SUBSTEPS (module docstring)
+    step_tolerance = None  # (rtol, atol): each trajectory picks its own steps per interval, 1 -> 2 -> .. -> substeps (module docstring)
     lead_in = 0.0  # L > 0: the length of an unscored phase before the first observation point, in the units of `times`
     lead_in_steps = 1  # steps a fixed-grid solver takes over the lead-in phase, 1 .. MAX_LEAD_IN_STEPS (module docstring)
     algebraic = ()  # names of the algebraic variables, read as self.algebraic.<name> in rhs and observe (module docstring)
@@ -2304,6 +2368,12 @@ class GeneratedOdeModel(OdeModel):
                 "chooses its own steps and is not available to it (fixed-grid solvers: %s)" % (
                     type(self).__name__, type(self).substeps, config.params.solver,
                     ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if type(self).step_tolerance is not None and config.params.solver in STEP_CONTROL_DECLINED_SOLVERS:  # (likewise)
+            raise NotImplementedError(
+                "%s has step_tolerance = %r, which divides the observation interval by step doubling: '%s' takes a fixed step "
+                "h0 that is not the interval and is not available to it (solvers with step control: %s)" % (
+                    type(self).__name__, type(self).step_tolerance, config.params.solver,
+                    ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS) - set(STEP_CONTROL_DECLINED_SOLVERS)))))
         if type(self)._jump_def is not None and config.params.solver in hip.ADAPTIVE_SOLVERS:  # (likewise)
             raise NotImplementedError(
                 "%s defines jump(self, y, p, c), a state jump applied between two steps of a fixed-grid scheme: the adaptive "
@@ -2378,6 +2448,18 @@ class GeneratedOdeModel(OdeModel):
     def has_start(self):
         """True for a model with a start map, start(self, y, p, c) (module docstring)."""
         return type(self)._start_def is not None
+
+    @property
+    def has_step_control(self):
+        """True for a model with step control, step_tolerance = (rtol, atol) (module docstring): the solution has one more row
+        behind the species and the precision rows, each interval's step count (substep_counts)."""
+        return type(self).step_tolerance is not None
+
+    def expand_precisions(self, theta, times, x_states):
+        # (step control: the count row, the last of the solution's rows, is neither a species nor a precision)
+        if type(self).step_tolerance is not None:
+            x_states = x_states[:, :, :-1, :]
+        return super(GeneratedOdeModel, self).expand_precisions(theta, times, x_states)
 
     @property
     def has_lead_in(self):
@@ -2994,6 +3076,8 @@ def _validate(cls):
         for has, what, why in (
                 (cls.implicit is True, "implicit = True", "the read would be data of the implicit step, and neither the "
                                                           "Jacobian's use of it nor its adjoint is built"),
+                (cls.step_tolerance is not None, "step_tolerance = %r" % (cls.step_tolerance,),
+                 "the history is stored at the observation points only, and a read inside a trial step has no adjoint path"),
                 (cls.substeps != 1, "substeps = %r" % (cls.substeps,), "the history is stored at the observation points only"),
                 (cls.lead_in != 0, "lead_in = %r" % (cls.lead_in,), "the history before the first point is the constant stored state"),
                 (getattr(cls, "_jump_def", None) is not None, "jump(self, y, p, c)", "the stored history holds the left limits"),
@@ -3088,6 +3172,26 @@ def _validate(cls):
         raise ModelDefinitionError("%s has substeps = %d and %d species: the adjoint keeps (substeps - 1) * species rows of an "
                                    "interval's intermediate states in LDS, at most %d (MAX_SUBSTEP_ROWS)"
                                    % (name, m, len(cls.species), MAX_SUBSTEP_ROWS))
+    tol = cls.step_tolerance
+    if tol is not None:
+        if (not isinstance(tol, (tuple, list)) or len(tol) != 2
+                or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in tol)
+                or not all(math.isfinite(v) and abs(v) <= _F32_MAX and v >= 0 for v in tol)
+                or not any(float(np.float32(v)) > 0 for v in tol)):
+            raise ModelDefinitionError("%s.step_tolerance = %r; it is (rtol, atol), two finite float32 numbers >= 0 that are not both "
+                                       "0: an interval is accepted where |fine - coarse| <= atol + rtol * max(|fine|, |coarse|) on "
+                                       "every species" % (name, tol))
+        if m not in STEP_CONTROL_CEILINGS:
+            raise ModelDefinitionError("%s has step_tolerance and substeps = %d: with step control substeps is the ceiling of the "
+                                       "ladder 1 -> 2 -> 4 -> 8 steps per observation interval, one of %s"
+                                       % (name, m, ", ".join(str(c) for c in STEP_CONTROL_CEILINGS)))
+        for has, what, why in (
+                (bool(nets), "networks", "the adjoint's dump of a network holds one evaluation per stage and observation interval"),
+                (getattr(cls, "_diffusion_def", None) is not None, "diffusion(self, y, p, c)",
+                 "the draws are counted by the steps of a fixed count, and the difference of two noisy trial solutions measures "
+                 "the noise, not the truncation error")):
+            if has:
+                raise ModelDefinitionError("%s has step_tolerance and %s: %s -- declined in this version" % (name, what, why))
     if m > 1 and nets:
         raise ModelDefinitionError("%s has substeps = %d and networks: the adjoint's dump of a network holds one evaluation per "
                                    "stage and observation interval (substeps > 1 is for models without networks)" % (name, m))

@@ -395,8 +395,8 @@ class OdeModel(nn.Module):
         """The DecodedSolution of an adaptive route: the log-likelihood at the output times with torch ops (observations
         exist there only) from the precision rows -- autograd then hands the adjoint kernel its upstream gradients."""
         if observations is not None:
-            if spec.n_species < spec.n_states:  # neural precisions: the last four states (reference precisions.py:89-94)
-                prec = traj[:, spec.n_species:, :, :]
+            if spec.n_precision_rows:  # neural precisions: the four states behind the species (reference precisions.py:89-94)
+                prec = traj[:, spec.n_species:spec.n_species + 4, :, :]
             else:  # constant precisions: four theta rows broadcast over time (reference precisions.py:31-35)
                 rows = [row_of[n] for n in spec.slots[-4:]]
                 prec = packed[rows][None]

@@ -96,6 +96,10 @@ class OdeProblemSpec:
                 "model '%s' has substeps = %d, which divide the observation intervals of a fixed-grid scheme: the adaptive solver "
                 "'%s' chooses its own steps and is not available to it (fixed-grid solvers: %s)" % (
                     model, hip.GENERATED_SUBSTEPS[model], solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if solver in ("modeuler", "modeulerwhile") and model in hip.GENERATED_STEP_CONTROL:  # (likewise)
+            raise NotImplementedError(
+                "model '%s' has step control (step_tolerance), which divides the observation interval by step doubling: '%s' "
+                "takes a fixed step h0 that is not the interval and is not available to it" % (model, solver))
         if solver in hip.ADAPTIVE_SOLVERS and model in hip.GENERATED_JUMP:  # (likewise)
             raise NotImplementedError(
                 "model '%s' has a state jump at the observation points, applied between two steps of a fixed-grid scheme: the "
@@ -164,8 +168,12 @@ class OdeProblemSpec:
         # a generated model's own networks [(n_inputs, n_hidden, n_outputs)]: their weights lead the weight buffer, their
         # dump fields lead the adjoint's aux buffer (decoder_weight_grads)
         self.networks = list(hip.GENERATED_NETWORKS.get(model, ()))
-        # a generated model's own precision map: n_states - n_species = 4 rows the kernel stores, not a precision network
+        # a generated model's own precision map: 4 rows behind the species that the kernel stores, not a precision network
         self.own_precision = model in hip.GENERATED_OWN_PRECISION
+        # a generated model with step control: the last row of n_states holds each interval's step count (modelgen.substep_counts);
+        # the rows n_species .. n_species + n_precision_rows - 1 are the precisions, of either kind, where the model has them
+        self.step_control = model in hip.GENERATED_STEP_CONTROL
+        self.n_precision_rows = self.n_states - self.n_species - (1 if self.step_control else 0)
         # a generated model's delayed reads: the adjoint's aux buffer is its history workspace, with or without weights
         self.n_delays = hip.GENERATED_DELAYS.get(model, 0)
         self.covers_all_rows = len({row_of[s] for s in self.slots}) == n_rows
@@ -732,7 +740,7 @@ def decoder_weight_grads(spec, prob, aux, g_w):
     is the same bits run to run.  The precision network's section (neural_precision_weight_grads) follows."""
     if not spec.networks:
         return neural_precision_weight_grads(spec, prob, aux, g_w)
-    neural = spec.n_species < spec.n_states and not spec.own_precision
+    neural = spec.n_precision_rows > 0 and not spec.own_precision
     F_all = sum(I + 2 * H + O for I, H, O in spec.networks)
     if neural:
         F_all += 8 + (spec.n_species + 1) + 2 * max(int(spec.proto.n_hidden_prec), 0)
@@ -767,7 +775,7 @@ def neural_precision_weight_grads(spec, prob, aux, g_w):
     76-87; buffer order Wp [4][NIN], bp [4], Wd [4][NIN], bd [4]) from the adjoint kernel's dump [8+NIN][E][n] --
     production / degradation pre-activation adjoints (fields 0..3 / 4..7) times the layer inputs (fields 8..) -- written
     into g_w by vihds_gram_blocks; the biases were already added to g_w by the kernel."""
-    NIN = spec.n_states - 4 + 1
+    NIN = spec.n_species + 1  # (the precision states are the four rows behind the species)
     H = max(int(spec.proto.n_hidden_prec), 0)
     F = 8 + NIN + 2 * H
     C = aux.numel() // F

@@ -341,13 +341,15 @@ class Training:
             traj = sol.traj_buffer.detach()
             # (a solution without a stored x_predict -- params.lazy_x_predict -- has the kernel form it from the states)
             xpred = sol.xpred_buffer.detach() if getattr(sol, "has_x_predict", True) else None
-            if ode_model.precisions.dynamic:  # the last four states are the precisions (reference precisions.py:89-94)
-                summ = ops.iw_summaries(log_unnormalized_iws.detach(), lse.detach(), traj, xpred, traj.shape[1] - 4,
+            # (a generated model with step control: the last row of the trajectory holds its step counts -- no species, no precision)
+            n_rows = traj.shape[1] - (1 if getattr(ode_model, "has_step_control", False) else 0)
+            if ode_model.precisions.dynamic:  # four rows behind the species are the precisions (reference precisions.py:89-94)
+                summ = ops.iw_summaries(log_unnormalized_iws.detach(), lse.detach(), traj, xpred, n_rows - 4,
                                         observe_kind=ode_model.observe_kind)
             else:
                 packed, row_of = theta.pack(ode_model.precisions.precision_vars)
                 rows = [row_of[v] for v in ode_model.precisions.precision_vars]
-                summ = ops.iw_summaries(log_unnormalized_iws.detach(), lse.detach(), traj, xpred, traj.shape[1],
+                summ = ops.iw_summaries(log_unnormalized_iws.detach(), lse.detach(), traj, xpred, n_rows,
                                         theta=packed.detach(), prec_rows=rows, observe_kind=ode_model.observe_kind)
         else:
             w = (log_unnormalized_iws - lse[:, None]).exp()[:, :, None, None]
