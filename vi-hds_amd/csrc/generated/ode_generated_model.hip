@@ -53,6 +53,9 @@ static_assert(!(has_diffusion<VIHDS_GEN_CORE>::value &&
                 (VIHDS_GEN_NEURAL != 0 || has_jacobian<VIHDS_GEN_CORE>::value || net_fields<VIHDS_GEN_CORE>::value > 0 ||
                  lead_in<VIHDS_GEN_CORE>::value > 0 || n_delays<VIHDS_GEN_CORE>::value > 0)),
               "process noise combines with the explicit fixed-grid schemes only: no NeuralPrecisions, implicit, networks, lead_in or delays");
+static_assert(noise_channels<VIHDS_GEN_CORE>::value >= 0 && noise_channels<VIHDS_GEN_CORE>::value <= 8 &&
+                  (noise_channels<VIHDS_GEN_CORE>::value == 0 || has_diffusion<VIHDS_GEN_CORE>::value),
+              "noise channels: at most 8 (two Philox blocks per step), and such a struct declares HAS_DIFFUSION (vihds_sde.hpp)");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds

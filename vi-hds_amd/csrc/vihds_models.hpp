@@ -1084,6 +1084,17 @@ template <class M, class = void>
 struct has_diffusion : std::false_type {};
 template <class M>
 struct has_diffusion<M, std::void_t<decltype(M::HAS_DIFFUSION)>> : std::bool_constant<M::HAS_DIFFUSION> {};
+// The channel form of that noise (vihds/modelgen.py: noise_channels, channel_noise(self, y, p, c)): every reaction channel r has
+// a Wiener process of its own, which enters every species the channel touches.  Such a core declares HAS_DIFFUSION = true as well
+// (the key, cond_tail and the time loops treat it as any noisy model), NOISE_CHANNELS = R, channel_species(r) (bit q: channel r
+// enters species q) and, in place of diffusion / diffusion_vjp,
+//   channel_noise(y, p, G)                G[q * R + r] = the amplitude of channel r in species q (the entries of the pattern only)
+//   channel_noise_vjp(y, p, Gb, yb, pb)   yb += (d G/d y)^T Gb ; pb += (d G/d p)^T Gb   (forward values recomputed)
+// 0 for every other model: noisy_step / noisy_step_vjp take the per-species path.
+template <class M, class = void>
+struct noise_channels : std::integral_constant<int, 0> {};
+template <class M>
+struct noise_channels<M, std::void_t<decltype(M::NOISE_CHANNELS)>> : std::integral_constant<int, M::NOISE_CHANNELS> {};
 // A core generated with `missing_observations = True` (vihds/modelgen.py) declares MASKED_OBS = true: a data row of cond carries
 // one mask word per time point behind its forcing samples (vihds_mask.hpp: bit j says whether signal j has a read there), and
 // the scoring point of the forward and the adjoint time loops selects by it.  False for every hand-written model; WithPrec<>

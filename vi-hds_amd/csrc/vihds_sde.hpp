@@ -15,6 +15,17 @@
 // thread's data row of cond ([treatments | forcing samples | key lo, key hi]), converted by truncation: the forward and the
 // adjoint launch are given the same cond, so they agree by construction.
 //
+// Reaction channels (vihds/modelgen.py: noise_channels, channel_noise(self, y, p, c); vihds_models.hpp: noise_channels<M>).  A
+// model may instead give every reaction channel r = 0 .. R-1 a Wiener process of its own, which enters every species q the
+// channel touches with the amplitude G[q][r] (the chemical Langevin equation: G[q][r] = nu_r[q] sqrt(a_r)):
+//     dw[r] = sqrtf(h) * xi_r;   for r ascending, for q ascending in the channel's pattern:  y[q] = fmaf(G[q][r], dw[r], y[q])
+// after the unchanged step Phi_h, G at the step's start state.  xi_r is normal r & 3 of the block at the counter
+// (traj, r >> 2, step, kSdeStreamTag): the layout above with the channel index where the species index stood, so a model with one
+// channel per species and a diagonal G repeats the per-species model bit for bit.  G is the flat array G[q * R + r]; an entry
+// outside the pattern M::channel_species(r) is a structural zero, never written and never read.  The adjoint regenerates dw,
+// seeds Gb[q][r] = lam'[q] * dw[r] on the pattern, runs channel_noise_vjp into a temporary yb, then the scheme's own step
+// adjoint on lam, then lam += yb.
+//
 // The first part below (which h a solver uses, the counter, block and lane of a species, the step index of a sub-step) uses
 // no HIP intrinsic and is __host__ __device__: a stand-alone host program can run it (tests/test_modelgen_sde_host.py compiles
 // one with the address and undefined-behaviour sanitizers).  The wrappers around the step follow under __HIPCC__.
@@ -64,6 +75,46 @@ VIHDS_SDE_HD float sde_step_length(int solver, float t0, float t1, float h0) {
 // whether any species of Philox block q is noisy under `mask` (bit j: species j has a non-zero amplitude)
 VIHDS_SDE_HD constexpr bool sde_block_drawn(unsigned int mask, int q) { return ((mask >> (4 * q)) & 0xfu) != 0u; }
 
+
+// ---- reaction channels: the draw of channel r sits where the draw of species r sits in the per-species layout
+VIHDS_SDE_HD unsigned int sde_channel_block(int channel) { return sde_block(channel); }
+VIHDS_SDE_HD int sde_channel_lane(int channel) { return sde_lane(channel); }
+VIHDS_SDE_HD SdeCounter sde_channel_counter(unsigned int traj, int channel, unsigned int step) {
+  return sde_counter(traj, channel, step);
+}
+// the channels 0 .. R-1 as a mask for sde_block_drawn: a Philox block none of whose channels exist draws nothing
+VIHDS_SDE_HD constexpr unsigned int sde_channel_mask(int R) { return R >= 32 ? 0xffffffffu : ((1u << R) - 1u); }
+// whether channel r enters species q under the model's pattern (M::channel_species(r): bit q)
+template <class M>
+VIHDS_SDE_HD constexpr bool sde_channel_enters(int r, int q) {
+  return ((M::channel_species(r) >> q) & 1u) != 0u;
+}
+// y[q] = fmaf(G[q][r], dw[r], y[q]) for r ascending and, within a channel, q ascending over the channel's pattern: the order is
+// part of the definition (two channels that enter one species add in this order).  M gives N, NOISE_CHANNELS, channel_species
+template <class M>
+VIHDS_SDE_HD void sde_channel_accumulate(const float* G, const float* dw, float* y) {
+  constexpr int N = M::N, R = M::NOISE_CHANNELS;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      if (sde_channel_enters<M>(r, q)) y[q] = __builtin_fmaf(G[q * R + r], dw[r], y[q]);
+    }
+  }
+}
+// the seeds of channel_noise_vjp: Gb[q][r] = lam[q] * dw[r] on the pattern (nothing else of Gb is written or read)
+template <class M>
+VIHDS_SDE_HD void sde_channel_seed(const float* lam, const float* dw, float* Gb) {
+  constexpr int N = M::N, R = M::NOISE_CHANNELS;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      if (sde_channel_enters<M>(r, q)) Gb[q * R + r] = lam[q] * dw[r];
+    }
+  }
+}
+
 }  // namespace vihds
 
 #if defined(__HIPCC__)
@@ -109,22 +160,53 @@ __device__ __forceinline__ void sde_increments(const SdeKey& key, unsigned int s
   }
 }
 
+// dw[r] = sqrt(h) * xi_r for the R channels of M: the instructions of sde_increments with the channel index where the species
+// index stood.  The forward and the adjoint both call this
+template <class M>
+__device__ __forceinline__ void sde_channel_increments(const SdeKey& key, unsigned int step, float h, float* dw) {
+  constexpr int R = noise_channels<M>::value;
+  const float sh = sqrtf(h);
+#pragma unroll
+  for (int q = 0; q < (R + 3) / 4; ++q) {
+    if (sde_block_drawn(sde_channel_mask(R), q)) {  // (a constant of the model: the branch folds)
+      float z[4];
+      const SdeCounter c = sde_channel_counter(key.traj, 4 * q, step);
+      philox_normal4(c.c0, c.c1, c.c2, c.c3, key.k0, key.k1, z);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (4 * q + r < R) dw[4 * q + r] = sh * z[r];
+      }
+    }
+  }
+}
+
 // one noisy step: y <- Phi_h(y) + g(y, p) * dw, g at the start state.  The amplitudes are evaluated first and live across the
 // scheme's step; the draws live only after it
 template <class M, int SOLVER>
 __device__ __forceinline__ void noisy_step(float t0, float t1, float h0, unsigned int step_index, const SdeKey& key, float* y,
                                            const float* p, const float* wts) {
   constexpr int N = M::N;
-  float g[N];
+  if constexpr (noise_channels<M>::value > 0) {
+    // reaction channels: the amplitudes of the pattern live across the scheme's step, the R increments only after it
+    constexpr int R = noise_channels<M>::value;
+    float G[N * R];
+    M::channel_noise(y, p, G);
+    ode_step<M, SOLVER>(t0, t1, h0, y, p, wts);
+    float dw[R];
+    sde_channel_increments<M>(key, step_index, sde_step_length(SOLVER, t0, t1, h0), dw);
+    sde_channel_accumulate<M>(G, dw, y);
+  } else {
+    float g[N];
 #pragma unroll
-  for (int j = 0; j < N; ++j) g[j] = 0.f;
-  M::diffusion(y, p, g);
-  ode_step<M, SOLVER>(t0, t1, h0, y, p, wts);
-  float dw[N];
-  sde_increments<M>(key, step_index, sde_step_length(SOLVER, t0, t1, h0), dw);
+    for (int j = 0; j < N; ++j) g[j] = 0.f;
+    M::diffusion(y, p, g);
+    ode_step<M, SOLVER>(t0, t1, h0, y, p, wts);
+    float dw[N];
+    sde_increments<M>(key, step_index, sde_step_length(SOLVER, t0, t1, h0), dw);
 #pragma unroll
-  for (int j = 0; j < N; ++j) {
-    if ((M::NOISE_MASK >> j) & 1u) y[j] = __builtin_fmaf(g[j], dw[j], y[j]);
+    for (int j = 0; j < N; ++j) {
+      if ((M::NOISE_MASK >> j) & 1u) y[j] = __builtin_fmaf(g[j], dw[j], y[j]);
+    }
   }
 }
 
@@ -136,17 +218,33 @@ __device__ __forceinline__ void noisy_step_vjp(float t0, float t1, float h0, uns
                                                const float* u, const float* p, const float* wts, float* lam, float* pb,
                                                Ctx& wtsb) {
   constexpr int N = M::N;
-  float gb[N], yb[N];
-  sde_increments<M>(key, step_index, sde_step_length(SOLVER, t0, t1, h0), gb);
+  if constexpr (noise_channels<M>::value > 0) {
+    constexpr int R = noise_channels<M>::value;
+    float yb[N];
+    {
+      float dw[R], Gb[N * R];
+      sde_channel_increments<M>(key, step_index, sde_step_length(SOLVER, t0, t1, h0), dw);
+      sde_channel_seed<M>(lam, dw, Gb);
 #pragma unroll
-  for (int j = 0; j < N; ++j) {
-    gb[j] *= lam[j];
-    yb[j] = 0.f;
+      for (int j = 0; j < N; ++j) yb[j] = 0.f;
+      M::channel_noise_vjp(u, p, Gb, yb, pb);
+    }
+    ode_step_vjp<M, SOLVER>(t0, t1, h0, u, p, wts, lam, pb, wtsb);
+#pragma unroll
+    for (int j = 0; j < N; ++j) lam[j] += yb[j];
+  } else {
+    float gb[N], yb[N];
+    sde_increments<M>(key, step_index, sde_step_length(SOLVER, t0, t1, h0), gb);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      gb[j] *= lam[j];
+      yb[j] = 0.f;
+    }
+    M::diffusion_vjp(u, p, gb, yb, pb);
+    ode_step_vjp<M, SOLVER>(t0, t1, h0, u, p, wts, lam, pb, wtsb);
+#pragma unroll
+    for (int j = 0; j < N; ++j) lam[j] += yb[j];
   }
-  M::diffusion_vjp(u, p, gb, yb, pb);
-  ode_step_vjp<M, SOLVER>(t0, t1, h0, u, p, wts, lam, pb, wtsb);
-#pragma unroll
-  for (int j = 0; j < N; ++j) lam[j] += yb[j];
 }
 
 }  // namespace vihds

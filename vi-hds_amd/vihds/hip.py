@@ -60,7 +60,8 @@ GENERATED_ALGEBRAIC = {}
 # is the trajectory stored on the observation grid), their forward needs the trajectory buffer and their adjoint a workspace of
 # n_delays * T * B * S floats in aux (vihds_ode_bwd_aux_floats), wanted whether or not a weight gradient is
 GENERATED_DELAYS = {}
-# keys of registered generated models with process noise (`diffusion(self, y, p, c)`): they decline the adaptive solvers (the
+# keys of registered generated models with process noise (`diffusion(self, y, p, c)`, or its channel form `noise_channels` /
+# `channel_noise(self, y, p, c)`: the library knows both as diffusion = 1): they decline the adaptive solvers (the
 # draws are counted by the steps of the observation grid), and a row of their cond ends with the two words of its noise key
 GENERATED_DIFFUSION = set()
 # keys of registered generated models with missing observations (`missing_observations = True`): they decline the adaptive

@@ -362,9 +362,59 @@ Combines with forcings, substeps, jump, start, the three observation hooks and t
 definition, each with its reason: implicit = True, networks, NeuralPrecisions, algebraic, delays, lead_in > 0, a wrong arity
 (there is no t to read) or a wrong number of returned values.  Such a model takes the fixed-grid solvers only (solve and
 ops.OdeProblemSpec raise NotImplementedError before anything is built or queued; the library answers VIHDS_E_UNSUPPORTED).
-Open: non-diagonal noise, Milstein or Stratonovich schemes, drift-implicit steps, the refused combinations, S sharded over
-ranks (the trajectory index is the launch's), noise in the lead-in.  torch_diffusion restates the hook with torch ops;
-tests/modelgen_sde_models.py has the float64 definition of the scheme, which takes the draws as an argument.
+Open: Milstein or Stratonovich schemes, drift-implicit steps, the refused combinations, S sharded over ranks (the trajectory
+index is the launch's), noise in the lead-in; non-diagonal noise is built as channels (next paragraph), a dense correlated
+matrix beyond them is not.  torch_diffusion restates the hook with torch ops; tests/modelgen_sde_models.py has the float64
+definition of the scheme, which takes the draws as an argument.
+
+Noise channels.  The intrinsic noise of a reaction network is not diagonal: in the chemical Langevin equation every REACTION has
+a Wiener process of its own, which enters every species the reaction touches through the stoichiometry,
+dX = sum_r nu_r a_r(X) dt + sum_r nu_r sqrt(a_r(X)) dW_r.  A conversion A -> B moves A down and B up by the same increment (the
+total is conserved); a species that is produced and degraded has two channels whose variances add; mRNA and protein, immature and
+matured fluorophore are correlated.  In place of diffusion a class may declare
+
+        noise_channels = ["tx", "deg", "mature"]     # 1 .. MAX_NOISE_CHANNELS = 8 identifiers, names of their own
+        def channel_noise(self, y, p, c):            # -> one list per channel, each with one amplitude per species
+            a_tx = sqrt(maximum(p.k * y.M, 0.0))
+            return [[a_tx, 0.0, ...], [-a_deg, 0.0, ...], [0.0, -a_m, a_m, ...]]
+
+Entry [r][q] is G[q][r], the amplitude with which channel r enters species q.  The hook has the rules of diffusion: no t, exactly
+its arguments, every operation of the model language (the piecewise ones included), self.forcing.<name> reads the sample of the
+interval's first point, channel_noise = None in a subclass removes it (and the inherited names), a treatment it reads becomes
+one more effective parameter.  An entry that folds to the constant 0 is a structural zero: it draws nothing, costs nothing and
+has no adjoint.  The scheme, exactly: for every step the fixed-grid scheme takes (every sub-step when substeps > 1) from the
+state u over the length h of the diagonal scheme,  dw[r] = sqrtf(h) * xi_r;  u' = Phi_h(u);  then for r = 0 .. R-1 ascending
+and every species q of channel r's pattern, ascending,  u'[q] = fmaf(G[q][r], dw[r], u'[q]),  G evaluated at the step's start
+state.  xi_r is normal r & 3 of the Philox block at the counter (b * S + s, r >> 2, k * substeps + j, the stream's tag) under the
+row's key: the layout of the diagonal hook with the channel index where the species index stood -- the tag, the key columns,
+noise_key, noise_seed and noise_key_state are the same, and a class with one channel per species and the diagonal amplitudes
+repeats its diffusion twin bit for bit.  The adjoint regenerates dw, seeds Gb[q][r] = lam'[q] * dw[r] on the pattern, runs
+channel_noise_vjp (reverse mode, forward values recomputed, it adds), the scheme's own step adjoint on lam, then lam += yb: no
+atomics, nothing stored, gradients repeat bit for bit.  The struct gains HAS_DIFFUSION (so everything that asks for a noisy model
+-- the key, the width of cond, the declined solvers -- holds unchanged), NOISE_CHANNELS, NOISE_ENTRIES, channel_species(r) (bit
+q: channel r enters species q), channel_noise(y, p, G) and channel_noise_vjp(y, p, Gb, yb, pb), G the flat array
+G[q * R + r]; the kernels' trait is noise_channels<M> (csrc/vihds_sde.hpp).  On instances has_diffusion is true and
+n_noise_channels is R (0 for every other model).
+Written once: langevin(stoichiometry, propensities, floor=0.0) returns the columns nu_r[q] * sqrt(maximum(a_r, 0.0) + floor)
+for channel_noise and langevin_drift(stoichiometry, propensities) the sums sum_r nu_r[q] * a_r for rhs; stoichiometry[r][q] is an
+integer, and a 0 is a structural zero.  Both are plain Python over this module's operations (symbols, tensors and numbers alike).
+The trap of the diagonal hook holds here too: the derivative of sqrt is infinite at 0, so a propensity that starts at 0 or is
+driven there gives a gradient that is not finite and the training step skips its update -- give langevin a floor > 0, or start
+the species above 0.
+Refused at class definition, each with its reason: channel_noise together with diffusion; noise_channels without the hook or
+the hook without noise_channels; a wrong arity; a wrong number of channels or of entries per channel; a channel that enters no
+species; a name that is also a species, a parameter, a forcing, an algebraic variable or a delay; more than MAX_NOISE_CHANNELS
+channels; more than MAX_NOISE_ENTRIES = 32 entries that are not structurally zero (each is a register held across the scheme's
+step: eight channels into four species, which compiles without scratch); what diffusion refuses, for its reasons (implicit =
+True, networks, NeuralPrecisions, algebraic, delays, lead_in > 0); and step_tolerance (two noisy trial solutions differ by the
+noise).  It combines with what diffusion combines with: forcings, substeps, jump, start, the three observation hooks,
+missing_observations and the piecewise operations; the fixed-grid solvers only, declined as for diffusion.  The hook's record,
+CHANNEL_NOISE_HOOK, stands beside the pinned tuples: MODEL_HOOKS = TRACED_HOOKS + (CHANNEL_NOISE_HOOK,) is what tracing, code
+generation and the capture of the definitions walk.  torch_channel_noise restates the hook with torch ops ([B,S,N,R,T]);
+tests/modelgen_channel_models.py has the float64 definition, which takes the draws as an argument.
+Open: more than 8 channels (a dense correlated matrix over many species), tau-leaping (Poisson increments in place of normal
+ones), Milstein or Stratonovich schemes (the channels do not commute: Levy areas), drift-implicit steps, S sharded over ranks,
+noise in the lead-in.
 
 Missing observations.  Plate-reader data has dropped and saturated reads, plates of different duration and channels that a plate
 does not record; the kernels' data contract is otherwise a complete rectangle of finite reads.  A class may set
@@ -462,6 +512,12 @@ MAX_LEAD_IN_STEPS = 8
 # unknowns of a model with `algebraic` variables: the matrix of a Newton step on the constraint lives in registers beside the
 # states, its structural pattern is one 16-bit constant (tests/test_modelgen_algebraic_host.py compiles four without scratch)
 MAX_ALGEBRAIC = 4
+# reaction channels of a model with `noise_channels` (each a Wiener process of its own: two Philox blocks of four normals), and
+# the entries of channel_noise that are not the constant 0: every one is an amplitude that lives in a register across the scheme's
+# step, beside the states, the parameters and the stages.  Four entries per channel on average is what compiles without scratch
+# with rk4 (tests/test_modelgen_channel_host.py builds that worst case; DESIGN.md 4.7 has the compiler's figures)
+MAX_NOISE_CHANNELS = 8
+MAX_NOISE_ENTRIES = 32
 
 
 class ModelDefinitionError(TypeError):
@@ -1278,7 +1334,9 @@ class Hook(object):
                          adds into the adjoint array of each group that has one (_GROUP_ADJOINT), in this order, and last
                          into pb of the named effective parameters (a treatment has no adjoint)
       outputs            what the four returned values are, in error messages
-      n_outputs          how many values it returns: 4, or "species" (one per species: the state jump)
+      n_outputs          how many values it returns: 4, "species" (one per species: the state jump) or "channels" (one list
+                         per noise channel, each with one value per species: the reaction-channel noise, kept as the flat
+                         list G[q * R + r] of species q and channel r)
       attr, traced       the class attribute that holds the definition; the Trace attribute that holds its four nodes
       c_out, seed        the C arrays of the values and of their adjoints
       c_forward, c_adjoint   the members' signatures
@@ -1309,8 +1367,10 @@ class Hook(object):
     def targets(self):
         return [(k, _GROUP_ADJOINT[k]) for k in self.groups + ("p",) if k in _GROUP_ADJOINT]
 
-    def count(self, n_species):
-        """The number of values the hook returns for a model of n_species species."""
+    def count(self, n_species, n_channels=0):
+        """The number of values the hook returns for a model of n_species species (and n_channels noise channels)."""
+        if self.n_outputs == "channels":
+            return n_species * n_channels
         return n_species if self.n_outputs == "species" else self.n_outputs
 
 
@@ -1383,9 +1443,63 @@ DIFFUSION_HOOK = \
          note=": it sees the species at a step's start, the effective parameters and the treatments -- no t "
               "(or None in a subclass, for no process noise)")
 
+# reaction-channel noise: the other form of the scheme's noise term, called where diffusion is (a class has one of the two).  It
+# returns one list per declared channel (noise_channels), each with one amplitude per species: entry [r][q] is G[q][r], the
+# amplitude with which the Wiener process of channel r enters species q.  The traced outputs are the flat list G[q * R + r]; an
+# entry that folds to the constant 0 is a structural zero (skips_zero: not written, no draw, no adjoint), and the struct's
+# channel_species(r) says which species channel r enters
+CHANNEL_NOISE_HOOK = \
+    Hook("channel_noise", signature="channel_noise(self, y, p, c)", groups=("y",),
+         outputs="one list per noise channel, each with the amplitude of that channel in every species; 0.0 where it does not enter",
+         n_outputs="channels", attr="_channel_noise_def", traced="chan", c_out="G", seed="Gb",
+         switch="HAS_DIFFUSION", switch_note="process noise by reaction channels, u' = Phi_h(u) + G(u) sqrt(h) xi per step: channel_noise / channel_noise_vjp (vihds_sde.hpp)",
+         c_forward=["  __device__ static void channel_noise(const float* y, const float* p, float* G) {"],
+         c_adjoint=["  __device__ static void channel_noise_vjp(const float* y, const float* p, const float* Gb, float* yb, float* pb) {"],
+         excludes_neural="process noise", none_resets=True, checks_arguments=True, skips_zero=True,
+         note=": it sees the species at a step's start, the effective parameters and the treatments -- no t "
+              "(or None in a subclass, for no channel noise)")
+
 ALL_HOOKS = (START_HOOK,) + HOOKS  # in the order in which the forward kernel calls them
 TRACED_HOOKS = ALL_HOOKS + (DIFFUSION_HOOK,)  # ... and the hook of the scheme's step behind them
-HOOK = {h.name: h for h in TRACED_HOOKS}
+# ... and its channel form: what tracing, code generation and the capture of the definitions walk (the three tuples above are
+# pinned by earlier tests as they stand)
+MODEL_HOOKS = TRACED_HOOKS + (CHANNEL_NOISE_HOOK,)
+NOISE_HOOKS = (DIFFUSION_HOOK, CHANNEL_NOISE_HOOK)  # the two forms of process noise
+HOOK = {h.name: h for h in MODEL_HOOKS}
+
+
+def _class_noise_channels(cls):
+    return list(getattr(cls, "noise_channels", None) or ())
+
+
+def _channel_entries(cls, g, out, N):
+    """What channel_noise returned -- one list per declared channel, each with one amplitude per species -- as the flat list of
+    nodes G[q * R + r] (species q, channel r), checked: the number of channels, the entries per channel, no channel without a
+    species, at most MAX_NOISE_ENTRIES entries that are not the constant 0."""
+    names = _class_noise_channels(cls)
+    R = len(names)
+    if not isinstance(out, (list, tuple)) or len(out) != R:
+        raise ModelDefinitionError("%s.channel_noise must return a list of %d lists, one per noise channel (%s), and returned %s"
+                                   % (cls.__name__, R, ", ".join(names),
+                                      "%d" % len(out) if isinstance(out, (list, tuple)) else type(out).__name__))
+    for r, col in enumerate(out):
+        if not isinstance(col, (list, tuple)) or len(col) != N:
+            raise ModelDefinitionError("%s.channel_noise: channel '%s' must be a list of %d entries, the amplitude with which it "
+                                       "enters each species (0.0 where it does not), and is %s"
+                                       % (cls.__name__, names[r], N,
+                                          "a list of %d" % len(col) if isinstance(col, (list, tuple)) else type(col).__name__))
+    G = [g._arg(out[r][q]) for q in range(N) for r in range(R)]
+    for r in range(R):
+        if all(_is_const(G[q * R + r], 0.0) for q in range(N)):
+            raise ModelDefinitionError("%s.channel_noise: channel '%s' enters no species (every entry folds to the constant 0): a "
+                                       "channel without a species draws for nothing -- remove it from noise_channels"
+                                       % (cls.__name__, names[r]))
+    nz = sum(1 for e in G if not _is_const(e, 0.0))
+    if nz > MAX_NOISE_ENTRIES:
+        raise ModelDefinitionError("%s.channel_noise has %d entries that are not the constant 0: every one is an amplitude held in a "
+                                   "register across the scheme's step, at most %d (MAX_NOISE_ENTRIES)"
+                                   % (cls.__name__, nz, MAX_NOISE_ENTRIES))
+    return G
 
 
 class Trace(object):
@@ -1478,18 +1592,22 @@ class Trace(object):
                     cls.__name__, name, "no derivative depends on its outputs" if name in self._called
                     else "never called in rhs"))
         # the hooks (optional) see their groups of leaves, the effective parameters and the treatments
-        for h in TRACED_HOOKS:
+        self.n_channels = 0  # (noise channels: the R of channel_noise's R x N entries)
+        for h in MODEL_HOOKS:
             setattr(self, h.traced, None)
             definition = getattr(cls, h.attr, None)
             if definition is not None:
                 self._phase = h.name
                 out = definition(inst, *[[g.leaf(k, j) for j in range(N if k == "y" else 4)] for k in h.groups], p,
                                  _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
-                if not isinstance(out, (list, tuple)) or len(out) != h.count(N):
+                if h.n_outputs == "channels":
+                    out = _channel_entries(cls, g, out, N)
+                    self.n_channels = len(out) // N
+                elif not isinstance(out, (list, tuple)) or len(out) != h.count(N):
                     raise ModelDefinitionError("%s.%s must return a list of %d entries (%s)"
                                                % (cls.__name__, h.name, h.count(N), h.outputs))
                 setattr(self, h.traced, [g._arg(x) for x in out])
-        used = {n.val for n in _topo(self.dy + [x for h in TRACED_HOOKS for x in getattr(self, h.traced) or []]
+        used = {n.val for n in _topo(self.dy + [x for h in MODEL_HOOKS for x in getattr(self, h.traced) or []]
                                      + (self.z0 or []) + (self.con or [])) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
@@ -1715,7 +1833,7 @@ def generate_source(cls, neural=False):
     recomputed inside them) and the switches csrc/generated/ode_generated_model.hip reads.  Deterministic: the same
     definition gives byte-identical text; its hash (with the kernel headers') names the library."""
     tr = cls._trace
-    for h in TRACED_HOOKS:
+    for h in MODEL_HOOKS:
         if neural and h.excludes_neural and getattr(tr, h.traced) is not None:
             raise ModelDefinitionError("%s defines %s: a model with a %s of its own does not take NeuralPrecisions"
                                        % (cls.__name__, h.signature, h.excludes_neural))
@@ -1851,7 +1969,7 @@ def generate_source(cls, neural=False):
         net_decl = []
     # the hooks a model defines: value and adjoint run once per time point inside the time loop
     hook_decl = []
-    for h in TRACED_HOOKS:
+    for h in MODEL_HOOKS:
         outs = getattr(tr, h.traced)
         if outs is None:
             continue
@@ -1862,7 +1980,18 @@ def generate_source(cls, neural=False):
         adj = vjp(g, [e for _j, e in kept], [g.leaf("seed", j) for j, _e in kept])
         if h.switch_note:
             hook_decl.append("  static constexpr bool %s = true;  // %s" % (h.switch, h.switch_note))
-        if h.skips_zero:
+        if h.n_outputs == "channels":
+            # entry j = q * R + r of the flat list: species q, channel r.  channel_species(r): bit q set where the entry is kept
+            R, chans = tr.n_channels, _class_noise_channels(cls)
+            enters = [sum(1 << (j // R) for j, _e in kept if j % R == r) for r in range(R)]
+            hook_decl += [
+                "  static constexpr int NOISE_CHANNELS = %d;  // %s: one Wiener process each; G[q * %d + r] is the amplitude of channel r in species q"
+                % (R, ", ".join(chans), R),
+                "  static constexpr int NOISE_ENTRIES = %d;  // entries of G that are not structurally zero, of %d" % (len(kept), N * R),
+                "  // bit q: channel r enters species q (the other entries of G are structural zeros: never written, never read)",
+                "  __host__ __device__ static constexpr unsigned channel_species(int r) { return %s; }" % " : ".join(
+                    ["r == %d ? 0x%xu" % (r, m) for r, m in enumerate(enters[:-1])] + ["0x%xu" % enters[-1]])]
+        elif h.skips_zero:
             hook_decl.append("  static constexpr unsigned NOISE_MASK = 0x%xu;  // bit j: species j has noise (%s)" % (
                 sum(1 << j for j, _e in kept), ", ".join(cls.species[j] for j, _e in kept)))
         with_z = reads_z(outs)  # (observe alone may: a class without algebraic variables emits what it emitted before)
@@ -2164,12 +2293,62 @@ def register_kernel(cls, neural=False):
         hip.GENERATED_START.add(key)
     if cls.lead_in > 0:  # (a lead-in phase: the fixed-grid schemes only, likewise)
         hip.GENERATED_LEAD_IN[key] = (float(cls.lead_in), int(cls.lead_in_steps))
-    if cls._trace.dif is not None:  # (process noise: the fixed-grid schemes only; a row of cond ends with its noise key)
+    if cls._trace.dif is not None or cls._trace.chan is not None:  # (process noise: the fixed-grid schemes only; a row of cond ends with its noise key)
         hip.GENERATED_DIFFUSION.add(key)
     if cls.missing_observations:  # (missing observations: the fixed-grid schemes only; a row of cond carries its mask words)
         hip.GENERATED_MASKED.add(key)
     _REGISTERED[key] = (cls, neural)
     return mid
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# reactions written once: the chemical Langevin equation from a stoichiometry and the propensities
+# ---------------------------------------------------------------------------------------------------------------------
+def _stoichiometry(stoichiometry, propensities, what):
+    if not isinstance(stoichiometry, (list, tuple)) or not isinstance(propensities, (list, tuple)) or \
+            len(stoichiometry) != len(propensities) or not stoichiometry:
+        raise ModelDefinitionError("%s(stoichiometry, propensities): one row of stoichiometry per propensity (one per reaction), "
+                                   "at least one" % what)
+    rows = [list(nu) if isinstance(nu, (list, tuple)) else None for nu in stoichiometry]
+    if any(nu is None or len(nu) != len(rows[0]) or not nu for nu in rows):
+        raise ModelDefinitionError("%s: every row of the stoichiometry lists the change of each species, the same number of "
+                                   "entries in every row" % what)
+    for nu in rows:
+        for v in nu:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ModelDefinitionError("%s: the stoichiometry holds integers (the molecules a reaction adds or removes), got %r"
+                                           % (what, v))
+    return rows
+
+
+def langevin(stoichiometry, propensities, floor=0.0):
+    """The channels of the chemical Langevin equation, for channel_noise: stoichiometry[r][q] is the integer change of species q
+    in reaction r, propensities[r] the rate a_r of reaction r (a model quantity, a tensor or a number).  Returns one list per
+    reaction, nu_r[q] * sqrt(maximum(a_r, 0.0) + floor); an entry with nu_r[q] == 0 is the Python float 0.0, a structural zero.
+    floor > 0 keeps the root's derivative finite where a propensity reaches 0 (module docstring, "Noise channels")."""
+    rows = _stoichiometry(stoichiometry, propensities, "langevin")
+    floor = _number(floor, "langevin's floor")
+    if floor < 0.0:
+        raise ModelDefinitionError("langevin: the floor under the root is >= 0, got %g" % floor)
+    out = []
+    for nu, a in zip(rows, propensities):
+        root = sqrt(maximum(a, 0.0) + floor if floor else maximum(a, 0.0))
+        out.append([0.0 if v == 0 else (root if v == 1 else -root if v == -1 else float(v) * root) for v in nu])
+    return out
+
+
+def langevin_drift(stoichiometry, propensities):
+    """The drift of the same reactions, for rhs: one entry per species, sum_r nu_r[q] * a_r (0.0 for a species no reaction
+    changes)."""
+    rows = _stoichiometry(stoichiometry, propensities, "langevin_drift")
+    out = []
+    for q in range(len(rows[0])):
+        total = 0.0
+        for nu, a in zip(rows, propensities):
+            if nu[q] != 0:
+                total = total + (a if nu[q] == 1 else -a if nu[q] == -1 else float(nu[q]) * a)
+        out.append(total)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -2191,6 +2370,8 @@ class GeneratedOdeModel(OdeModel):
     _observe_def = _precision_def = _likelihood_def = _jump_def = None  # the definitions of the hooks the class has (HOOKS: attr)
     _start_def = None  # ... and of its start map (START_HOOK)
     _diffusion_def = None  # ... and of its process noise (HOOKS: diffusion)
+    _channel_noise_def = None  # ... or of its process noise by reaction channels (CHANNEL_NOISE_HOOK)
+    noise_channels = ()  # names of the noise channels channel_noise returns one list for, 1 .. MAX_NOISE_CHANNELS (module docstring)
     noise_seed = 0  # the seed of the noise key a model with process noise keeps on the device (module docstring), 0 .. 2^48 - 1
     missing_observations = False  # True: a batch may carry 'observed' [rows, 4, T], 1 where a read exists (module docstring)
     networks = None  # {name: Network}: learned terms of rhs (module docstring)
@@ -2217,7 +2398,7 @@ class GeneratedOdeModel(OdeModel):
             cls.parameter_names = list(declared)
             del cls.parameters
         # ... and its hooks (HOOKS says how each is taken from the class body)
-        for h in TRACED_HOOKS:
+        for h in MODEL_HOOKS:
             definition = cls.__dict__.get(h.name)
             if definition is not None:
                 ok = callable(definition)
@@ -2234,6 +2415,8 @@ class GeneratedOdeModel(OdeModel):
                 setattr(cls, h.attr, None)
             if h.settle:
                 h.settle(cls)
+        if cls._channel_noise_def is None and "noise_channels" not in cls.__dict__ and "channel_noise" in cls.__dict__:
+            cls.noise_channels = ()  # (channel_noise = None in a subclass: the inherited names go with the hook)
         if cls.__dict__.get("model_key") is None and getattr(cls, "_trace", None) is not None:
             cls._trace = Trace(cls)  # (a subclass that only changes __init__)
             return
@@ -2252,7 +2435,7 @@ class GeneratedOdeModel(OdeModel):
         if type(self)._precision_def is not None:  # the model's own precision map: the rows the kernel stores behind the species
             from vihds.precisions import ModelPrecisions
             self.precisions = ModelPrecisions()
-        if type(self)._diffusion_def is not None:
+        if _noise_def(type(self)) is not None:
             # process noise: the two-word key state a training step reads and advances (a persistent buffer: checkpoints keep the
             # stream's position) and the fixed key of evaluation passes (derived from the seed: not saved)
             seed = int(type(self).noise_seed)
@@ -2283,7 +2466,7 @@ class GeneratedOdeModel(OdeModel):
             rows = torch.cat([rows, self._mask_rows(data, observed, rows)], dim=1)
         elif observed is not None:
             raise RuntimeError(_OBSERVED_WITHOUT_MASK % (type(self).__name__, "does not set missing_observations = True"))
-        if type(self)._diffusion_def is None:
+        if _noise_def(type(self)) is None:
             return rows
         # process noise: the two words of the row's key close the row (csrc/vihds_sde.hpp)
         key = data.get("noise_key", None) if hasattr(data, "get") else getattr(data, "noise_key", None)
@@ -2393,12 +2576,12 @@ class GeneratedOdeModel(OdeModel):
                 "%s declares delays, which read the trajectory stored on the observation grid: the adaptive solver '%s' "
                 "integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
                     type(self).__name__, config.params.solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
-        if type(self)._diffusion_def is not None:  # (likewise)
+        if _noise_def(type(self)) is not None:  # (likewise)
             if config.params.solver in hip.ADAPTIVE_SOLVERS:
                 raise NotImplementedError(
-                    "%s defines diffusion(self, y, p, c), process noise drawn once per step of a fixed-grid scheme on the "
+                    "%s defines %s, process noise drawn once per step of a fixed-grid scheme on the "
                     "observation grid: the adaptive solver '%s' chooses its own steps and is not available to it (fixed-grid "
-                    "solvers: %s)" % (type(self).__name__, config.params.solver,
+                    "solvers: %s)" % (type(self).__name__, _noise_hook(type(self)).signature, config.params.solver,
                                       ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
             _check_forcing_width(type(self), conditions.shape[1], len(times), self.n_treatments)
         if type(self).missing_observations:  # (likewise)
@@ -2441,8 +2624,13 @@ class GeneratedOdeModel(OdeModel):
 
     @property
     def has_diffusion(self):
-        """True for a model with process noise, diffusion(self, y, p, c) (module docstring)."""
-        return type(self)._diffusion_def is not None
+        """True for a model with process noise, diffusion(self, y, p, c) or channel_noise(self, y, p, c) (module docstring)."""
+        return _noise_def(type(self)) is not None
+
+    @property
+    def n_noise_channels(self):
+        """The number of noise channels of a model with channel_noise(self, y, p, c) (module docstring); 0 for any other."""
+        return len(_class_noise_channels(type(self))) if type(self)._channel_noise_def is not None else 0
 
     @property
     def has_start(self):
@@ -2762,6 +2950,17 @@ class GeneratedOdeModel(OdeModel):
         return _hook_torch(cls, HOOK["diffusion"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond, n_times)
 
     @classmethod
+    def torch_channel_noise(cls, y, theta, cond, n_times=None):
+        """The model's own channel amplitudes with torch ops in y's dtype (the float64 reference of the generated channel_noise /
+        channel_noise_vjp, as torch_diffusion is for the diagonal hook): y [B,S,N,T] species at the start of steps, theta
+        {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as the kernels take it, the two key columns
+        last (n_times as in torch_diffusion) -> G [B,S,N,R,T]: entry [.., q, r, .] is the amplitude with which channel r enters
+        species q; 0 where it does not."""
+        if cls._channel_noise_def is None:
+            raise ModelDefinitionError("%s defines no channel_noise(self, y, p, c)" % cls.__name__)
+        return _hook_torch(cls, HOOK["channel_noise"], cls.__new__(cls), [y[:, :, :len(cls.species), :]], theta, cond, n_times)
+
+    @classmethod
     def torch_start(cls, y, theta, cond, n_times=None):
         """The model's own start map with torch ops in y's dtype (the float64 reference of the generated start / start_vjp): y
         [B,S,N] what initial_state returned, theta {parameter name: [B,S]} -- prepare is applied to it first -- and cond [B,C] as
@@ -2841,7 +3040,20 @@ NOISE_KEY_WORD = 1 << 24  # each an integer-valued float in [0, 2^24) (csrc/vihd
 
 
 def _noise_key_columns(cls):
-    return NOISE_KEY_COLUMNS if getattr(cls, "_diffusion_def", None) is not None else 0
+    return NOISE_KEY_COLUMNS if _noise_def(cls) is not None else 0
+
+
+def _noise_hook(cls):
+    """The record of the form of process noise the class defines (DIFFUSION_HOOK or CHANNEL_NOISE_HOOK), or None."""
+    for h in NOISE_HOOKS:
+        if getattr(cls, h.attr, None) is not None:
+            return h
+    return None
+
+
+def _noise_def(cls):
+    h = _noise_hook(cls)
+    return None if h is None else getattr(cls, h.attr)
 
 
 def noise_key_rows(key, n_rows):
@@ -3009,6 +3221,8 @@ def _hook_torch(cls, h, inst, groups, th, cond, n_times=None):
             object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda _i, name: _algebraic_misread(name, h.name)))
     out = getattr(cls, h.attr)(inst, *[list(torch.unbind(v, dim=2)) for v in groups], p, _Conditions([over_time(v) for v in cs]))
     full = lambda v: v.expand_as(ref) if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))  # noqa: E731
+    if h.n_outputs == "channels":  # (one list per channel -> [B,S,N,R,T])
+        return torch.stack([torch.stack([full(v) for v in col], dim=2) for col in out], dim=3)
     return torch.stack([full(v) for v in out], dim=2)
 
 
@@ -3087,7 +3301,33 @@ def _validate(cls):
                 raise ModelDefinitionError("%s has delays and %s: %s -- declined in this version" % (name, what, why))
     if not isinstance(alg, (list, tuple)) or not all(isinstance(a, str) and a.isidentifier() for a in alg):
         raise ModelDefinitionError("%s.algebraic must be a list of names (valid identifiers)" % name)
-    if getattr(cls, "_diffusion_def", None) is not None:
+    chans = getattr(cls, "noise_channels", None) or ()
+    if getattr(cls, "_channel_noise_def", None) is not None and getattr(cls, "_diffusion_def", None) is not None:
+        raise ModelDefinitionError("%s defines channel_noise(self, y, p, c) together with diffusion(self, y, p, c): a model has one "
+                                   "noise term -- a Wiener process per species is one channel per species, so write the diagonal "
+                                   "part as channels of its own (or set the inherited hook to None)" % name)
+    if chans and getattr(cls, "_channel_noise_def", None) is None:
+        raise ModelDefinitionError("%s declares noise_channels without channel_noise(self, y, p, c): the channels are the lists "
+                                   "that hook returns, one per name" % name)
+    if getattr(cls, "_channel_noise_def", None) is not None:
+        if not chans:
+            raise ModelDefinitionError("%s defines channel_noise(self, y, p, c) without noise_channels: the class names its "
+                                       "channels, noise_channels = [\"tx\", \"deg\", ...], and the hook returns one list per name"
+                                       % name)
+        if not isinstance(chans, (list, tuple)) or not all(isinstance(k, str) and k.isidentifier() for k in chans):
+            raise ModelDefinitionError("%s.noise_channels must be a list of names (valid identifiers)" % name)
+        if len(set(chans)) != len(chans):
+            raise ModelDefinitionError("%s.noise_channels has duplicates" % name)
+        if len(chans) > MAX_NOISE_CHANNELS:
+            raise ModelDefinitionError("%s: %d noise channels; a generated model draws for at most %d (MAX_NOISE_CHANNELS: two "
+                                       "Philox blocks of four normals per step)" % (name, len(chans), MAX_NOISE_CHANNELS))
+        clash = [k for k in chans if k in cls.species or k in cls.parameter_names or k in forc or k in alg or k in (dl or ())]
+        if clash:
+            raise ModelDefinitionError("%s.noise_channels: %s %s also a species, a parameter, a forcing, an algebraic variable or "
+                                       "a delay; a noise channel needs a name of its own"
+                                       % (name, ", ".join("'%s'" % k for k in clash), "is" if len(clash) == 1 else "are"))
+    noise = _noise_hook(cls)
+    if noise is not None:
         # process noise: what does not combine with it in this version, each with its reason
         for has, what, why in (
                 (cls.implicit is True, "implicit = True", "a drift-implicit step of an SDE is a scheme of its own, and the implicit "
@@ -3101,8 +3341,8 @@ def _validate(cls):
                 (cls.lead_in != 0, "lead_in = %r" % (cls.lead_in,), "the steps before the first observation point have no step "
                                                                     "index in the noise stream (noise in the lead-in is open)")):
             if has:
-                raise ModelDefinitionError("%s defines diffusion(self, y, p, c) and has %s: %s -- declined in this version"
-                                           % (name, what, why))
+                raise ModelDefinitionError("%s defines %s and has %s: %s -- declined in this version"
+                                           % (name, noise.signature, what, why))
         seed = cls.noise_seed
         if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < (1 << 48):
             raise ModelDefinitionError("%s.noise_seed = %r; the seed of the noise key is an int, 0 .. 2^48 - 1 (two words of 24 bits)"
@@ -3187,7 +3427,7 @@ def _validate(cls):
                                        % (name, m, ", ".join(str(c) for c in STEP_CONTROL_CEILINGS)))
         for has, what, why in (
                 (bool(nets), "networks", "the adjoint's dump of a network holds one evaluation per stage and observation interval"),
-                (getattr(cls, "_diffusion_def", None) is not None, "diffusion(self, y, p, c)",
+                (_noise_hook(cls) is not None, getattr(_noise_hook(cls), "signature", ""),
                  "the draws are counted by the steps of a fixed count, and the difference of two noisy trial solutions measures "
                  "the noise, not the truncation error")):
             if has:
