@@ -56,6 +56,10 @@ static_assert(!(has_diffusion<VIHDS_GEN_CORE>::value &&
 static_assert(noise_channels<VIHDS_GEN_CORE>::value >= 0 && noise_channels<VIHDS_GEN_CORE>::value <= 8 &&
                   (noise_channels<VIHDS_GEN_CORE>::value == 0 || has_diffusion<VIHDS_GEN_CORE>::value),
               "noise channels: at most 8 (two Philox blocks per step), and such a struct declares HAS_DIFFUSION (vihds_sde.hpp)");
+static_assert(!(VIHDS_GEN_NEURAL != 0 && has_steady<VIHDS_GEN_CORE>::value > 0),
+              "a model with steady species does not take NeuralPrecisions: WithPrec<> does not forward steady / steady_vjp");
+static_assert(has_steady<VIHDS_GEN_CORE>::value >= 0 && has_steady<VIHDS_GEN_CORE>::value <= kMaxSteady,
+              "steady_species: at most 8 (vihds_steady.hpp)");
 using GenM = GenSel<VIHDS_GEN_NEURAL != 0>::type;
 typedef int (*gen_launch_fn)(bool, int, const OdeArgs&, hipStream_t, const LaunchMode&);
 }  // namespace vihds
@@ -107,7 +111,8 @@ extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void) {
                                    n_forcings<GenM>::value, implicit_order<GenM>::value, substeps<GenM>::value,
                                    has_jump<GenM>::value ? 1 : 0, has_start<GenM>::value ? 1 : 0, lead_in<GenM>::value,
                                    n_delays<GenM>::value, has_diffusion<GenM>::value ? 1 : 0,
-                                   masked_obs<GenM>::value ? 1 : 0, step_control<GenM>::value ? 1 : 0};
+                                   masked_obs<GenM>::value ? 1 : 0, step_control<GenM>::value ? 1 : 0,
+                                   has_steady<GenM>::value};
   return &r;
 }
 #endif

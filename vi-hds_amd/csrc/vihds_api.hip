@@ -135,6 +135,8 @@ struct ModelEntry {
   // a registered model with step control (GenModelRecord::step_control): one more row of n_states behind the species and the
   // precision rows holds each interval's step count; it takes euler, midpoint, rk4 and the implicit solver only
   bool step_control = false;
+  // a registered model with steady species (GenModelRecord::steady, their number; 0: none): it takes no adaptive solver
+  int steady = 0;
   bool has_weights() const { return neural_prec || n_net_weights > 0; }
   bool prec_rows() const { return neural_prec || own_prec; }  // four rows of n_states behind the species are precisions
   int n_species() const { return n_states - (prec_rows() ? 4 : 0) - (step_control ? 1 : 0); }
@@ -192,7 +194,7 @@ static ModelEntry gen_entry_of(const GenModelRecord* r) {
   return {r->launch, r->n_slots, r->n_states, r->n_cond, nullptr, r->slot_names, r->neural_prec != 0, 0, r->n_net_weights,
           r->net_fields, r->own_prec != 0, r->n_weights, r->n_forcings, r->implicit != 0, r->substeps, r->jump != 0,
           r->start != 0, r->lead_in_steps, r->n_delays, r->diffusion != 0, r->masked_obs != 0,
-          r->step_control != 0};
+          r->step_control != 0, r->steady};
 }
 static bool is_registered(int model) {
   return model >= VIHDS_GEN_MODEL_BASE && model < VIHDS_GEN_MODEL_BASE + g_gen_count.load(std::memory_order_acquire);
@@ -290,6 +292,9 @@ static int build_args(const vihds_ode_problem* p, const ModelEntry* e, OdeArgs& 
   if (e->start && solver_is_adaptive(p->solver))
     return fail(VIHDS_E_UNSUPPORTED, "the model has a start map (start), which the kernels of the fixed-grid schemes call before "
                                      "the first step: an adaptive solver is not available to it");
+  if (e->steady > 0 && solver_is_adaptive(p->solver))
+    return fail(VIHDS_E_UNSUPPORTED, "the model has steady species (steady_species), solved for by the kernels of the fixed-grid "
+                                     "schemes before the first step: an adaptive solver is not available to it");
   if (e->lead_in_steps > 0 && solver_is_adaptive(p->solver))
     return fail(VIHDS_E_UNSUPPORTED, "the model has a lead-in phase (lead_in), steps of a fixed-grid scheme before the first "
                                      "observation point: an adaptive solver chooses its own steps and is not available to it");
@@ -428,7 +433,8 @@ int vihds_model_register(const char* library_path) {
       (r->diffusion && (r->neural_prec || r->n_net_weights > 0 || r->implicit || r->lead_in_steps || r->n_delays > 0)) ||
       (r->step_control != 0 && r->step_control != 1) ||
       (r->step_control && ((r->substeps != 2 && r->substeps != 4 && r->substeps != 8) || r->n_delays > 0 || r->diffusion ||
-                           r->n_states < (r->own_prec ? 6 : 2)))) {
+                           r->n_states < (r->own_prec ? 6 : 2))) ||
+      r->steady < 0 || r->steady > kMaxSteady || (r->steady && r->neural_prec)) {
     dlclose(h);
     return fail(VIHDS_E_BADARG, "vihds_model_register: the model's record is out of range (slots, states, observation kind)");
   }

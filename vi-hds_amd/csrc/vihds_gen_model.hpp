@@ -9,6 +9,7 @@
 
 #include "vihds_algebraic.hpp"  // a generated struct with algebraic variables calls its templates from rhs and observe
 #include "vihds_delay.hpp"      // the lookups of a generated struct with delayed reads (the time loops call them)
+#include "vihds_steady.hpp"     // the iteration and the adjoint solve of a generated struct with steady species
 #include "vihds_args.hpp"
 
 // registered models take ids from here on (far above the built-in enum vihds_model)
@@ -80,6 +81,9 @@ struct GenModelRecord {
   // trajectory picks its step count per observation interval up to `substeps`, the last row of n_states holds the counts (the
   // forward writes it, the adjoint reads it from traj_in); euler, midpoint, rk4 and the implicit solver only
   int step_control;
+  // species the generated struct solves for before the first step (steady / steady_vjp, vihds_models.hpp has_steady<>;
+  // vihds_steady.hpp): 0 for none, else 1 .. kMaxSteady; above 0 the fixed-grid solvers only, as for start
+  int steady;
 };
 }  // namespace vihds
 extern "C" const vihds::GenModelRecord* vihds_generated_model_v1(void);  // the one symbol a generated library exports

@@ -1073,6 +1073,23 @@ struct lead_in<M, std::void_t<decltype(M::LEAD_STEPS), decltype(M::LEAD_TIME)>> 
   static constexpr int value = M::LEAD_STEPS;
 };
 
+// A core generated with `steady_species` (vihds/modelgen.py: pre-equilibration) declares N_STEADY = M (1 .. kMaxSteady of
+// vihds_steady.hpp), STEADY_STEPS, STEADY_DELTA0, STEADY_GROWTH, STEADY_NZ, steady_species(e), steady_rate, steady_jac,
+// steady_rate_vjp and the two members the time loops call once per trajectory, after start and before the lead-in phase:
+//   steady(y, p)                         y_E <- the steady state by STEADY_STEPS pseudo-transient iterations from y (in place)
+//   steady_vjp(y, p, lam, pb)            y the state steady returned: J^T mu = lam_E; lam, pb += the product of steady_rate seeded
+//                                        with -mu (the other species and p); lam_E = 0
+// p holds the first forcing samples (set_point(p, u_0)).  The adjoint kernel recomputes init, start and steady by the forward's
+// calls.  value is M, 0 for every other model.  Such a model takes the fixed-grid solvers only.
+template <class M, class = void>
+struct has_steady {
+  static constexpr int value = 0;
+};
+template <class M>
+struct has_steady<M, std::void_t<decltype(M::N_STEADY)>> {
+  static constexpr int value = M::N_STEADY;
+};
+
 // A core generated with process noise (vihds/modelgen.py: diffusion(self, y, p, c)) declares HAS_DIFFUSION = true, NOISE_MASK
 // (bit j: species j has an amplitude that is not the constant 0) and two members that run once per step of the scheme:
 //   diffusion(y, p, g)                   g[j] = the noise amplitude of species j at the step's start state (noisy species only)

@@ -766,9 +766,10 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
     ff.word = LDS_IN ? in_lds[ff.mlds] : ff.msrc[0];
     ff.word_ahead = ff.word;
   }
-  if constexpr (has_start<M>::value || lead_in<M>::value > 0) {
+  if constexpr (has_start<M>::value || lead_in<M>::value > 0 || has_steady<M>::value > 0) {
     // where the trajectory starts, for a generated model that says so (a branch of its own: every other model's code stays what
-    // it was).  start maps what init returned, with the first forcing samples in p (set_point); the lead-in phase then takes
+    // it was).  start maps what init returned, with the first forcing samples in p (set_point); steady then takes the steady
+    // species from that guess to a steady state of the pre-culture system (vihds_steady.hpp); the lead-in phase then takes
     // the scheme from t_0 - L to t_0 with those samples held (slope 0) and rhs seeing the true t < t_0.  Nothing of it is
     // stored, observed or scored: the time loop below begins at y_0
     if constexpr (NF > 0) M::set_point(p, ff.lo);
@@ -777,6 +778,7 @@ __global__ void __launch_bounds__(256) ode_fwd_kernel(OdeArgs a) {
       M::start(y, p, ys);
       VIHDS_UNROLL for (int j = 0; j < N; ++j) y[j] = ys[j];
     }
+    if constexpr (has_steady<M>::value > 0) M::steady(y, p);
     if constexpr (lead_in<M>::value > 0) {
       if constexpr (NF > 0) M::set_interval(p, tA - M::LEAD_TIME, 0.f, ff.lo, ff.lo);
       ode_lead_in<M, SOLVER>(tA, y, p, wts);
@@ -1444,25 +1446,30 @@ __global__ void __launch_bounds__(256) ode_bwd_kernel(OdeArgs a) {
       VIHDS_UNROLL for (int e = 0; e < ND; ++e) lam[M::delay_species(e)] += a.aux[((size_t)e * a.T + k) * n + i];
     }
   }
-  if constexpr (has_start<M>::value || lead_in<M>::value > 0) {
+  if constexpr (has_start<M>::value || lead_in<M>::value > 0 || has_steady<M>::value > 0) {
     // where the trajectory started (a branch of its own: every other model's code stays what it was).  lam is the adjoint of
-    // y_0 and tHi is t_0; ff.lo holds the first forcing samples.  init and start are recomputed by the forward's calls on the
-    // forward's operands; the lead-in's step adjoints run last to first (an implicit scheme's last one at the stored y_0,
-    // which ff.y_next holds), then start_vjp takes lam to the adjoint of what init returned and adds its parameter part to pb
-    // ahead of prepare_vjp; init_vjp below is handed that state adjoint
+    // y_0 and tHi is t_0; ff.lo holds the first forcing samples.  init, start and steady are recomputed by the forward's calls
+    // on the forward's operands; the lead-in's step adjoints run last to first from the state steady returned (an implicit
+    // scheme's last one at the stored y_0, which ff.y_next holds), then steady_vjp applies the implicit-function step at that
+    // state and clears the steady species' adjoint, then start_vjp takes lam to the adjoint of what init returned and adds its
+    // parameter part to pb ahead of prepare_vjp; init_vjp below is handed that state adjoint
     float yi[N];
     M::init(th, c, yi);
     if constexpr (NF > 0) M::set_point(p, ff.lo);
-    if constexpr (lead_in<M>::value > 0) {
+    if constexpr (lead_in<M>::value > 0 || has_steady<M>::value > 0) {
       float ys[N];
       if constexpr (has_start<M>::value) {
         M::start(yi, p, ys);
       } else {
         VIHDS_UNROLL for (int j = 0; j < N; ++j) ys[j] = yi[j];
       }
-      if constexpr (NF > 0) M::set_interval(p, tHi - M::LEAD_TIME, 0.f, ff.lo, ff.lo);  // (the value entries stay u_0)
-      if constexpr (solver_is_implicit(SOLVER)) ode_lead_in_vjp<M, SOLVER>(tHi, ys, ff.y_next, p, wts, lam, pb, wtsb);
-      else ode_lead_in_vjp<M, SOLVER>(tHi, ys, nullptr, p, wts, lam, pb, wtsb);
+      if constexpr (has_steady<M>::value > 0) M::steady(ys, p);
+      if constexpr (lead_in<M>::value > 0) {
+        if constexpr (NF > 0) M::set_interval(p, tHi - M::LEAD_TIME, 0.f, ff.lo, ff.lo);  // (the value entries stay u_0)
+        if constexpr (solver_is_implicit(SOLVER)) ode_lead_in_vjp<M, SOLVER>(tHi, ys, ff.y_next, p, wts, lam, pb, wtsb);
+        else ode_lead_in_vjp<M, SOLVER>(tHi, ys, nullptr, p, wts, lam, pb, wtsb);
+      }
+      if constexpr (has_steady<M>::value > 0) M::steady_vjp(ys, p, lam, pb);
     }
     if constexpr (has_start<M>::value) {
       float lami[N];
@@ -1611,7 +1618,7 @@ template <class M, int ONLY = kOnlySolver>
 inline int launch_ode(bool backward, int solver, const OdeArgs& a, hipStream_t st, const LaunchMode& mode) {
   if (solver_is_implicit(solver)) return launch_ode_implicit<M, ONLY>(backward, solver, a, st, mode);
   if constexpr (n_forcings<M>::value > 0 || substeps<M>::value > 1 || has_jump<M>::value || has_start<M>::value ||
-                lead_in<M>::value > 0 || n_delays<M>::value > 0 || has_diffusion<M>::value || masked_obs<M>::value ||
+                lead_in<M>::value > 0 || has_steady<M>::value > 0 || n_delays<M>::value > 0 || has_diffusion<M>::value || masked_obs<M>::value ||
                 step_control<M>::value) {
     // a model with forcings: its samples live on the observation grid, so only the fixed-grid schemes integrate it -- the
     // adaptive pairs (either controller) and the one-pass summaries are declined here, and none of their kernels

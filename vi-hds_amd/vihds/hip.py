@@ -53,6 +53,9 @@ GENERATED_JUMP = set()
 # fixed-grid schemes call start and run the steps before t_0)
 GENERATED_START = set()
 GENERATED_LEAD_IN = {}
+# registered generated models with steady species (`steady_species`, `steady_rate`): key -> the number of species their kernels
+# solve for before the first step; they decline the adaptive solvers as a start map does
+GENERATED_STEADY = {}
 # registered generated models with algebraic variables (`algebraic`, `constraint`): key -> the number of unknowns their struct
 # solves for inside rhs and observe (nothing else differs: every explicit solver takes them)
 GENERATED_ALGEBRAIC = {}

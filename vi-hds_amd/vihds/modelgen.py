@@ -264,6 +264,47 @@ last to first, then start_vjp ahead of prepare_vjp, and hands the state part to 
 NeuralPrecisions; a lead-in takes no networks (the dump is sized (T-1) x stages), start combines with networks in rhs.  A class
 with neither generates byte for byte the text it generated before.  torch_start restates the hook with torch ops.
 
+Pre-equilibration.  Cells are pre-cultured until the circuit has relaxed, and only then induced and read: the right initial state
+is a steady state of the model itself under the pre-culture conditions, a function of the parameters being inferred.  start
+covers it where the steady state has a closed form; a toggle switch, a repressilator, a cascade with Hill repression have none:
+
+        steady_species = ["U", "V"]                  # 1 .. MAX_STEADY = 8 names out of `species`
+        steady_steps = 12                            # an int, 1 .. MAX_STEADY_STEPS = 16: a fixed count
+        steady_first_step = 0.1                      # the pseudo-time step delta_0 > 0, in the units of `times`
+        steady_growth = 4.0                          # delta_k+1 = delta_k * steady_growth, at least 1
+        def steady_rate(self, y, p, c):              # -> one residual per steady species: their d/dt in the pre-culture
+            f = self.rhs(0.0, y, p, [0.0] * len(c))  # e.g. the model's own rhs with the inducers absent
+            return [f[1], f[2]]
+
+steady_rate has the rules of start (no t, no network call, self.forcing.<name> is the first sample u_0, a treatment it reads
+becomes one more effective parameter, a parameter may be read by it alone); y is the full state, and the species not named are
+inputs held fixed (the cell density grows and is at no steady state).  A self.rhs(...) it calls is traced as part of it: where
+that rhs calls a network or reads self.algebraic / self.delayed the read raises and names steady_rate.  The value, exactly: from
+y_s = start(initial_state(...)) (initial_state(...) without a start), with E the steady species, F = steady_rate, J = dF/dy_E
+(generated from the DAG like rhs_jac, its structural pattern STEADY_NZ known at compile time) and delta_0 = steady_first_step,
+for k = 0 .. steady_steps - 1: solve (I - delta_k J(y)) d = delta_k F(y), y_E += d, delta_k+1 = delta_k * steady_growth in
+float32.  Each iteration is one Newton iteration of a backward-Euler step in pseudo-time (pseudo-transient continuation): the
+early ones follow the flow from the guess, so a bistable model lands in the basin its guess is in; the late ones are Newton's
+method up to 1 / delta_k.  No convergence test, no data-dependent branch.  The order is initial_state, start, the solve, the
+lead-in, the scored time loop; nothing of the solve is stored or scored, traj[0] is what follows it (or the lead-in), and a
+delayed read's history before t_0 is that stored y_0.  The adjoint is the implicit-function theorem's at the final state y*: with
+lam the adjoint of y*, solve J(y*)^T mu = lam_E (J itself, not I - delta J), add steady_rate's vector-Jacobian product seeded
+with -mu into the adjoint of the other species and of p, set lam_E = 0.  Nothing is differentiated through the iteration, so
+the guess of a steady species receives exactly 0 gradient: an init_* parameter that only feeds such a guess is learned from its
+prior alone (INTEGRATION.md lists this trap).  Too few steps leave a y* that is no root, and the adjoint is then not the gradient
+of what was computed: choose the count on torch_steady(y, theta, cond, forcing=None, return_residual=True), which runs the same
+iteration in y's dtype, carries the implicit-function gradient through a custom autograd function and also returns the last
+increment relative to |y_E| and |F(y*)|.  torch_problem's x0 includes the solve; torch_steady_jacobian evaluates the generated J
+from the same DAG nodes.  The solves eliminate without a pivot search (csrc/vihds_steady.hpp): residual i must depend on steady
+species i; a zero column or row of J and a structurally zero pivot after fill-in are refused when the class is defined.  The
+struct gains N_STEADY, STEADY_STEPS, STEADY_DELTA0, STEADY_GROWTH, STEADY_NZ, steady_species(e), steady_rate, steady_jac,
+steady_rate_vjp, steady and steady_vjp.  It combines with start, lead_in, forcings, an own observe / precision / log_likelihood,
+piecewise terms, substeps, step_tolerance, jump, missing_observations, implicit (both orders), delays, diffusion / noise_channels
+and networks in rhs.  Refused in this version: together with `algebraic`, with NeuralPrecisions, more than MAX_STEADY names.
+Fixed-grid solvers only, as for start (an adaptive solver is declined: solve and ops.OdeProblemSpec raise before anything is
+queued, the library answers VIHDS_E_UNSUPPORTED).  `steady_species = None` (or []) in a subclass removes it; a class without it
+generates byte for byte the text it generated before.
+
 Algebraic variables.  A fast reaction held at its equilibrium -- binding and unbinding of a repressor, an inducer, a dimer, orders
 of magnitude faster than expression and dilution -- is the reduction modellers reach for before a stiff solver: the TOTALS stay
 ODE states and the complex is defined by a constraint g(y, z, p) = 0 (quasi-steady state, rapid equilibrium).  A class declares
@@ -518,6 +559,11 @@ MAX_ALGEBRAIC = 4
 # with rk4 (tests/test_modelgen_channel_host.py builds that worst case; DESIGN.md 4.7 has the compiler's figures)
 MAX_NOISE_CHANNELS = 8
 MAX_NOISE_ENTRIES = 32
+# species a model with `steady_species` solves for before the first step: the matrix of an iteration lives in registers beside
+# the states, its structural pattern is one 64-bit constant (csrc/vihds_steady.hpp; tests/test_modelgen_steady_host.py compiles
+# eight without scratch); and the iterations it may ask for (`steady_steps`, a fixed count)
+MAX_STEADY = 8
+MAX_STEADY_STEPS = 16
 
 
 class ModelDefinitionError(TypeError):
@@ -1291,6 +1337,10 @@ class _Algebraic(object):
         return iter(self._names)
 
 
+def _class_steady(cls):
+    return list(getattr(cls, "steady_species", None) or ())
+
+
 _ALGEBRAIC_READERS = ("rhs", "observe")  # the functions that may read self.algebraic.<name>
 
 
@@ -1516,7 +1566,7 @@ class Trace(object):
         def call(k, name, net, inputs):
             if self._phase != "rhs":
                 raise ModelDefinitionError("network '%s' called from %s: networks are evaluated in rhs only (not in "
-                                           "prepare, initial_state, observe or precision, nor in log_likelihood, jump or start)" % (name, self._phase))
+                                           "prepare, initial_state, observe or precision, nor in log_likelihood, jump, start or steady_rate)" % (name, self._phase))
             if name in self._called:
                 raise ModelDefinitionError("network '%s' is called twice: a network may be called at most once per rhs "
                                            "evaluation (its adjoint dump has one slot per evaluation)" % name)
@@ -1607,8 +1657,23 @@ class Trace(object):
                     raise ModelDefinitionError("%s.%s must return a list of %d entries (%s)"
                                                % (cls.__name__, h.name, h.count(N), h.outputs))
                 setattr(self, h.traced, [g._arg(x) for x in out])
+        # the steady species: steady_rate, traced last (a class without them traces nothing here and keeps the numbering of its
+        # nodes).  It sees what start sees -- no t, no network call, a forcing's first sample; a self.rhs(...) it calls is traced
+        # in its phase, so whatever that rhs does that steady_rate may not do raises here and names steady_rate
+        self.steady, self.srate = _class_steady(cls), None
+        if self.steady:
+            self._phase = "steady_rate"
+            out = inst.steady_rate([g.leaf("y", j) for j in range(N)], p, _Conditions([g.leaf("p", NPU + q) for q in range(C)]))
+            if not isinstance(out, (list, tuple)) or len(out) != len(self.steady):
+                raise ModelDefinitionError("%s.steady_rate must return a list of %d entries (one residual per steady species: %s)"
+                                           % (cls.__name__, len(self.steady), ", ".join(self.steady)))
+            self.srate = [g._arg(x) for x in out]
+            bad = sorted({n.op for n in _topo(self.srate) if n.op in ("t", "net", "z", "d", "dt")})
+            if bad:
+                raise ModelDefinitionError("%s.steady_rate reads %s: it sees the species, the effective parameters, the treatments "
+                                           "and the forcings' first samples only" % (cls.__name__, ", ".join(bad)))
         used = {n.val for n in _topo(self.dy + [x for h in MODEL_HOOKS for x in getattr(self, h.traced) or []]
-                                     + (self.z0 or []) + (self.con or [])) if n.op == "p"}
+                                     + (self.z0 or []) + (self.con or []) + (self.srate or [])) if n.op == "p"}
         self.c_in_rhs = [q for q in range(C) if NPU + q in used]  # (read by rhs, by observe, by precision or by log_likelihood)
         # remap the treatments rhs / observe / precision read to consecutive parameter indices behind the named ones
         self.NP = NPU + len(self.c_in_rhs)
@@ -1824,6 +1889,50 @@ def _check_constraint_pattern(cls):
                     pat[i][j] = pat[i][j] or pat[k][j]
 
 
+def steady_jacobian_nodes(cls):
+    """J = d steady_rate / d y_E of the class as DAG nodes, row by row: J[i][j] = d F_i / d y[steady species j], by reverse mode
+    with constant one-hot seeds (as jacobian_nodes does for rhs).  A structural zero is the constant 0."""
+    tr = cls._trace
+    g, M = tr.g, len(tr.steady)
+    idx = [list(cls.species).index(s) for s in tr.steady]
+    rows = []
+    for i in range(M):
+        adj = vjp(g, tr.srate, [1.0 if k == i else 0.0 for k in range(M)])
+        rows.append([adj.get(g.leaf("y", j).id, g.const(0.0)) for j in idx])
+    return rows
+
+
+def steady_pattern(cls):
+    """[M][M] bools: the entries of d steady_rate / d y_E that are not structurally zero."""
+    return [[not _is_const(e, 0.0) for e in row] for row in steady_jacobian_nodes(cls)]
+
+
+def _check_steady_pattern(cls):
+    """A structurally singular J is refused when the class is defined, as _check_constraint_pattern does for dg/dz: a steady
+    species no residual depends on, a residual that depends on no steady species, and -- the adjoint's elimination has no pivot
+    search -- a pivot that is a structural zero after fill-in."""
+    names, pat = _class_steady(cls), [list(r) for r in steady_pattern(cls)]
+    M = len(names)
+    for j in range(M):
+        if not any(pat[i][j] for i in range(M)):
+            raise ModelDefinitionError("%s.steady_rate: no residual depends on the steady species '%s' -- d steady_rate / d y_E "
+                                       "has a zero column and is structurally singular" % (cls.__name__, names[j]))
+    for i in range(M):
+        if not any(pat[i]):
+            raise ModelDefinitionError("%s.steady_rate: residual %d depends on no steady species -- d steady_rate / d y_E has a "
+                                       "zero row and is structurally singular" % (cls.__name__, i))
+    for k in range(M):
+        if not pat[k][k]:
+            raise ModelDefinitionError(
+                "%s.steady_rate: residual %d does not depend on the steady species '%s' (not even after the elimination's "
+                "fill-in) -- the solve eliminates without a pivot search, so pivot %d would be a structural zero: order the "
+                "residuals so that residual i depends on steady species i" % (cls.__name__, k, names[k], k))
+        for i in range(k + 1, M):
+            if pat[i][k]:
+                for j in range(k + 1, M):
+                    pat[i][j] = pat[i][j] or pat[k][j]
+
+
 def _leaf_free(node, allowed):
     return all(n.op not in _LEAVES or n.op == "const" or n.op in allowed for n in _topo([node]))
 
@@ -1862,6 +1971,10 @@ def generate_source(cls, neural=False):
         raise ModelDefinitionError("%s declares delays: WithPrec<> forwards neither the reserved slots nor set_delay, so a model "
                                    "with delayed reads does not take NeuralPrecisions (constant precisions, or a precision map "
                                    "of its own)" % cls.__name__)
+    if neural and tr.steady:
+        raise ModelDefinitionError("%s declares steady_species: WithPrec<> does not forward steady / steady_vjp, so a model with "
+                                   "steady species does not take NeuralPrecisions (constant precisions, or a precision map of "
+                                   "its own)" % cls.__name__)
     g = tr.g
     N, P, C = len(cls.species), list(cls.parameter_names), int(cls.n_conditions)
     NPU = len(tr.p_names)
@@ -2098,6 +2211,57 @@ def generate_source(cls, neural=False):
             vjp_open = rhs_open + ["    float zb[%d];" % M]
             vjp_pull = pull_z(adj1)
             vjp_close = ["    algebraic_vjp(y, z, p, u, zb, yb, pb);"]
+    # steady species: the constants, the three traced members and the two the time loops call once per trajectory
+    # (csrc/vihds_steady.hpp); a forcing is its first sample, as in start.  None without them
+    steady_decl = []
+    MS = len(tr.steady)
+    if MS:
+        sidx = [list(cls.species).index(sp) for sp in tr.steady]
+        SJ = steady_jacobian_nodes(cls)
+        snz = [(i, j) for i in range(MS) for j in range(MS) if not _is_const(SJ[i][j], 0.0)]
+        sadj = vjp(g, tr.srate, [g.leaf("seed", i) for i in range(MS)])
+        others = [j for j in range(N) if j not in sidx]
+        svjp = [("yb[%d]" % j, "+=", sadj[g.leaf("y", j).id]) for j in others if g.leaf("y", j).id in sadj]
+        svjp += [("pb[%d]" % k, "+=", sadj[g.leaf("p", k).id]) for k in range(NPU) if g.leaf("p", k).id in sadj]
+        put = " ".join("u[%d] = s[%d];" % (j, e) for e, j in enumerate(sidx))
+        steady_decl = [
+            "  static constexpr int N_STEADY = %d;  // %s: solved for before the first step (vihds_steady.hpp); the other species are held" % (
+                MS, ", ".join(tr.steady)),
+            "  static constexpr int STEADY_STEPS = %d;  // pseudo-transient iterations from the guess, a fixed count" % int(cls.steady_steps),
+            "  static constexpr float STEADY_DELTA0 = %s;  // the first pseudo-time step" % _lit(cls.steady_first_step),
+            "  static constexpr float STEADY_GROWTH = %s;  // delta_k+1 = delta_k * STEADY_GROWTH" % _lit(cls.steady_growth),
+            "  static constexpr unsigned long long STEADY_NZ = 0x%xull;  // structural non-zeros of steady_jac, bit i * N_STEADY + j: %d of %d" % (
+                sum(1 << (i * MS + j) for i, j in snz), len(snz), MS * MS),
+            "  __host__ __device__ static constexpr int steady_species(int e) { return %s; }" % " : ".join(
+                ["e == %d ? %d" % (e, j) for e, j in enumerate(sidx[:-1])] + ["%d" % sidx[-1]]),
+            "  __device__ static void steady_rate(const float* y, const float* p, float* F) {",
+            body([("F[%d]" % i, "=", e) for i, e in enumerate(tr.srate)], True, "v", tr.c_slot, f_at_point),
+            "  }",
+            "  // A[i * N_STEADY + j] = d F[i] / d y[steady_species(j)]; a structural zero is not written (and not read by the solves)",
+            "  __device__ static void steady_jac(const float* y, const float* p, float* A) {",
+            body([("A[%d]" % (i * MS + j), "=", SJ[i][j]) for i, j in snz], True, "v", tr.c_slot, f_at_point),
+            "  }",
+            "  // yb (the species that are not steady), pb += v^T dF/dy, v^T dF/dp (the adjoint passes v = -mu)",
+            "  __device__ static void steady_rate_vjp(const float* y, const float* p, const float* v, float* yb, float* pb) {",
+            body(svjp, True, "v", tr.c_slot, f_at_point),
+            "  }",
+            "  __device__ static void steady(float* y, const float* p) {",
+            "    float u[%d], z[%d] = {%s};" % (N, MS, ", ".join("y[%d]" % j for j in sidx)),
+        ] + ["    u[%d] = y[%d];" % (j, j) for j in others] + [
+            "    steady_iterate<N_STEADY, STEADY_STEPS, STEADY_NZ>(",
+            "        STEADY_DELTA0, STEADY_GROWTH, z,",
+            "        [&](const float* s, float* F) { %s steady_rate(u, p, F); }," % put,
+            "        [&](const float* s, float* A) { %s steady_jac(u, p, A); });" % put,
+        ] + ["    y[%d] = z[%d];" % (j, e) for e, j in enumerate(sidx)] + [
+            "  }",
+            "  // y: the state steady returned; lam: its adjoint.  J^T mu = lam_E, then steady_rate's product with -mu; lam_E = 0",
+            "  __device__ static void steady_vjp(const float* y, const float* p, float* lam, float* pb) {",
+            "    float mu[%d] = {%s};" % (MS, ", ".join("lam[%d]" % j for j in sidx)),
+            "    steady_adjoint<N_STEADY, STEADY_NZ>(mu, [&](float* A) { steady_jac(y, p, A); });",
+        ] + ["    lam[%d] = 0.f;" % j for j in sidx] + [
+            "    steady_rate_vjp(y, p, mu, lam, pb);",
+            "  }",
+        ]
     # substeps = m > 1: the one line the kernels' time loops read (vihds_models.hpp substeps<>); a class without it generates
     # the text it generated before
     substeps_decl = ["  static constexpr int SUBSTEPS = %d;" % int(cls.substeps)] if cls.substeps > 1 else []
@@ -2156,7 +2320,7 @@ def generate_source(cls, neural=False):
         body(rhs_vjp + vjp_pull, True, "v", tr.c_slot, f_at_t),
     ] + vjp_close + [
         "  }",
-    ] + jac_decl + hook_decl + [
+    ] + jac_decl + hook_decl + steady_decl + [
         "};",
         "}  // namespace vihds",
         "#define VIHDS_GEN_CORE %s" % sname,
@@ -2291,6 +2455,8 @@ def register_kernel(cls, neural=False):
         hip.GENERATED_JUMP.add(key)
     if cls._trace.start is not None:  # (a start map: the fixed-grid schemes only, likewise)
         hip.GENERATED_START.add(key)
+    if cls._trace.steady:  # (steady species, solved for before the first step: the fixed-grid schemes only, likewise)
+        hip.GENERATED_STEADY[key] = len(cls._trace.steady)
     if cls.lead_in > 0:  # (a lead-in phase: the fixed-grid schemes only, likewise)
         hip.GENERATED_LEAD_IN[key] = (float(cls.lead_in), int(cls.lead_in_steps))
     if cls._trace.dif is not None or cls._trace.chan is not None:  # (process noise: the fixed-grid schemes only; a row of cond ends with its noise key)
@@ -2388,6 +2554,11 @@ class GeneratedOdeModel(OdeModel):
     algebraic_iterations = 6  # Newton iterations on the constraint, 1 .. MAX_NEWTON_ITERATIONS (a fixed count, no test)
     constraint = None  # constraint(self, y, z, p, c) -> one residual per algebraic variable; z solves constraint(...) == 0
     algebraic_start = None  # algebraic_start(self, y, p, c) -> the iteration's starting value, one entry per algebraic variable
+    steady_species = ()  # names of the species solved for before the first step, 1 .. MAX_STEADY out of `species` (module docstring)
+    steady_steps = 12  # pseudo-transient iterations of that solve, 1 .. MAX_STEADY_STEPS (a fixed count, no test)
+    steady_first_step = 0.1  # delta_0 > 0: the first pseudo-time step, in the units of `times`
+    steady_growth = 4.0  # delta_k+1 = delta_k * steady_growth, at least 1
+    steady_rate = None  # steady_rate(self, y, p, c) -> one residual per steady species: their d/dt under pre-culture conditions
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -2426,6 +2597,8 @@ class GeneratedOdeModel(OdeModel):
         cls._trace = Trace(cls)
         if cls._trace.algebraic:
             _check_constraint_pattern(cls)
+        if cls._trace.steady:
+            _check_steady_pattern(cls)
         generate_source(cls)  # (the checks that need the adjoints: an initial state the kernels can differentiate)
 
     def __init__(self, config):
@@ -2565,7 +2738,8 @@ class GeneratedOdeModel(OdeModel):
                     ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         for has, what in ((type(self)._start_def is not None, "defines start(self, y, p, c), the state the integration starts from"),
                           (type(self).lead_in > 0, "has lead_in = %r, steps of a fixed-grid scheme before the first observation "
-                                                   "point" % (type(self).lead_in,))):
+                                                   "point" % (type(self).lead_in,)),
+                          (bool(_class_steady(type(self))), "declares steady_species, solved for before the first step")):
             if has and config.params.solver in hip.ADAPTIVE_SOLVERS:  # (likewise)
                 raise NotImplementedError(
                     "%s %s: only the kernels of the fixed-grid schemes run it, the adaptive solver '%s' is not available to it "
@@ -2636,6 +2810,12 @@ class GeneratedOdeModel(OdeModel):
     def has_start(self):
         """True for a model with a start map, start(self, y, p, c) (module docstring)."""
         return type(self)._start_def is not None
+
+    @property
+    def n_steady_species(self):
+        """The number of species a model with steady_species solves for before the first step (module docstring); 0 for any
+        other."""
+        return len(_class_steady(type(self)))
 
     @property
     def has_step_control(self):
@@ -2776,6 +2956,8 @@ class GeneratedOdeModel(OdeModel):
         x0 = torch.stack([full(v) for v in inst.initial_state(thn, _Conditions(cs))], dim=2)
         if start and cls._start_def is not None:  # (the state the integration starts from)
             x0 = cls.torch_start(x0, th, cond, **({"n_times": tg.shape[0]} if names else {}))
+        if start and _class_steady(cls):  # (... after the solve for its steady species, which carries the implicit-function gradient)
+            x0 = cls.torch_steady(x0, th, cond, forcing=[series[:, k, 0, None].expand(B, S) for k in range(len(names))] if names else None)
 
         def rhs(t, state, delayed=None):
             y = list(torch.unbind(state[:, :, :N], dim=2))
@@ -2887,6 +3069,129 @@ class GeneratedOdeModel(OdeModel):
         env.update({("z", i): z[:, :, i] for i in range(M)})
         env.update({("f", k): v for k, v in enumerate(forcing or ())})
         flat = evaluate([e for row in constraint_jacobian_nodes(cls) for e in row], env)
+        return torch.stack([v.to(ref.dtype).expand_as(ref) for v in flat], dim=2).reshape(ref.shape + (M, M))
+
+    @classmethod
+    def torch_steady(cls, y, theta, cond, forcing=None, return_residual=False, steps=None, first_step=None, growth=None):
+        """The solve for the steady species with torch ops in y's dtype, by the iteration the kernels run (module docstring): from
+        y [B,S,N] (what initial_state, then start returned), steady_steps times F = steady_rate(y, p), J = dF/dy_E by autograd,
+        (I - delta J) d = delta F by torch.linalg.solve (pivoted), y_E += d, delta *= steady_growth (delta in float32, as the
+        kernels form it).  theta {parameter name: [B,S]} -- prepare is applied to it first --, cond [B,C] as the data holds it,
+        forcing: the K first samples u_0 (tensors that broadcast to [B,S]) for a class with forcings -> the state [B,S,N].  The
+        value is the iterate's; a custom autograd function carries the implicit-function gradient of the converged solution at
+        it: J^T mu = the adjoint of y_E, then the product of steady_rate seeded with -mu into the other species and theta, and 0
+        into the guess of the steady species -- nothing is differentiated through the iteration.  return_residual: (state, the
+        largest last increment relative to the largest |y_E| of its trajectory, the largest |F(y*)|) -- what says whether the
+        count is enough.  steps / first_step / growth override the class's for such an experiment."""
+        names_e = _class_steady(cls)
+        if not names_e:
+            raise ModelDefinitionError("%s declares no steady_species" % cls.__name__)
+        inst = cls.__new__(cls)
+        N = len(cls.species)
+        idx = [list(cls.species).index(s) for s in names_e]
+        y = y[:, :, :N]
+        ref = y[:, :, 0]
+        cs = _treatments_torch(cls, cond, ref, ref.shape[1])
+        names = _class_forcings(cls)
+        if names:
+            if forcing is None or len(forcing) != len(names):
+                raise ValueError("%s.torch_steady needs forcing=[%s]: the first samples of the class's forcings"
+                                 % (cls.__name__, ", ".join(names)))
+            object.__setattr__(inst, "forcing", _Forcings(cls, lambda k, _name: forcing[k]))
+        object.__setattr__(inst, "algebraic", _Algebraic(cls, lambda _i, name: _algebraic_misread(name, "steady_rate")))
+        if _class_delays(cls):
+            object.__setattr__(inst, "delayed", _Delayed(cls, lambda _e, name: _delay_misread(name, "steady_rate")))
+        pnames = list(cls.parameter_names)
+        n_steps = int(cls.steady_steps if steps is None else steps)
+        delta0 = np.float32(cls.steady_first_step if first_step is None else first_step)
+        grow = np.float32(cls.steady_growth if growth is None else growth)
+
+        def residual(state, thetas):
+            thn = _Named([(n, v.to(ref.dtype)) for n, v in zip(pnames, thetas)], "parameter")
+            p = _Named(inst.prepare(thn, _Conditions(cs)).items(), "effective parameter")
+            out = inst.steady_rate(list(torch.unbind(state, dim=2)), p, _Conditions(cs))
+            return torch.stack([(v if isinstance(v, torch.Tensor) else torch.full_like(ref, float(v))).expand_as(ref)
+                                for v in out], dim=2)
+
+        def linearised(state, thetas):
+            """(J [B,S,M,M], F [B,S,M]) at the state, detached."""
+            with torch.enable_grad():
+                z = state[:, :, idx].detach().requires_grad_(True)
+                full = state.detach().clone()
+                cols = list(torch.unbind(full, dim=2))
+                for e, j in enumerate(idx):
+                    cols[j] = z[:, :, e]
+                F = residual(torch.stack(cols, dim=2), [v.detach() for v in thetas])
+                rows = []
+                for i in range(len(idx)):
+                    fi = F[:, :, i].sum()
+                    row = torch.autograd.grad(fi, z, retain_graph=True, allow_unused=True)[0] if fi.requires_grad else None
+                    rows.append(torch.zeros_like(z) if row is None else row)
+            return torch.stack(rows, dim=2).detach(), F.detach()
+
+        holder = {}
+
+        class _Steady(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, state, *thetas):
+                cur, delta = state.detach().clone(), delta0
+                eye = torch.eye(len(idx), dtype=state.dtype, device=state.device)
+                d = torch.zeros_like(cur[:, :, idx])
+                for _ in range(n_steps):
+                    J, F = linearised(cur, thetas)
+                    d = torch.linalg.solve(eye - float(delta) * J, (float(delta) * F).unsqueeze(-1)).squeeze(-1)
+                    cur[:, :, idx] = cur[:, :, idx] + d
+                    delta = np.float32(delta * grow)
+                ctx.save_for_backward(cur, *thetas)
+                holder["last"] = d
+                return cur
+
+            @staticmethod
+            def backward(ctx, lam):
+                cur, thetas = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+                J, _F = linearised(cur, thetas)
+                mu = torch.linalg.solve(J.transpose(-1, -2), lam[:, :, idx].unsqueeze(-1)).squeeze(-1)
+                with torch.enable_grad():
+                    st = cur.detach().requires_grad_(True)
+                    ths = [v.detach().requires_grad_(True) for v in thetas]
+                    F = residual(st, ths)
+                    grads = torch.autograd.grad(F, [st] + ths, grad_outputs=-mu, allow_unused=True) if F.requires_grad \
+                        else [None] * (1 + len(ths))
+                gy = lam.clone()
+                if grads[0] is not None:
+                    gy = gy + grads[0]
+                gy[:, :, idx] = 0.0
+                return (gy,) + tuple(None if v is None else v for v in grads[1:])
+
+        thetas = [theta[n].to(ref.dtype) for n in pnames]
+        out = _Steady.apply(y, *thetas)
+        if not return_residual:
+            return out
+        with torch.no_grad():
+            _J, F = linearised(out, thetas)
+            d = holder["last"]
+            scale = out[:, :, idx].abs().amax(-1).clamp_min(1e-30)
+            inc = float((d.abs().amax(-1) / scale).max()) if bool(torch.isfinite(d).all()) else float("inf")
+            res = float(F.abs().max()) if bool(torch.isfinite(F).all()) else float("inf")
+        return out, inc, res
+
+    @classmethod
+    def torch_steady_jacobian(cls, y, theta, cond, forcing=None):
+        """The generated J = d steady_rate / d y_E evaluated with torch ops in y's dtype -- the SAME DAG nodes steady_jac is
+        emitted from (steady_jacobian_nodes), not autograd: it exists to check the generator against autograd of the class's
+        steady_rate.  y [B,S,N], theta, cond and forcing as torch_steady takes them -> [B,S,M,M], entry [i][j] = d F_i / d
+        y[steady species j]."""
+        tr = cls._trace
+        N, M, NPU = len(cls.species), len(tr.steady), len(tr.p_names)
+        ref = y[:, :, 0]
+        cs = _treatments_torch(cls, cond, ref, ref.shape[1])
+        env = {("th", s): theta[n].to(ref.dtype) for s, n in enumerate(cls.parameter_names)}
+        env.update({("c", q): v for q, v in enumerate(cs)})
+        env.update({("p", k): v.to(ref.dtype) for k, v in enumerate(evaluate(tr.p_exprs, env))})
+        env.update({("p", NPU + q): v for q, v in enumerate(cs)})
+        env.update({("y", j): y[:, :, j] for j in range(N)})
+        env.update({("f", k): v for k, v in enumerate(forcing or ())})
+        flat = evaluate([e for row in steady_jacobian_nodes(cls) for e in row], env)
         return torch.stack([v.to(ref.dtype).expand_as(ref) for v in flat], dim=2).reshape(ref.shape + (M, M))
 
     @classmethod
@@ -3454,6 +3759,47 @@ def _validate(cls):
         raise ModelDefinitionError("%s has lead_in = %r and networks: the adjoint's dump of a network holds one evaluation per "
                                    "stage and observation interval, (T-1) x stages (a lead-in phase is for models without "
                                    "networks)" % (name, L))
+    st = getattr(cls, "steady_species", None) or ()
+    if not isinstance(st, (list, tuple)) or not all(isinstance(a, str) for a in st):
+        raise ModelDefinitionError("%s.steady_species must be a list of names out of `species`" % name)
+    if not st:
+        # (set in this class body; one that removes an inherited solve with steady_species = None keeps what it inherits)
+        own = [a for a in ("steady_steps", "steady_first_step", "steady_growth", "steady_rate") if cls.__dict__.get(a) is not None]
+        if own:
+            raise ModelDefinitionError("%s sets %s without steady_species: the attributes describe the solve for the species "
+                                       "steady_species names" % (name, ", ".join(own)))
+    else:
+        unknown = [a for a in st if a not in cls.species]
+        if unknown:
+            raise ModelDefinitionError("%s.steady_species: %s %s no species of the model (species: %s)" % (
+                name, ", ".join("'%s'" % a for a in unknown), "is" if len(unknown) == 1 else "are", ", ".join(cls.species)))
+        if len(set(st)) != len(st):
+            raise ModelDefinitionError("%s.steady_species has duplicates" % name)
+        if len(st) > MAX_STEADY:
+            raise ModelDefinitionError("%s: %d steady species; the matrix of an iteration lives in registers: at most %d "
+                                       "(MAX_STEADY)" % (name, len(st), MAX_STEADY))
+        fn = getattr(cls, "steady_rate", None)
+        if fn is None:
+            raise ModelDefinitionError("%s declares steady_species without steady_rate: the steady state is defined by "
+                                       "steady_rate(self, y, p, c) == 0" % name)
+        required = [q for q in inspect.signature(fn).parameters.values()
+                    if q.default is q.empty and q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD)] if callable(fn) else []
+        if len(required) != 4:
+            raise ModelDefinitionError("%s.steady_rate must be a function steady_rate(self, y, p, c): it sees the species, the "
+                                       "effective parameters and the treatments -- no t" % name)
+        k = cls.steady_steps
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_STEADY_STEPS:
+            raise ModelDefinitionError("%s.steady_steps = %r; the steady state is approached by a fixed number of iterations, an "
+                                       "int in 1 .. %d (MAX_STEADY_STEPS)" % (name, k, MAX_STEADY_STEPS))
+        for attr, low, strict, what in (("steady_first_step", 0.0, True, "the first pseudo-time step is a finite number above 0"),
+                                        ("steady_growth", 1.0, False, "the pseudo-time step grows by a finite factor of at least 1")):
+            v = getattr(cls, attr)
+            if (isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v)
+                    or not math.isfinite(float(np.float32(v))) or (float(np.float32(v)) <= low if strict else float(np.float32(v)) < low)):
+                raise ModelDefinitionError("%s.%s = %r; %s (as a float32)" % (name, attr, v, what))
+        if getattr(cls, "algebraic", None):
+            raise ModelDefinitionError("%s has algebraic variables and steady_species: steady_rate cannot read an algebraic "
+                                       "variable and the two solves are not combined in this version" % name)
     if nets is None:
         return
     if not isinstance(nets, dict) or not all(isinstance(k, str) and k.isidentifier() and isinstance(v, Network)

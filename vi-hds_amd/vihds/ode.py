@@ -145,12 +145,14 @@ def x_predict_on_demand(request, ode, config):
     such a model always stores x_predict, and the summaries take it from that buffer; so does a model with a precision map
     of its own -- its precision rows go to vihds_iw_summaries, which takes x_predict as a buffer -- and a model with a state
     jump (has_jump, vihds/modelgen.py): what is read afterwards is the buffer its kernel scored, the left limits.  A model
-    with a start map or a lead-in phase (has_start / has_lead_in) likewise: its evaluation stores what its kernel scored; a
+    with a start map, steady species or a lead-in phase (has_start / n_steady_species / has_lead_in) likewise: its evaluation
+    stores what its kernel scored; a
     model with process noise (has_diffusion) likewise: the stored buffers are the realisation its kernel scored."""
     return ((not torch.is_grad_enabled() or request.general_tail)
             and bool(default_get_value(config.params, "lazy_x_predict", True)) and ode.observe_kind != "custom"
             and ode.precision_kind != "custom" and not getattr(ode, "has_jump", False)
             and not getattr(ode, "has_start", False) and not getattr(ode, "has_lead_in", False)
+            and not getattr(ode, "n_steady_species", 0)
             and not getattr(ode, "has_diffusion", False))
 
 

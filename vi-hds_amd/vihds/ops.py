@@ -105,6 +105,11 @@ class OdeProblemSpec:
                 "model '%s' has a state jump at the observation points, applied between two steps of a fixed-grid scheme: the "
                 "adaptive solver '%s' integrates on a grid of its own and is not available to it (fixed-grid solvers: %s)" % (
                     model, solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
+        if solver in hip.ADAPTIVE_SOLVERS and model in hip.GENERATED_STEADY:  # (likewise)
+            raise NotImplementedError(
+                "model '%s' has steady species (steady_species), which only the kernels of the fixed-grid schemes solve for "
+                "before the first step: the adaptive solver '%s' is not available to it (fixed-grid solvers: %s)" % (
+                    model, solver, ", ".join(sorted(set(hip.SOLVERS) - set(hip.ADAPTIVE_SOLVERS)))))
         if solver in hip.ADAPTIVE_SOLVERS and (model in hip.GENERATED_START or model in hip.GENERATED_LEAD_IN):  # (likewise)
             raise NotImplementedError(
                 "model '%s' has %s, which only the kernels of the fixed-grid schemes run before the first observation point: "
